@@ -10,22 +10,30 @@ survivors and rewrites its 4 erased shards). Inputs are synthetic splitmix64
 stripes generated in HBM before the timed region.
 
 value = data-payload GiB/s over all ranks: (encode 10*L + decode 10*L bytes
-per stripe) * stripes * ranks / max-over-ranks step time. After the timed
-region (outside the clock) every rank checks its WHOLE batch against the C
-oracle (oracle/corc.py: data, parity and the rebuilt shards of every stripe)
-and its mixed leg's stripes; `verified` is the AND over ranks. Multi-GPU: one
-process per GPU, independent stripe batches per rank (seed base
-0x5EED0000 + rank*2^20), no data-path collective ("scaling": "weak"); the
-only cross-rank traffic is the barrier and the max-reduce of the timings
-(gloo, host side).
+per stripe) * stripes * ranks / max-over-ranks step time; ms_per_step is that
+time per timed step. Multi-GPU: one process per GPU, independent stripe
+batches per rank (seed base 0x5EED0000 + rank*2^20), no data-path collective
+("scaling": "weak"); the only cross-rank traffic is the barrier and the
+max-reduce of the timings (gloo, host side).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only that: set up, warm up, time the K steps, print the
+line (the per-launch and roofline figures in it come from the HIP events of
+the timed steps themselves). --full adds, after the timed region (outside
+the clock): every rank checks its WHOLE batch against the C oracle
+(oracle/corc.py: data, parity and the rebuilt shards of every stripe) and
+its mixed leg's stripes, `verified` being the AND over ranks; the
+packed-layout pass; the end-to-end and mixed-workload legs; the CPU
+baselines. --dump-outputs DIR writes a fixed, seeded sample of what the last
+timed step left in the batch (dump_outputs) as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   Without WORLD_SIZE in the environment and N > 1, this process is only a
   launcher: it makes no GPU call, starts N ranks with torch.distributed.run
   (127.0.0.1 rendezvous) and exits with their status. Under an external
   launcher WORLD_SIZE must equal N. --dry-run runs the launcher and the
   control plane (seeds, barrier, max-over-ranks timing, aggregation) with a
-  GPU-free stand-in step (tests/test_bench_launcher.py).
+  GPU-free stand-in step, with --full also stand-in records of the host legs,
+  the verification and the CPU baselines (tests/test_bench_launcher.py).
 """
 from __future__ import annotations
 
@@ -623,6 +631,49 @@ def packed_layout_pass(rs, S: int, L: int, masks, rank: int, reps: int) -> dict:
             "data_GiB_s": round(2 * S * K_DATA * L / ((enc + dec) * 1e-3) / 2**30, 2)}
 
 
+DUMP_STRIPES, DUMP_WINDOW = 256, 4096  # per array: 256 x 4 x 4096 float32 = 16 MiB
+
+
+def dump_sample(n_stripes: int, shard_len: int, world: int = 1, rank: int = 0):
+    """The fixed sample --dump-outputs writes: which stripes, and the byte
+    window [off, off + w) taken of each of their shards. Seeded by the rank
+    alone, so two builds run with the same arguments write the same places.
+    The first stripe's window is the shard's head and the second's its tail."""
+    rng = np.random.default_rng(0xD0D0 + rank)
+    n = min(n_stripes, max(1, DUMP_STRIPES // world))
+    idx = np.sort(rng.choice(n_stripes, n, replace=False))
+    w = min(shard_len, DUMP_WINDOW)
+    offs = rng.integers(0, shard_len - w + 1, n)
+    offs[0] = 0
+    offs[-1 if n == 1 else 1] = shard_len - w
+    return idx, offs, w
+
+
+def dump_outputs(out_dir: str, t, masks_host: np.ndarray, world: int, rank: int) -> dict:
+    """What the last timed step computed, as a caller of encode_batch /
+    reconstruct_batch receives it in the batch `t`: of dump_sample's stripes,
+    the 4 parity shards the encode wrote (encode_parity) and the 4 erased
+    shards the reconstruct rewrote, in shard order (reconstruct_rebuilt).
+    Byte values as float32, [stripes, 4, window]; rank r > 0 of a multi-rank
+    job writes <name>_rank<r>.npy."""
+    import torch
+    S, L = t.shape[0], t.shape[2]
+    idx, offs, w = dump_sample(S, L, world, rank)
+    parity, rebuilt = [], []
+    for s, o in zip(idx.tolist(), offs.tolist()):
+        erased = [i for i in range(N_TOTAL) if not (int(masks_host[s]) >> i) & 1]
+        parity.append(t[s, K_DATA:, o:o + w])
+        rebuilt.append(t[s, erased, o:o + w])
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    written = {}
+    for name, parts in (("encode_parity", parity), ("reconstruct_rebuilt", rebuilt)):
+        a = torch.stack(parts).cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[f"{name}{suffix}"] = list(a.shape)
+    return written
+
+
 def init_control_plane() -> None:
     """gloo process group for the barrier / max-reduce / gather of host
     scalars. gloo prints its connection report on stdout, which carries only
@@ -651,10 +702,17 @@ def parse_args(argv=None):
     ap.add_argument("--base-align", type=int, default=0,
                     help="start the batch at a multiple of this many bytes inside an over-allocation "
                          "(power of two; 0 = the allocator's base; measurement, VERDICT r04 item 1(c))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the whole-batch check against the C oracle, the "
+                         "packed-layout pass, the end-to-end and mixed-workload legs, the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write a fixed, seeded sample of what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end and mixed-workload sections")
-    ap.add_argument("--no-packed", action="store_true", help="skip the packed-layout pass beside the padded batch")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the end-to-end and mixed-workload sections")
+    ap.add_argument("--no-packed", action="store_true",
+                    help="--full without the packed-layout pass beside the padded batch")
     ap.add_argument("--e2e-multi-child", default="",
                     help="internal: the multi-GPU end-to-end leg in its own process over this device list "
                          "(e.g. 0,1,2,3; 0,0 rehearses it on one GPU)")
@@ -676,6 +734,9 @@ def main(argv=None):
         return e2e_multi_child_main([int(d) for d in args.e2e_multi_child.split(",")])
     if args.gpus < 1:
         log("bench.py: --gpus must be >= 1")
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        log("bench.py: --steps must be >= 1 and --warmup >= 0")
         return 2
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -719,43 +780,46 @@ def dry_run(args, world: int, rank: int, local_rank: int) -> int:
         time.sleep(step)
     barrier()
     wall = time.perf_counter() - t0
-    chk_ok = rank != args.dry_fail_rank  # stand-in for the rank's oracle verification
     t_job = reduce_max(wall, world)
     per_rank = gather({"rank": rank, "local_rank": local_rank, "world_size": int(os.environ.get("WORLD_SIZE", "1")),
                        "seed_base": rank_seed_base(rank), "wall_s": wall, "pid": os.getpid(),
                        "step_ms": step * 1e3, "masks_head": erasure_masks(4, rank).tolist()}, world)
-    # host legs: stand-in records with the real records' shape (rank r moves
-    # (r + 1) GiB in (r + 1) x dry_step_ms per phase), assembled as run_rank does
-    barrier()
-    e0 = time.time()
-    time.sleep(step)
-    e1 = time.time()
-    time.sleep(step)
-    e2 = time.time()
-    gib = (rank + 1) * 2**30
-    e2e = {"stand_in": True, "raw": {"data_bytes": gib, "encode": [e0, e1], "decode": [e1, e2]}}
-    barrier()
-    w0 = time.time()
-    time.sleep(step)
-    mixed = {"stand_in": True, "verification": {"ok": chk_ok},
-             "raw": {"payload_bytes": gib, "e2e": [w0, time.time()], "device_s": step}}
-    e2e_all, mixed_all = gather(e2e, world), gather(mixed, world)
-    chk_ok = chk_ok and all(m["verification"]["ok"] for m in mixed_all)
-    extras = assemble_host_legs(e2e_all, mixed_all, world)
-    chk_ok = reduce_max(0.0 if chk_ok else 1.0, world) == 0.0
+    chk_ok, extras = None, {}  # a plain run checks nothing and runs no host leg
+    if args.full:
+        chk_ok = rank != args.dry_fail_rank  # stand-in for the rank's oracle verification
+        # host legs: stand-in records with the real records' shape (rank r moves
+        # (r + 1) GiB in (r + 1) x dry_step_ms per phase), assembled as run_rank does
+        barrier()
+        e0 = time.time()
+        time.sleep(step)
+        e1 = time.time()
+        time.sleep(step)
+        e2 = time.time()
+        gib = (rank + 1) * 2**30
+        e2e = {"stand_in": True, "raw": {"data_bytes": gib, "encode": [e0, e1], "decode": [e1, e2]}}
+        barrier()
+        w0 = time.time()
+        time.sleep(step)
+        mixed = {"stand_in": True, "verification": {"ok": chk_ok},
+                 "raw": {"payload_bytes": gib, "e2e": [w0, time.time()], "device_s": step}}
+        e2e_all, mixed_all = gather(e2e, world), gather(mixed, world)
+        chk_ok = chk_ok and all(m["verification"]["ok"] for m in mixed_all)
+        extras = assemble_host_legs(e2e_all, mixed_all, world)
+        chk_ok = reduce_max(0.0 if chk_ok else 1.0, world) == 0.0
     if rank == 0:
         payload = 2 * S * K_DATA * L
         out = {"metric": "dry run (no GPU): launcher and control plane only", "dry_run": True,
                "value": round(job_throughput(payload, args.steps, world, t_job), 4), "unit": "GiB/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(t_job / args.steps * 1e3, 4), "scaling": "weak", "verified": chk_ok,
+               "ms_per_step": round(t_job / args.steps * 1e3, 4), "scaling": "weak", "full": args.full,
+               "verified": chk_ok,
                "rank_seed_bases": [r["seed_base"] for r in per_rank], "ranks": per_rank}
         out.update(scaling_fields(out["value"], world, per_rank))
         out.update(extras)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out.update(cpu_baseline_legs(args.cpu_seconds, os.sched_getaffinity(0), stand_in=True))
         print(json.dumps(out), flush=True)
-    return 0 if chk_ok else 3
+    return 3 if chk_ok is False else 0
 
 
 def run_rank(args, world: int, rank: int, local_rank: int) -> int:
@@ -781,7 +845,8 @@ def run_rank(args, world: int, rank: int, local_rank: int) -> int:
     t = B.empty_stripes(S, N_TOTAL, L, shard_pad=args.shard_pad, base_align=args.base_align)
     base_alignment = B.address_alignment(t.data_ptr())
     B.fill_stripes_splitmix(t, K_DATA, rank_seed_base(rank))  # same bytes as a packed batch
-    masks = torch.from_numpy(erasure_masks(S, rank)).cuda()
+    masks_host = erasure_masks(S, rank)
+    masks = torch.from_numpy(masks_host).cuda()
     stream = torch.cuda.current_stream()
 
     def barrier():
@@ -812,40 +877,46 @@ def run_rank(args, world: int, rank: int, local_rank: int) -> int:
     enc_med, dec_med = float(np.median(enc_steps)), float(np.median(dec_steps))
     t_job = reduce_max(wall, world)
 
-    # correctness of what was timed (outside the clock), the WHOLE batch: the
-    # erased shards of every stripe are zeroed and rebuilt by one more
-    # reconstruct launch, then every stripe is compared with the C oracle
-    # (data = its seed's splitmix64 stream, parity = the oracle's encode, the
-    # 4 rebuilt shards = the oracle's reconstruct from the same survivors)
-    from oracle import corc
-    v0 = time.perf_counter()
-    er = torch.zeros((S, N_TOTAL), dtype=torch.bool, device="cuda")
-    for i in range(N_TOTAL):
-        er[:, i] = (masks & (1 << i)) == 0
-    t[er] = 0
-    B.reconstruct_batch(rs, t, masks)
-    torch.cuda.synchronize()
-    del er
-    # the seeded-data check regenerates splitmix64 words, so it needs whole
-    # 8-byte words per shard; other lengths check parity and rebuilt shards only
-    seeds = rank_seed_base(rank) + np.arange(S, dtype=np.uint64) if L % 8 == 0 else None
-    bad = corc.check_device_batch(t, masks.cpu().numpy(), data_seeds=seeds)
-    chk_ok = not bad
-    verification = {"stripes_checked": S, "rebuilt_shards_checked": 4 * S, "mismatched_stripes": bad[:16],
-                    "data_seeds_checked": seeds is not None,
-                    "seconds": round(time.perf_counter() - v0, 2),
-                    "method": "erased shards zeroed and rebuilt, every stripe vs the C oracle (seeded data, "
-                              "encode, reconstruct from survivors), 16 threads"}
+    dumped = None
+    if args.dump_outputs:  # the batch as the last timed step left it, before anything else touches it
+        dumped = dump_outputs(args.dump_outputs, t, masks_host, world, rank)
+
+    chk_ok, verification = None, None  # a plain run compares nothing with the oracle
+    if args.full:
+        # correctness of what was timed (outside the clock), the WHOLE batch: the
+        # erased shards of every stripe are zeroed and rebuilt by one more
+        # reconstruct launch, then every stripe is compared with the C oracle
+        # (data = its seed's splitmix64 stream, parity = the oracle's encode, the
+        # 4 rebuilt shards = the oracle's reconstruct from the same survivors)
+        from oracle import corc
+        v0 = time.perf_counter()
+        er = torch.zeros((S, N_TOTAL), dtype=torch.bool, device="cuda")
+        for i in range(N_TOTAL):
+            er[:, i] = (masks & (1 << i)) == 0
+        t[er] = 0
+        B.reconstruct_batch(rs, t, masks)
+        torch.cuda.synchronize()
+        del er
+        # the seeded-data check regenerates splitmix64 words, so it needs whole
+        # 8-byte words per shard; other lengths check parity and rebuilt shards only
+        seeds = rank_seed_base(rank) + np.arange(S, dtype=np.uint64) if L % 8 == 0 else None
+        bad = corc.check_device_batch(t, masks_host, data_seeds=seeds)
+        chk_ok = not bad
+        verification = {"stripes_checked": S, "rebuilt_shards_checked": 4 * S, "mismatched_stripes": bad[:16],
+                        "data_seeds_checked": seeds is not None,
+                        "seconds": round(time.perf_counter() - v0, 2),
+                        "method": "erased shards zeroed and rebuilt, every stripe vs the C oracle (seeded data, "
+                                  "encode, reconstruct from survivors), 16 threads"}
     t_shard_stride = t.stride(1)
     del t
     packed = None
-    if args.shard_pad and not args.no_packed:
+    if args.full and args.shard_pad and not args.no_packed:
         torch.cuda.empty_cache()
         packed = packed_layout_pass(rs, S, L, masks, rank, max(3, args.steps // 2))
     enc_bytes = S * N_TOTAL * L                      # read 10 L + write 4 L per stripe
     dec_bytes = S * (K_DATA + 4) * L                 # read 10 survivors + write 4 erased
     per_rank = gather({"rank": rank, "device": device, "seed_base": rank_seed_base(rank), "numa": numa,
-                       "verification": verification,
+                       "verification": verification, "dumped": dumped,
                        "wall_s": round(wall, 6), "encode_ms": round(enc_ms, 4), "decode_ms": round(dec_ms, 4),
                        "encode_ms_median": round(enc_med, 4), "decode_ms_median": round(dec_med, 4),
                        "step_ms": enc_ms + dec_ms,
@@ -864,7 +935,8 @@ def run_rank(args, world: int, rank: int, local_rank: int) -> int:
         prof = {}  # the committed counters are of another batch size: no traffic figure for this one
 
     extras = {}
-    if not args.no_extras:
+    host_legs = args.full and not args.no_extras
+    if host_legs:
         # host-path legs on every rank at once (after one barrier), so at N > 1
         # the aggregate shows the shared host-memory / PCIe limit
         barrier()
@@ -876,11 +948,12 @@ def run_rank(args, world: int, rank: int, local_rank: int) -> int:
         chk_ok = chk_ok and all(m["verification"]["ok"] for m in mixed_all)
         extras = assemble_host_legs(e2e_all, mixed_all, world)
 
-    # every rank's verification counts (headline batch and mixed leg): the job
-    # is verified only if all are
-    chk_ok = reduce_max(0.0 if chk_ok else 1.0, world) == 0.0
+    if args.full:
+        # every rank's verification counts (headline batch and mixed leg): the
+        # job is verified only if all are
+        chk_ok = reduce_max(0.0 if chk_ok else 1.0, world) == 0.0
 
-    if world == 1 and not args.no_extras and torch.cuda.device_count() > 1:
+    if world == 1 and host_legs and torch.cuda.device_count() > 1:
         # one process, every visible GPU: one host call split over them
         # (hec_host_*_batch_multi, the in-process multi-GPU host path), run
         # in a child process with a time limit so that it cannot cost the
@@ -938,17 +1011,20 @@ def run_rank(args, world: int, rank: int, local_rank: int) -> int:
                        "data_GiB_s": round(S * K_DATA * L / (dec_ms * 1e-3) / 2**30, 1),
                        "frac": round(dec_gbps / HBM_PEAK_GBPS, 4),
                        "traffic": prof.get("decode_hbm_bytes_per_launch")},
+            "full": args.full,  # False: nothing below was checked or measured beyond the timed steps
             "packed_layout": packed,
             "verified": chk_ok,
             "verification": verification,
+            "dumped_outputs": dumped and {"dir": args.dump_outputs, "dtype": "float32", "arrays": dumped},
             "ranks": per_rank,
         }
         out.update(scaling_fields(out["value"], world, per_rank))
         out.update(extras)
-        if not args.no_cpu_baseline:  # every world size; the other ranks wait at main()'s closing barrier
+        if args.full and not args.no_cpu_baseline:
+            # every world size; the other ranks wait at main()'s closing barrier
             out.update(cpu_baseline_legs(args.cpu_seconds, allowed))
         print(json.dumps(out), flush=True)
-    return 0 if chk_ok else 3
+    return 3 if chk_ok is False else 0
 
 
 if __name__ == "__main__":

@@ -50,6 +50,31 @@ def test_single_rank_default_stays_in_process():
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 1 and len(out["ranks"]) == 1
+    # a plain run: the timed steps and the line, no check, host leg or CPU baseline
+    assert out["full"] is False and out["steps"] == 2 and out["verified"] is None
+    assert not {"end_to_end", "mixed", "cpu_baseline", "cpu_baseline_threads", "cpu_baseline_cores"} & set(out)
+
+
+def test_dump_sample_is_fixed_and_within_the_size_limit():
+    """--dump-outputs samples the same stripes and byte windows on every run
+    with the same arguments; the two float32 arrays of the default batch stay
+    under 64 MB together, at any world size."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    S, L = 4096, 1 << 20
+    idx, offs, w = bench.dump_sample(S, L)
+    idx2, offs2, w2 = bench.dump_sample(S, L)
+    assert np.array_equal(idx, idx2) and np.array_equal(offs, offs2) and w == w2
+    assert len(set(idx.tolist())) == len(idx) and 0 <= idx.min() and idx.max() < S
+    assert offs[0] == 0 and offs[1] == L - w and ((0 <= offs) & (offs + w <= L)).all()
+    assert 2 * len(idx) * 4 * w * 4 <= 64 * 10**6
+    for world in (2, 8):
+        per_rank = [bench.dump_sample(S, L, world, r) for r in range(world)]
+        assert sum(2 * len(i) * 4 * ww * 4 for i, _, ww in per_rank) <= 64 * 10**6
+        assert not np.array_equal(per_rank[0][0], per_rank[1][0])
+    idx, offs, w = bench.dump_sample(3, 100)  # shards shorter than the window: whole shards
+    assert sorted(idx.tolist()) == [0, 1, 2] and w == 100 and offs.tolist() == [0, 0, 0]
 
 
 def test_world_size_must_match_gpus():
@@ -97,8 +122,8 @@ def test_eight_rank_dry_run_assembles_the_node_line():
     sys.path.insert(0, ROOT)
     import bench
     steps, step_ms = 3, 10.0
-    r = _run(["--gpus", "8", "--dry-run", "--steps", str(steps), "--warmup", "1", "--dry-step-ms", str(step_ms)],
-             timeout=300)
+    r = _run(["--gpus", "8", "--dry-run", "--full", "--steps", str(steps), "--warmup", "1",
+              "--dry-step-ms", str(step_ms)], timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -184,7 +209,7 @@ def test_cpu_baseline_cores_sized_to_the_quota(monkeypatch):
 def test_dry_run_one_failing_rank_fails_the_job():
     """Verification is reduced over ranks: one rank's failed check makes the
     job's line say verified false and every rank exit 3."""
-    r = _run(["--gpus", "4", "--dry-run", "--steps", "2", "--warmup", "0", "--dry-step-ms", "1",
+    r = _run(["--gpus", "4", "--dry-run", "--full", "--steps", "2", "--warmup", "0", "--dry-step-ms", "1",
               "--dry-fail-rank", "2"], timeout=240)
     assert r.returncode != 0
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

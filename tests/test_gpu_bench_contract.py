@@ -19,7 +19,7 @@ KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 def test_bench_line_contract():
     S, L, steps = 64, 1 << 20, 3  # 0.9 GiB: larger than the 256 MB Infinity Cache
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stripes", str(S), "--shard-len", str(L),
-                        "--steps", str(steps), "--warmup", "1", "--no-extras", "--cpu-seconds", "0.4"],
+                        "--steps", str(steps), "--warmup", "1", "--full", "--no-extras", "--cpu-seconds", "0.4"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
@@ -48,6 +48,48 @@ def test_bench_line_contract():
     assert 0 < pk["encode_frac"] < 1 and 0 < pk["decode_frac"] < 1
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L", [65536, 65536 + 16])  # the bit-sliced encode kernel / the table one
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, L):
+    """A plain run (no --full) times its steps and prints the line: nothing
+    checked against the oracle, no packed pass, host leg or CPU baseline.
+    --dump-outputs writes the seeded sample of the batch as the last timed
+    step left it, float32; every sampled parity and rebuilt shard equals the
+    C oracle's codeword of that stripe's seeded data."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import corc
+    S, steps = 24, 2
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stripes", str(S),
+                        "--shard-len", str(L), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, p.stdout[-3000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == steps and d["verified"] is None and d["verification"] is None
+    assert d["packed_layout"] is None
+    assert not {"cpu_baseline", "cpu_baseline_threads", "end_to_end", "mixed"} & set(d)
+    assert d["value"] == pytest.approx(2 * S * 10 * L / (d["ms_per_step"] * 1e-3) / 2**30, rel=0.01)
+    assert sorted(f.name for f in out.iterdir()) == ["encode_parity.npy", "reconstruct_rebuilt.npy"]
+    parity, rebuilt = np.load(out / "encode_parity.npy"), np.load(out / "reconstruct_rebuilt.npy")
+    idx, offs, w = bench.dump_sample(S, L)
+    assert w == 4096 and len(idx) == S and offs[0] == 0 and offs[1] == L - w  # head and tail of a shard
+    assert parity.dtype == np.float32 and parity.shape == rebuilt.shape == (S, 4, w)
+    assert d["dumped_outputs"]["arrays"] == {"encode_parity": [S, 4, w], "reconstruct_rebuilt": [S, 4, w]}
+    masks = bench.erasure_masks(S, 0)
+    for j, (s, o) in enumerate(zip(idx.tolist(), offs.tolist())):
+        data = corc.splitmix64_bytes(bench.rank_seed_base(0) + s, 10 * L).reshape(1, 10, L)
+        word = np.concatenate([data[0], corc.encode_stripes(data)[0]])  # the stripe's 14 shards
+        erased = [i for i in range(14) if not (int(masks[s]) >> i) & 1]
+        assert np.array_equal(parity[j], word[10:, o:o + w].astype(np.float32)), s
+        assert np.array_equal(rebuilt[j], word[erased, o:o + w].astype(np.float32)), s
 
 
 @pytest.mark.gpu
@@ -92,8 +134,8 @@ def test_bench_base_align_and_odd_shard_length():
     for extra, L, seeds in ((["--base-align", str(1 << 30)], 1 << 20, True),
                             (["--shard-pad", "0"], 4096 + 4, False)):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stripes", "32", "--shard-len", str(L),
-                            "--steps", "2", "--warmup", "1", "--no-extras", "--no-packed", "--no-cpu-baseline",
-                            *extra], capture_output=True, text=True, timeout=300, cwd=ROOT)
+                            "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-packed",
+                            "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=300, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-3000:]
         d = json.loads([x for x in p.stdout.splitlines() if x.strip()][-1])
         assert d["verified"] is True and d["verification"]["data_seeds_checked"] is seeds
