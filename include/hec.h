@@ -186,6 +186,13 @@ int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const s
  * Shard (stripe s, shard i) lives at base + s*stripe_stride + i*shard_stride.
  * Pointers are device pointers on the current HIP device; stream is a
  * hipStream_t (NULL = default stream). Calls are asynchronous.
+ * Any strides that keep shards apart are supported, on device and host
+ * batches alike: stripe-major [S][shards][L] with or without padding and gaps
+ * between stripes, shard-major [shards][S][L] (stripe stride below shard
+ * stride), different layouts for data and parity (and separate buffers), odd
+ * bases and strides (those take the generic kernel). A call writes the parity
+ * or erased shard ranges and no other byte: not the gaps, not the survivors,
+ * not a skipped stripe (tests/test_gpu_footprint.py compares whole buffers).
  * Layout (speed only): with 1 MiB shards, a 64 KiB gap after each shard
  * (shard_stride = shard_len + 65536) runs encode and decode ~1.6% faster than
  * packed shards (the bench's batch is laid out so). */
