@@ -29,7 +29,6 @@
 #include <deque>
 #include <functional>
 #include <future>
-#include <map>
 #include <string>
 #include <chrono>
 #include <thread>
@@ -58,25 +57,7 @@ struct Fd {
     }
 };
 
-// ---------------------------------------------------------------------------
-// First-error record shared by the pipeline's threads.
-// ---------------------------------------------------------------------------
-struct ErrorSlot {
-    std::mutex mu;
-    std::atomic<int> code{HEC_OK};
-    std::string detail;
-    ErrorValues values;  // hec_last_error_values of the first failure
-    void set(int c, const std::string& d, const ErrorValues& v = ErrorValues{}) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (code.load() == HEC_OK) {
-            detail = d;
-            values = v;
-            code.store(c);
-        }
-    }
-    bool failed() const { return code.load() != HEC_OK; }
-};
-
+// An I/O failure (errno) as the first-error record of the pipeline's threads.
 void io_error(ErrorSlot& e, const std::string& what) {
     const int err = errno;
     ErrorValues v;
@@ -219,8 +200,8 @@ struct Job {
 };
 
 struct Slot {
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
+    PinnedBuf<> host;
+    DeviceBuf<> dev;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     bool busy = false;
@@ -250,19 +231,9 @@ class FilePipeline {
                 HEC_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
                 HEC_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
             }
-            if (host_bytes > host_cap_) {
-                if (s.host) HEC_HIP(hipHostFree(s.host));
-                s.host = nullptr;
-                HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&s.host), host_bytes));
-            }
-            if (dev_bytes > dev_cap_) {
-                if (s.dev) HEC_HIP(hipFree(s.dev));
-                s.dev = nullptr;
-                HEC_HIP(hipMalloc(reinterpret_cast<void**>(&s.dev), dev_bytes));
-            }
+            HEC_TRY(s.host.reserve(host_bytes));
+            HEC_TRY(s.dev.reserve(dev_bytes));
         }
-        host_cap_ = std::max(host_cap_, host_bytes);
-        dev_cap_ = std::max(dev_cap_, dev_bytes);
         if (!writer_.joinable())
             writer_ = std::thread([this] { writer_loop(); });
         return HEC_OK;
@@ -295,7 +266,7 @@ class FilePipeline {
         int rc = gpu(s, job);
         clk_.submit_ns += StageClock::now() - t2;
         if (rc) {
-            err_.set(rc, hec_last_error_detail(), last_error_values());
+            err_.capture(rc);
             return release(si);
         }
         {
@@ -317,13 +288,7 @@ class FilePipeline {
                          clk_.slot_wait_ns * 1e-9, clk_.read_ns * 1e-9, clk_.submit_ns * 1e-9,
                          clk_.gpu_wait_ns * 1e-9, clk_.write_ns * 1e-9);
         clk_.reset();
-        int code = err_.code.load();
-        std::string detail = err_.detail;
-        const ErrorValues values = err_.values;
-        err_.code.store(HEC_OK);
-        err_.detail.clear();
-        err_.values = ErrorValues{};
-        return code ? fail_with(code, detail, values) : HEC_OK;
+        return err_.raise();
     }
     ErrorSlot& errors() { return err_; }
 
@@ -384,7 +349,6 @@ class FilePipeline {
     std::condition_variable cv_;
     std::deque<std::pair<int, Job>> wq_;
     uint64_t inflight_ = 0;
-    uint64_t host_cap_ = 0, dev_cap_ = 0;
     uint64_t next_ = 0;
     int dev_id_ = 0;
     ErrorSlot err_;
@@ -394,27 +358,21 @@ class FilePipeline {
 // One pipeline per device, created on first use and intentionally never
 // destroyed (its threads and HIP resources live for the process; a static
 // destructor could run after the HIP runtime is gone).
-struct PipelineLease {
+struct DevicePipeline {
+    std::mutex mu;  // one file operation per device at a time
+    FilePipeline pipe;
+};
+struct FileLease {
     std::unique_lock<std::mutex> lock;
     FilePipeline* pipe = nullptr;
 };
-int lease_pipeline(uint64_t host_bytes, uint64_t dev_bytes, PipelineLease& out) {
-    static std::mutex reg_mu;
-    static std::map<int, std::pair<std::mutex*, FilePipeline*>>* reg =
-        new std::map<int, std::pair<std::mutex*, FilePipeline*>>();
+int lease_pipeline(uint64_t host_bytes, uint64_t dev_bytes, FileLease& out) {
     int dev;
-    int rc = current_device(&dev);
-    if (rc) return rc;
-    std::pair<std::mutex*, FilePipeline*> e;
-    {
-        std::lock_guard<std::mutex> lk(reg_mu);
-        auto& slot = (*reg)[dev];
-        if (!slot.first) slot = {new std::mutex(), new FilePipeline()};
-        e = slot;
-    }
-    out.lock = std::unique_lock<std::mutex>(*e.first);  // one file operation per device at a time
-    out.pipe = e.second;
-    return e.second->ensure(host_bytes, dev_bytes);
+    HEC_TRY(current_device(&dev));
+    DevicePipeline* e = per_device<DevicePipeline>(dev);
+    out.lock = std::unique_lock<std::mutex>(e->mu);
+    out.pipe = &e->pipe;
+    return out.pipe->ensure(host_bytes, dev_bytes);
 }
 
 struct Rs104 {
@@ -549,9 +507,9 @@ static int write_ec_files_impl(const std::string& base, uint64_t buf_size, uint6
 
     const uint64_t T = n_large ? std::min<uint64_t>(large, kLargeSlice) : 0;                    // large-row slice
     const uint64_t B = std::min(n_small, std::max<uint64_t>(1, kBatchBytes / small_row));  // small rows per job
-    const uint64_t data_cap = (std::max(T * K, B * small_row) + 255) / 256 * 256;
+    const uint64_t data_cap = round_up(std::max(T * K, B * small_row), 256);
     const uint64_t par_cap = std::max<uint64_t>(256, std::max(T * M, B * small * M));
-    PipelineLease lease;
+    FileLease lease;
     if ((rc = lease_pipeline(data_cap + par_cap, data_cap + par_cap, lease))) return rc;
     FilePipeline& pipe = *lease.pipe;
     const DevicePlanSet* enc = &gd->encode;
@@ -694,7 +652,7 @@ static int rebuild_ec_files_impl(const std::string& base, uint32_t* ids, size_t*
         }
         const uint64_t B = std::max<uint64_t>(1, std::min<uint64_t>(rows, kBatchBytes / (K * row_size)));
         const uint64_t slot = B * row_size;  // bytes per shard slot: layout [14][B rows]
-        PipelineLease lease;
+        FileLease lease;
         if ((rc = lease_pipeline(slot * N, slot * N, lease))) return rc;
         FilePipeline& pipe = *lease.pipe;
         const DevicePlanSet* psp = &ps;

@@ -1,5 +1,7 @@
-// Internal declarations shared by the C ABI (hec_api.cpp) and the file layer
-// (ec_files.cpp).
+// Internal declarations of libhec, shared by every csrc/*.cpp: the error
+// record (errors.cpp), staging buffers, the per-device registry and slot
+// leases, the host worker pool (host_pool.cpp), plans and per-geometry device
+// state (plans.cpp) and the per-call host paths' scratch (host_calls.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -9,6 +11,7 @@
 #include <cerrno>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -43,6 +46,40 @@ int fail_errno(int code, const std::string& what, int err);
 int fail_with(int code, const std::string& detail, const ErrorValues& v);
 ErrorValues last_error_values();
 
+// First failure among several threads (host-pool workers, the file pipeline's
+// reader and writer): failure detail and values are thread-local, so a worker
+// captures its own and the caller's thread re-raises them.
+struct ErrorSlot {
+    std::mutex mu;
+    std::atomic<int> code{HEC_OK};
+    std::string detail;
+    ErrorValues values;
+    void set(int c, const std::string& d, const ErrorValues& v = ErrorValues{}) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (code.load() == HEC_OK) {
+            detail = d;
+            values = v;
+            code.store(c);
+        }
+    }
+    // Record status c of a call that just failed on the calling thread.
+    void capture(int c) { set(c, hec_last_error_detail(), last_error_values()); }
+    bool failed() const { return code.load() != HEC_OK; }
+    // Re-raise the first failure on the calling thread and clear the record
+    // (HEC_OK, the thread's record untouched, when there was none).
+    int raise() {
+        std::lock_guard<std::mutex> lk(mu);
+        const int c = code.exchange(HEC_OK);
+        if (!c) return HEC_OK;
+        fail_with(c, detail, values);
+        detail.clear();
+        values = ErrorValues{};
+        return c;
+    }
+};
+
+constexpr uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
 // Strided-batch geometry sanity (the C ABI sees only pointers, so sizes cannot
 // be checked): shards of a stripe and stripes of a shard must not overlap,
 // and the batch's byte extent must not wrap the address space.
@@ -58,6 +95,19 @@ inline int check_strided(const char* what, uint32_t shards, uint64_t stripe_stri
         __builtin_add_overflow(a, b, &e) || __builtin_add_overflow(e, len, &e))
         return fail(HEC_ERR_INVALID_ARGUMENT, std::string(what) + ": batch extent overflows");
     return HEC_OK;
+}
+// Prologue of the strided batch entry points (hec_gpu_*_batch, hec_host_*_batch,
+// hec_host_*_batch_multi): the null / empty-shard checks, and an encode's two
+// stride checks. What an entry point does between and after them is its own.
+inline int check_batch_args(const hec_rs* rs, const void* a, const void* b, uint64_t len) {
+    if (!rs || !a || !b) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    return HEC_OK;
+}
+inline int check_encode_strides(const hec_rs* rs, uint64_t data_stripe, uint64_t data_shard, uint64_t parity_stripe,
+                                uint64_t parity_shard, uint64_t len, uint32_t n_stripes) {
+    if (int rc = check_strided("data", uint32_t(rs->k), data_stripe, data_shard, len, n_stripes)) return rc;
+    return check_strided("parity", uint32_t(rs->m), parity_stripe, parity_shard, len, n_stripes);
 }
 int hip_fail(hipError_t e, const char* what);
 
@@ -88,6 +138,52 @@ int pinned_alloc(void** p, size_t bytes);
         if (e_ != hipSuccess) return ::hec::hip_fail(e_, #call); \
     } while (0)
 
+// Staging buffer of T, in device memory (hipMalloc) or pinned host memory
+// (pinned_alloc), grown on demand. No destructor: its owners live for the
+// process (a static destructor could run after the HIP runtime is gone);
+// owners that do end call release().
+template <typename T, bool Pinned>
+struct StagingBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    StagingBuf() = default;
+    StagingBuf(const StagingBuf&) = delete;
+    StagingBuf& operator=(const StagingBuf&) = delete;
+    operator T*() const { return p; }
+    // At least `bytes`: nothing when it fits; otherwise the old allocation is
+    // freed first (the peak is never old + new), then max(bytes, floor) is
+    // allocated. Empty (null, cap 0) after a failure.
+    int reserve(size_t bytes, size_t floor = 0) {
+        if (bytes <= cap) return HEC_OK;
+        release();
+        const size_t want = std::max(bytes, floor);
+        void* q = nullptr;
+        if (Pinned) HEC_TRY(pinned_alloc(&q, want));
+        else HEC_HIP(hipMalloc(&q, want));
+        p = static_cast<T*>(q);
+        cap = want;
+        return HEC_OK;
+    }
+    void release() {
+        if (p && (Pinned ? hipHostFree(p) : hipFree(p)) != hipSuccess) (void)hipGetLastError();
+        p = nullptr;
+        cap = 0;
+    }
+};
+template <typename T = uint8_t>
+using DeviceBuf = StagingBuf<T, false>;
+template <typename T = uint8_t>
+using PinnedBuf = StagingBuf<T, true>;
+// Buffers sized together (a pipeline's slots): when the last one, allocated
+// last, does not fit, all are freed before any is allocated.
+template <typename B, size_t N>
+int reserve_all(B (&bufs)[N], size_t bytes) {
+    if (bytes <= bufs[N - 1].cap) return HEC_OK;
+    for (B& b : bufs) b.release();
+    for (B& b : bufs) HEC_TRY(b.reserve(bytes));
+    return HEC_OK;
+}
+
 // Host-side plan list, uploaded as one DevicePlanSet.
 struct HostPlans {
     std::vector<DevPlan> plans;
@@ -104,11 +200,8 @@ struct HostPlans {
 
 // Device copy of a HostPlans (+ optional mask LUT).
 struct DevicePlanSet {
-    DevPlan* plans = nullptr;
-    uint32_t* tabs = nullptr;
-    uint32_t* idx = nullptr;
-    uint32_t* lut = nullptr;
-    size_t cap_plans = 0, cap_tabs = 0, cap_idx = 0, cap_lut = 0;
+    DeviceBuf<DevPlan> plans;
+    DeviceBuf<uint32_t> tabs, idx, lut;
     bool fast104 = false;  // RS(10,4) set with fixed 4-row tables (rs104_kernel eligible)
     uint32_t lut_bits = 0; // total shards the LUT covers (2^lut_bits entries)
     int upload(const HostPlans& hp, const std::vector<uint32_t>* lut_host, hipStream_t s);
@@ -159,28 +252,22 @@ std::atomic<uint64_t>& completion_flag_max();
 struct Scratch {
     std::mutex mu;
     hipStream_t stream = nullptr;
-    uint8_t* dbuf = nullptr;
-    size_t dcap = 0;
-    uint8_t* hbuf = nullptr;  // pinned staging for small calls (one H2D + one D2H)
-    size_t hcap = 0;
+    DeviceBuf<> dbuf;  // reserved with floor kStagingFloor
+    PinnedBuf<> hbuf;  // pinned staging for small calls (one H2D + one D2H), same floor
     DevicePlanSet adhoc;
     Completion done;
     int init();
-    int reserve(size_t bytes);
-    int reserve_host(size_t bytes);
-    void trim_large();  // free staging above 64 MiB (end of a call, slot still held)
+    void end_call(bool burst);  // a burst slot frees staging above kStagingKeep
 };
+constexpr size_t kStagingFloor = size_t(16) << 20;
+constexpr size_t kMetaFloor = size_t(1) << 20;
 // Slots created beyond the first kWarmSlots of a pool (bursts of concurrent
-// calls) free their large staging when their call ends, so the steady
-// footprint per device is that of kWarmSlots slots, not kScratchSlots.
+// calls) free their large staging when their call ends (S::end_call), so the
+// steady footprint per device is that of kWarmSlots slots, not kScratchSlots:
+// a burst of large per-call encodes (say 1 GiB shards: 14 GiB of HBM each)
+// must not stay resident in every slot for the life of the process.
 constexpr size_t kWarmSlots = 2;
-struct ScratchTrim {
-    Scratch* sc;
-    bool on;
-    ~ScratchTrim() {
-        if (on) sc->trim_large();
-    }
-};
+constexpr size_t kStagingKeep = size_t(64) << 20;
 // Drains a stream when its scope ends, whatever the return path. For calls
 // that queue copies or kernels onto CALLER memory: an error return between
 // two enqueues must not leave that work in flight once the caller, told the
@@ -197,16 +284,24 @@ struct StreamDrain {
 // overlap on the GPU instead of queueing behind one mutex (SURVEY.md §8b:
 // reentrant, a stream per call). Free slots are taken first; a new slot is
 // created while fewer than kScratchSlots exist; past that a call waits for
-// one. The lease holds the slot's mutex until it is destroyed.
+// one. The lease holds the slot's mutex until it is destroyed, and ends the
+// call itself: S::end_call(burst slot?) runs with the mutex still held.
 constexpr int kScratchSlots = 8;
 template <typename S>
 struct Lease {
     S* sc = nullptr;
     std::unique_lock<std::mutex> lk;
     size_t index = 0;  // the slot's creation order in its pool
+    Lease() = default;
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    S* operator->() const { return sc; }
+    ~Lease() {
+        if (sc) sc->end_call(index >= kWarmSlots);
+    }
 };
-// Per-device pool of S (S has `std::mutex mu` and `int init()`, called once
-// when a slot is created).
+// Per-device pool of S. S has `std::mutex mu`, `int init()` (called once when
+// a slot is created: its streams) and `void end_call(bool burst)`.
 template <typename S>
 struct SlotPool {
     std::mutex mu;
@@ -240,7 +335,24 @@ struct SlotPool {
         return 0;
     }
 };
-int lease_scratch(Lease<Scratch>& out);
+// One T per device, created on first use and never destroyed (threads and
+// HIP resources live for the process). create = false only looks it up.
+template <typename T>
+T* per_device(int dev, bool create = true) {
+    static std::mutex mu;
+    static auto* reg = new std::map<int, T*>();
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = reg->find(dev);
+    if (it != reg->end()) return it->second;
+    return create ? (*reg)[dev] = new T() : nullptr;
+}
+// Lease a slot of the calling thread's current device.
+template <typename S>
+int lease_slot(Lease<S>& out) {
+    int dev;
+    HEC_TRY(current_device(&dev));
+    return per_device<SlotPool<S>>(dev)->lease(out);
+}
 
 // Zero-copy switch (hec_set_host_zero_copy): pinned host memory the GPU can
 // address is coded by the kernels in place over PCIe instead of being copied.

@@ -7,8 +7,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
 
 #include "hec_internal.hpp"
 
@@ -18,141 +16,66 @@ namespace {
 constexpr int kDepth = 3;
 constexpr uint64_t kChunkBytes = 96ull << 20;  // target bytes of one chunk's 14 shards
 
+// One slot of the per-device pool of pipelines (SlotPool, hec_internal.hpp):
+// concurrent host batches on one device -- other threads, or two ranges of one
+// multi-device call on the same GPU -- each lease their own streams and slots.
+// Up to kScratchSlots (8) pipelines exist per device, but only the first
+// kWarmSlots (2) keep their staging between calls (end_call), so the steady
+// footprint per device is that of two pipelines (INTEGRATION.md §5 states the
+// worst case).
 struct Pipeline {
     std::mutex mu;
     hipStream_t streams[kDepth] = {};
-    uint8_t* slot[kDepth] = {};
-    uint32_t* mask_dev[kDepth] = {};
-    uint32_t* mask_host[kDepth] = {};  // pinned staging for per-chunk masks
-    size_t slot_cap = 0, mask_cap = 0;
+    DeviceBuf<> slot[kDepth];               // exact bytes, all reallocated together
+    DeviceBuf<uint32_t> mask_dev[kDepth];
+    PinnedBuf<uint32_t> mask_host[kDepth];  // pinned staging for per-chunk masks
     // pinned staging for pageable callers: two slots the kernels code in place
-    uint8_t* hslot[2] = {};
+    PinnedBuf<> hslot[2];
     hipEvent_t hdone[2] = {};
-    size_t hslot_cap = 0;
+    int init() {
+        for (auto& st : streams) HEC_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return HEC_OK;
+    }
+    int reserve(size_t slot_bytes, size_t n_masks) {
+        HEC_TRY(reserve_all(slot, slot_bytes));
+        HEC_TRY(reserve_all(mask_dev, n_masks * 4));
+        return reserve_all(mask_host, n_masks * 4);
+    }
     int reserve_host(size_t bytes) {
         if (!hdone[0])
             for (auto& e : hdone) HEC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (bytes <= hslot_cap) return HEC_OK;
-        for (auto& h : hslot) {
-            if (h) HEC_HIP(hipHostFree(h));
-            h = nullptr;
-        }
-        hslot_cap = 0;
-        for (auto& h : hslot) HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&h), bytes));
-        hslot_cap = bytes;
-        return HEC_OK;
+        return reserve_all(hslot, bytes);
     }
-    int init() { return HEC_OK; }  // streams and slots are made on first use (reserve)
     // Staging bytes held (pinned host, device).
     uint64_t pinned_bytes() const {
-        return (hslot[0] ? 2 * hslot_cap : 0) + (mask_host[0] ? uint64_t(kDepth) * mask_cap * 4 : 0);
+        uint64_t b = hslot[0].cap + hslot[1].cap;
+        for (auto& m : mask_host) b += m.cap;
+        return b;
     }
     uint64_t device_bytes() const {
-        return (slot[0] ? uint64_t(kDepth) * slot_cap : 0) + (mask_dev[0] ? uint64_t(kDepth) * mask_cap * 4 : 0);
+        uint64_t b = 0;
+        for (int i = 0; i < kDepth; ++i) b += slot[i].cap + mask_dev[i].cap;
+        return b;
     }
-    // Free the large staging (the pageable path's pinned slots and the copy
-    // path's device slots); streams, events and mask words stay. The next
-    // call on this pipeline reserves again.
-    void trim() {  // (the lease has drained the streams)
-        for (auto& h : hslot) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-        hslot_cap = 0;
-        for (auto& d : slot) {
-            if (d) (void)hipFree(d);
-            d = nullptr;
-        }
-        slot_cap = 0;
-    }
-    ~Pipeline() {
-        for (auto& h : hslot) (void)hipHostFree(h);
-        for (auto& e : hdone)
-            if (e) (void)hipEventDestroy(e);
-        for (int i = 0; i < kDepth; ++i) {
-            (void)hipFree(slot[i]);
-            (void)hipFree(mask_dev[i]);
-            (void)hipHostFree(mask_host[i]);
-            if (streams[i]) (void)hipStreamDestroy(streams[i]);
-        }
-    }
-    int reserve(size_t slot_bytes, size_t n_masks) {
-        if (!streams[0])
-            for (int i = 0; i < kDepth; ++i) HEC_HIP(hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking));
-        if (slot_bytes > slot_cap) {
-            for (int i = 0; i < kDepth; ++i) {
-                if (slot[i]) HEC_HIP(hipFree(slot[i]));
-                slot[i] = nullptr;
-            }
-            slot_cap = 0;
-            for (int i = 0; i < kDepth; ++i) HEC_HIP(hipMalloc(reinterpret_cast<void**>(&slot[i]), slot_bytes));
-            slot_cap = slot_bytes;
-        }
-        if (n_masks > mask_cap) {
-            for (int i = 0; i < kDepth; ++i) {
-                if (mask_dev[i]) HEC_HIP(hipFree(mask_dev[i]));
-                if (mask_host[i]) HEC_HIP(hipHostFree(mask_host[i]));
-                mask_dev[i] = mask_host[i] = nullptr;
-            }
-            mask_cap = 0;
-            for (int i = 0; i < kDepth; ++i) {
-                HEC_HIP(hipMalloc(reinterpret_cast<void**>(&mask_dev[i]), n_masks * 4));
-                HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&mask_host[i]), n_masks * 4));
-            }
-            mask_cap = n_masks;
-        }
-        return HEC_OK;
-    }
-};
-
-// Per-device pool of pipelines (SlotPool, hec_internal.hpp): concurrent host
-// batches on one device -- other threads, or two ranges of one multi-device
-// call on the same GPU -- each lease their own streams and slots. Up to
-// kScratchSlots (8) pipelines exist per device, but only the first
-// kWarmSlots (2) keep their staging between calls: a pipeline created by a
-// burst of concurrent calls frees its large buffers when its call ends
-// (PipelineLease), so the steady footprint per device is that of two
-// pipelines (INTEGRATION.md §5 states the worst case).
-std::mutex& pipeline_reg_mu() {
-    static std::mutex* m = new std::mutex();
-    return *m;
-}
-std::map<int, std::unique_ptr<SlotPool<Pipeline>>>& pipeline_reg() {
-    static auto* reg = new std::map<int, std::unique_ptr<SlotPool<Pipeline>>>();  // process lifetime
-    return *reg;
-}
-
-struct PipelineLease {
-    Lease<Pipeline> lease;
-    bool trim_after = false;
-    Pipeline* operator->() const { return lease.sc; }
-    ~PipelineLease() {  // still holding the pipeline's mutex
-        if (!lease.sc) return;
-        // Host batches code caller memory in place (zero copy) or copy into
-        // it: an error return between enqueues must not leave that work in
-        // flight for the caller's freed buffers (StreamDrain's rule). After
-        // a successful call every stream is idle already.
-        for (auto st : lease.sc->streams)
+    // Host batches code caller memory in place (zero copy) or copy into it: an
+    // error return between enqueues must not leave that work in flight for the
+    // caller's freed buffers (StreamDrain's rule), so every call ends by
+    // draining the streams; after a successful call they are idle already. A
+    // burst slot then frees its large staging (the pageable path's pinned
+    // slots and the copy path's device slots); streams, events and mask words
+    // stay, and the next call on this pipeline reserves again.
+    void end_call(bool burst) {
+        for (auto st : streams)
             if (st && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-        if (trim_after) lease.sc->trim();
+        if (!burst) return;
+        for (auto& h : hslot) h.release();
+        for (auto& d : slot) d.release();
+    }
+    ~Pipeline() {  // only a slot whose init() failed is ever destroyed
+        for (auto st : streams)
+            if (st) (void)hipStreamDestroy(st);
     }
 };
-
-int lease_pipeline(PipelineLease& out) {
-    int dev;
-    int rc = current_device(&dev);
-    if (rc) return rc;
-    SlotPool<Pipeline>* pool;
-    {
-        std::lock_guard<std::mutex> lk(pipeline_reg_mu());
-        auto& p = pipeline_reg()[dev];
-        if (!p) p.reset(new SlotPool<Pipeline>());
-        pool = p.get();
-    }
-    if ((rc = pool->lease(out.lease))) return rc;
-    out.trim_after = out.lease.index >= kWarmSlots;
-    return HEC_OK;
-}
 
 // Copy `rows` rows of `width` bytes with pitches (2D; 1D when both are dense).
 hipError_t copy2d(void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t width, uint64_t rows,
@@ -209,6 +132,77 @@ int forced_failure_chunk() {
 uint32_t chunk_stripes(uint64_t shard_len, int n, uint32_t n_stripes) {
     uint64_t c = std::max<uint64_t>(1, kChunkBytes / (uint64_t(n) * shard_len));
     return uint32_t(std::min<uint64_t>(c, n_stripes));
+}
+
+// A chunk's present masks, normalised (& full) into dst; returns how many of
+// its stripes have fewer than k shards present.
+uint32_t load_masks(uint32_t* dst, const uint32_t* src, uint32_t c, uint32_t full, int k) {
+    uint32_t bad = 0;
+    for (uint32_t s = 0; s < c; ++s) {
+        dst[s] = src[s] & full;
+        bad += __builtin_popcount(dst[s]) < k ? 1u : 0u;
+    }
+    return bad;
+}
+
+// fn(first, count) for each run of adjacent set bits of `bits` below n, over
+// the first `cap` set bits only (the run the cap falls in is cut there).
+template <typename F>
+int for_bit_runs(uint32_t bits, int n, int cap, F fn) {
+    int used = 0;
+    for (int i = 0; i < n && used < cap;) {
+        if (!((bits >> i) & 1)) {
+            ++i;
+            continue;
+        }
+        int j = i;
+        while (j < n && ((bits >> j) & 1) && used + (j - i) < cap) ++j;
+        HEC_TRY(fn(i, j - i));
+        used += j - i;
+        i = j;
+    }
+    return HEC_OK;
+}
+
+// Pageable batches with zero copy on: chunks of C stripes go through the two
+// pinned slots, coded in place there on streams[0]. pack(s0, c, q) fills slot q
+// on the host, launch(c, q) queues its kernel, unpack(s0, c, q) hands the
+// results back; packing chunk i+1 and unpacking chunk i-1 overlap the kernel
+// of chunk i.
+template <typename Pack, typename Launch, typename Unpack>
+int two_slot_loop(Pipeline* p, uint32_t n_stripes, uint32_t C, Pack pack, Launch launch, Unpack unpack) {
+    uint32_t prev_s0 = 0, prev_c = 0;
+    int q = 0;
+    for (uint32_t s0 = 0; s0 < n_stripes; s0 += C, q ^= 1) {
+        const uint32_t c = std::min(C, n_stripes - s0);
+        pack(s0, c, q);
+        HEC_TRY(launch(c, q));
+        HEC_HIP(hipEventRecord(p->hdone[q], p->streams[0]));
+        if (s0 > 0) {  // the previous chunk (other slot) is done or nearly: hand it back
+            HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
+            unpack(prev_s0, prev_c, q ^ 1);
+        }
+        prev_s0 = s0, prev_c = c;
+    }
+    HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
+    unpack(prev_s0, prev_c, q ^ 1);
+    return HEC_OK;
+}
+
+// The copy pipeline: chunk `it` of C stripes runs on stream and device slot
+// q = it % kDepth. in(s0, c, q) queues its H2D copies, launch(c, q, it) its
+// kernel, out(s0, c, q) its D2H copies; all streams are drained at the end.
+template <typename In, typename Launch, typename Out>
+int copy_loop(Pipeline* p, uint32_t n_stripes, uint32_t C, In in, Launch launch, Out out) {
+    for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
+        const uint32_t c = std::min(C, n_stripes - s0);
+        const int q = int(it % kDepth);
+        HEC_TRY(in(s0, c, q));
+        HEC_TRY(launch(c, q, it));
+        HEC_TRY(out(s0, c, q));
+    }
+    for (auto st : p->streams) HEC_HIP(hipStreamSynchronize(st));
+    return HEC_OK;
 }
 
 // One host batch over a device set (contiguous stripe ranges
@@ -287,274 +281,215 @@ extern "C" {
 int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t data_stripe_stride,
                           uint64_t data_shard_stride, uint8_t* h_parity, uint64_t parity_stripe_stride,
                           uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes) {
-    if (!rs || !h_data || !h_parity) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
     if (n_stripes == 0) return HEC_OK;
-    int rc;
-    if ((rc = check_strided("data", uint32_t(rs->k), data_stripe_stride, data_shard_stride, shard_len, n_stripes)) ||
-        (rc = check_strided("parity", uint32_t(rs->m), parity_stripe_stride, parity_shard_stride, shard_len,
-                            n_stripes)))
-        return rc;
+    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
+                                 parity_shard_stride, shard_len, n_stripes));
     GeomDevice* gd;
-    if ((rc = geom_device(rs, &gd))) return rc;
-    PipelineLease lease;
-    if ((rc = lease_pipeline(lease))) return rc;
-    Pipeline* p = lease.lease.sc;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<Pipeline> p;
+    HEC_TRY(lease_slot(p));
     const int k = rs->k, m = rs->m;
     uint8_t *zd, *zp;
     if (host_device_view(h_data, batch_span(data_stripe_stride, data_shard_stride, k, shard_len, n_stripes), &zd) &&
         host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
                          &zp)) {
-        if ((rc = p->reserve(0, 1))) return rc;
-        if ((rc = run_apply(gd->encode, uint32_t(k), zd, data_stripe_stride, data_shard_stride, zp,
-                            parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, nullptr, nullptr,
-                            p->streams[0], nullptr, /*over_pcie=*/true)))
-            return rc;
+        HEC_TRY(p->reserve(0, 1));
+        HEC_TRY(run_apply(gd->encode, uint32_t(k), zd, data_stripe_stride, data_shard_stride, zp,
+                          parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, nullptr, nullptr,
+                          p->streams[0], nullptr, /*over_pcie=*/true));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
         return HEC_OK;
     }
-    const uint64_t Lp = (shard_len + 255) / 256 * 256;  // device shard pitch
+    const uint64_t Lp = round_up(shard_len, 256);  // device shard pitch
+    // len rounded to 16: the pad bytes of the pitch are computed but never copied back
+    const uint64_t L16 = round_up(shard_len, 16);
     const uint32_t C = chunk_stripes(Lp, rs->n, n_stripes);
     const uint64_t dstripe = uint64_t(rs->n) * Lp;
     if (zero_copy_enabled()) {
         // Pageable memory: chunks are copied into two pinned slots on the host
-        // pool and coded in place by the zero-copy kernel; packing chunk i+1
-        // and unpacking chunk i-1 overlap the kernel of chunk i.
-        if ((rc = p->reserve(0, 1)) || (rc = p->reserve_host(size_t(C) * dstripe))) return rc;
+        // pool and coded in place by the zero-copy kernel.
+        HEC_TRY(p->reserve(0, 1));
+        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
         uint8_t* zs[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
-        if (zs[0] && zs[1]) {
-            hipStream_t st = p->streams[0];
-            auto unpack = [&](uint32_t s0, uint32_t c, int q) {
-                parallel_for(size_t(c) * m, uint64_t(c) * m * shard_len, [&](size_t t) {
-                    const uint32_t s = uint32_t(t / m);
-                    const int j = int(t % m);
-                    std::memcpy(h_parity + (s0 + s) * parity_stripe_stride + j * parity_shard_stride,
-                                p->hslot[q] + s * dstripe + uint64_t(k + j) * Lp, shard_len);
+        if (zs[0] && zs[1])
+            return two_slot_loop(
+                p.sc, n_stripes, C,
+                [&](uint32_t s0, uint32_t c, int q) {
+                    uint8_t* h = p->hslot[q];
+                    parallel_for(size_t(c) * k, uint64_t(c) * k * shard_len, [&](size_t t) {
+                        const uint32_t s = uint32_t(t / k);
+                        const int i = int(t % k);
+                        std::memcpy(h + s * dstripe + uint64_t(i) * Lp,
+                                    h_data + (s0 + s) * data_stripe_stride + i * data_shard_stride, shard_len);
+                    });
+                },
+                [&](uint32_t c, int q) {
+                    return run_apply(gd->encode, uint32_t(k), zs[q], dstripe, Lp, zs[q] + uint64_t(k) * Lp, dstripe,
+                                     Lp, L16, c, nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true);
+                },
+                [&](uint32_t s0, uint32_t c, int q) {
+                    parallel_for(size_t(c) * m, uint64_t(c) * m * shard_len, [&](size_t t) {
+                        const uint32_t s = uint32_t(t / m);
+                        const int j = int(t % m);
+                        std::memcpy(h_parity + (s0 + s) * parity_stripe_stride + j * parity_shard_stride,
+                                    p->hslot[q] + s * dstripe + uint64_t(k + j) * Lp, shard_len);
+                    });
                 });
-            };
-            uint32_t prev_s0 = 0, prev_c = 0;
-            for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
-                const uint32_t c = std::min(C, n_stripes - s0);
-                const int q = int(it % 2);
-                uint8_t* h = p->hslot[q];
-                parallel_for(size_t(c) * k, uint64_t(c) * k * shard_len, [&](size_t t) {
-                    const uint32_t s = uint32_t(t / k);
-                    const int i = int(t % k);
-                    std::memcpy(h + s * dstripe + uint64_t(i) * Lp,
-                                h_data + (s0 + s) * data_stripe_stride + i * data_shard_stride, shard_len);
-                });
-                if ((rc = run_apply(gd->encode, uint32_t(k), zs[q], dstripe, Lp, zs[q] + uint64_t(k) * Lp, dstripe,
-                                    Lp, (shard_len + 15) / 16 * 16, c, nullptr, nullptr, st, nullptr,
-                                    /*over_pcie=*/true)))
-                    return rc;
-                HEC_HIP(hipEventRecord(p->hdone[q], st));
-                if (it > 0) {  // chunk it-1 (other slot) is done or nearly: hand its parity back
-                    HEC_HIP(hipEventSynchronize(p->hdone[1 - q]));
-                    unpack(prev_s0, prev_c, 1 - q);
-                }
-                prev_s0 = s0, prev_c = c;
-            }
-            const int last = int(((n_stripes + C - 1) / C - 1) % 2);
-            HEC_HIP(hipEventSynchronize(p->hdone[last]));
-            unpack(prev_s0, prev_c, last);
-            return HEC_OK;
-        }
     }
-    if ((rc = p->reserve(size_t(C) * rs->n * Lp, 1))) return rc;
+    HEC_TRY(p->reserve(size_t(C) * rs->n * Lp, 1));
     const int fail_at = forced_failure_chunk();
-    for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
-        const uint32_t c = std::min(C, n_stripes - s0);
-        const int q = int(it % kDepth);
-        hipStream_t st = p->streams[q];
-        uint8_t* d = p->slot[q];
-        for (uint32_t s = 0; s < c; ++s)  // data shards of stripe s -> [s][0..k)
-            HEC_HIP(copy2d(d + s * dstripe, Lp, h_data + (s0 + s) * data_stripe_stride, data_shard_stride,
-                           shard_len, uint64_t(k), hipMemcpyHostToDevice, st));
-        // len rounded to 16: the pad bytes of the device pitch are computed but never copied back
-        if ((rc = run_apply(gd->encode, uint32_t(k), d, dstripe, Lp, d + uint64_t(k) * Lp, dstripe, Lp,
-                            (shard_len + 15) / 16 * 16, c, nullptr, nullptr, st)))
-            return rc;
-        if (int(it) == fail_at) return fail(HEC_ERR_HIP, "test hook: failure after chunk " + std::to_string(it));
-        for (uint32_t s = 0; s < c; ++s)
-            HEC_HIP(copy2d(h_parity + (s0 + s) * parity_stripe_stride, parity_shard_stride,
-                           d + s * dstripe + uint64_t(k) * Lp, Lp, shard_len, uint64_t(m), hipMemcpyDeviceToHost, st));
-    }
-    for (int q = 0; q < kDepth; ++q) HEC_HIP(hipStreamSynchronize(p->streams[q]));
-    return HEC_OK;
+    return copy_loop(
+        p.sc, n_stripes, C,
+        [&](uint32_t s0, uint32_t c, int q) -> int {
+            for (uint32_t s = 0; s < c; ++s)  // data shards of stripe s -> [s][0..k)
+                HEC_HIP(copy2d(p->slot[q] + s * dstripe, Lp, h_data + (s0 + s) * data_stripe_stride,
+                               data_shard_stride, shard_len, uint64_t(k), hipMemcpyHostToDevice, p->streams[q]));
+            return HEC_OK;
+        },
+        [&](uint32_t c, int q, uint32_t it) -> int {
+            uint8_t* d = p->slot[q];
+            HEC_TRY(run_apply(gd->encode, uint32_t(k), d, dstripe, Lp, d + uint64_t(k) * Lp, dstripe, Lp, L16, c,
+                              nullptr, nullptr, p->streams[q]));
+            if (int(it) == fail_at) return fail(HEC_ERR_HIP, "test hook: failure after chunk " + std::to_string(it));
+            return HEC_OK;
+        },
+        [&](uint32_t s0, uint32_t c, int q) -> int {
+            for (uint32_t s = 0; s < c; ++s)
+                HEC_HIP(copy2d(h_parity + (s0 + s) * parity_stripe_stride, parity_shard_stride,
+                               p->slot[q] + s * dstripe + uint64_t(k) * Lp, Lp, shard_len, uint64_t(m),
+                               hipMemcpyDeviceToHost, p->streams[q]));
+            return HEC_OK;
+        });
 }
 
 int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
                                uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
                                uint32_t* n_bad_stripes) {
-    if (!rs || !h_shards || !h_present_masks) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    HEC_TRY(check_batch_args(rs, h_shards, h_present_masks, shard_len));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    int rc;
-    if ((rc = check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes))) return rc;
+    HEC_TRY(check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes));
     GeomDevice* gd;
-    if ((rc = geom_device(rs, &gd))) return rc;
-    PipelineLease lease;
-    if ((rc = lease_pipeline(lease))) return rc;
-    Pipeline* p = lease.lease.sc;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<Pipeline> p;
+    HEC_TRY(lease_slot(p));
     const int k = rs->k, n = rs->n;
     const uint32_t full = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1);
+    uint32_t bad = 0;
     uint8_t* zs;
     if (host_device_view(h_shards, batch_span(stripe_stride, shard_stride, n, shard_len, n_stripes), &zs)) {
         // masks to the device (the caller's array may be pageable), then one
         // decode over the pinned host shards in place
-        if ((rc = p->reserve(0, n_stripes))) return rc;
-        if ((rc = ensure_dense_decode(rs, gd, p->streams[0]))) return rc;
-        uint32_t bad = 0;
-        for (uint32_t s = 0; s < n_stripes; ++s) {
-            const uint32_t mask = h_present_masks[s] & full;
-            p->mask_host[0][s] = mask;
-            bad += __builtin_popcount(mask) < k ? 1u : 0u;
-        }
+        HEC_TRY(p->reserve(0, n_stripes));
+        HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
+        bad = load_masks(p->mask_host[0], h_present_masks, n_stripes, full, k);
         HEC_HIP(hipMemcpyAsync(p->mask_dev[0], p->mask_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
                                p->streams[0]));
-        if ((rc = run_apply(gd->decode_dense, uint32_t(k), zs, stripe_stride, shard_stride, zs, stripe_stride,
-                            shard_stride, shard_len, n_stripes, p->mask_dev[0], nullptr, p->streams[0])))
-            return rc;
+        HEC_TRY(run_apply(gd->decode_dense, uint32_t(k), zs, stripe_stride, shard_stride, zs, stripe_stride,
+                          shard_stride, shard_len, n_stripes, p->mask_dev[0], nullptr, p->streams[0]));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
         if (n_bad_stripes) *n_bad_stripes = bad;
         return HEC_OK;
     }
-    const uint64_t Lp = (shard_len + 255) / 256 * 256;
+    const uint64_t Lp = round_up(shard_len, 256), L16 = round_up(shard_len, 16);
     const uint32_t C = chunk_stripes(Lp, n, n_stripes);
     const uint64_t dstripe = uint64_t(n) * Lp;
+    auto host_shard = [&](uint32_t s, int i) { return h_shards + s * stripe_stride + uint64_t(i) * shard_stride; };
+    auto finish = [&](int rc) {
+        if (!rc && n_bad_stripes) *n_bad_stripes = bad;
+        return rc;
+    };
     if (zero_copy_enabled()) {
         // Pageable memory: the first k present shards of each stripe are copied
         // into two pinned slots on the host pool, decoded in place there by the
-        // zero-copy kernel, and only the erased shards are copied back; chunk
-        // i+1's copies in and chunk i-1's copies out overlap chunk i's kernel.
-        if ((rc = p->reserve(0, C)) || (rc = p->reserve_host(size_t(C) * dstripe))) return rc;
-        if ((rc = ensure_dense_decode(rs, gd, p->streams[0]))) return rc;
+        // zero-copy kernel, and only the erased shards are copied back.
+        HEC_TRY(p->reserve(0, C));
+        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
+        HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
         uint8_t* hz[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
         uint32_t* zm[2] = {reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[0])),
                            reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[1]))};
-        if (hz[0] && hz[1] && zm[0] && zm[1]) {
-            hipStream_t st = p->streams[0];
-            uint32_t bad = 0;
-            auto unpack = [&](uint32_t s0, uint32_t c, int q) {
-                parallel_for(size_t(c) * n, uint64_t(c) * 4 * shard_len, [&](size_t t) {
-                    const uint32_t s = uint32_t(t / n);
-                    const int i = int(t % n);
-                    const uint32_t mask = p->mask_host[q][s];
-                    if (__builtin_popcount(mask) < k || ((mask >> i) & 1)) return;
-                    std::memcpy(h_shards + (s0 + s) * stripe_stride + uint64_t(i) * shard_stride,
-                                p->hslot[q] + s * dstripe + uint64_t(i) * Lp, shard_len);
-                });
-            };
-            uint32_t prev_s0 = 0, prev_c = 0;
-            for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
-                const uint32_t c = std::min(C, n_stripes - s0);
-                const int q = int(it % 2);
-                for (uint32_t s = 0; s < c; ++s) {
-                    const uint32_t mask = h_present_masks[s0 + s] & full;
-                    p->mask_host[q][s] = mask;
-                    bad += __builtin_popcount(mask) < k ? 1u : 0u;
-                }
-                uint8_t* h = p->hslot[q];
-                parallel_for(size_t(c) * n, uint64_t(c) * k * shard_len, [&](size_t t) {
-                    const uint32_t s = uint32_t(t / n);
-                    const int i = int(t % n);
-                    const uint32_t mask = p->mask_host[q][s];
-                    if (__builtin_popcount(mask) < k || __builtin_popcount(mask) == n || !((mask >> i) & 1)) return;
-                    if (__builtin_popcount(mask & ((1u << i) - 1)) >= k) return;  // only the first k present
-                    std::memcpy(h + s * dstripe + uint64_t(i) * Lp,
-                                h_shards + (s0 + s) * stripe_stride + uint64_t(i) * shard_stride, shard_len);
-                });
-                if ((rc = run_apply(gd->decode_dense, uint32_t(k), hz[q], dstripe, Lp, hz[q], dstripe, Lp,
-                                    (shard_len + 15) / 16 * 16, c, zm[q], nullptr, st)))
-                    return rc;
-                HEC_HIP(hipEventRecord(p->hdone[q], st));
-                if (it > 0) {
-                    HEC_HIP(hipEventSynchronize(p->hdone[1 - q]));
-                    unpack(prev_s0, prev_c, 1 - q);
-                }
-                prev_s0 = s0, prev_c = c;
+        if (hz[0] && hz[1] && zm[0] && zm[1])
+            return finish(two_slot_loop(
+                p.sc, n_stripes, C,
+                [&](uint32_t s0, uint32_t c, int q) {
+                    bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k);
+                    parallel_for(size_t(c) * n, uint64_t(c) * k * shard_len, [&](size_t t) {
+                        const uint32_t s = uint32_t(t / n);
+                        const int i = int(t % n);
+                        const uint32_t mask = p->mask_host[q][s];
+                        if (__builtin_popcount(mask) < k || __builtin_popcount(mask) == n || !((mask >> i) & 1))
+                            return;
+                        if (__builtin_popcount(mask & ((1u << i) - 1)) >= k) return;  // only the first k present
+                        std::memcpy(p->hslot[q] + s * dstripe + uint64_t(i) * Lp, host_shard(s0 + s, i), shard_len);
+                    });
+                },
+                [&](uint32_t c, int q) {
+                    return run_apply(gd->decode_dense, uint32_t(k), hz[q], dstripe, Lp, hz[q], dstripe, Lp, L16, c,
+                                     zm[q], nullptr, p->streams[0]);
+                },
+                [&](uint32_t s0, uint32_t c, int q) {
+                    parallel_for(size_t(c) * n, uint64_t(c) * 4 * shard_len, [&](size_t t) {
+                        const uint32_t s = uint32_t(t / n);
+                        const int i = int(t % n);
+                        const uint32_t mask = p->mask_host[q][s];
+                        if (__builtin_popcount(mask) < k || ((mask >> i) & 1)) return;
+                        std::memcpy(host_shard(s0 + s, i), p->hslot[q] + s * dstripe + uint64_t(i) * Lp, shard_len);
+                    });
+                }));
+    }
+    HEC_TRY(p->reserve(size_t(C) * n * Lp, C));
+    HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
+    auto dev_shard = [&](int q, uint32_t s, int i) { return p->slot[q] + s * dstripe + uint64_t(i) * Lp; };
+    return finish(copy_loop(
+        p.sc, n_stripes, C,
+        [&](uint32_t s0, uint32_t c, int q) -> int {
+            // the staging of this slot was last read by the copy issued kDepth chunks ago
+            HEC_HIP(hipStreamSynchronize(p->streams[q]));
+            bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k);
+            for (uint32_t s = 0; s < c; ++s) {
+                const uint32_t mask = p->mask_host[q][s];
+                const int present = __builtin_popcount(mask);
+                if (present < k || present == n) continue;
+                // H2D only the first k present shards (the ones the decode reads),
+                // merged into runs of adjacent shard ids
+                HEC_TRY(for_bit_runs(mask, n, k, [&](int i, int count) -> int {
+                    HEC_HIP(copy2d(dev_shard(q, s, i), Lp, host_shard(s0 + s, i), shard_stride, shard_len,
+                                   uint64_t(count), hipMemcpyHostToDevice, p->streams[q]));
+                    return HEC_OK;
+                }));
             }
-            const int last = int(((n_stripes + C - 1) / C - 1) % 2);
-            HEC_HIP(hipEventSynchronize(p->hdone[last]));
-            unpack(prev_s0, prev_c, last);
-            if (n_bad_stripes) *n_bad_stripes = bad;
+            HEC_HIP(hipMemcpyAsync(p->mask_dev[q], p->mask_host[q], c * 4, hipMemcpyHostToDevice, p->streams[q]));
             return HEC_OK;
-        }
-    }
-    if ((rc = p->reserve(size_t(C) * n * Lp, C))) return rc;
-    if ((rc = ensure_dense_decode(rs, gd, p->streams[0]))) return rc;
-    uint32_t bad = 0;
-    for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
-        const uint32_t c = std::min(C, n_stripes - s0);
-        const int q = int(it % kDepth);
-        hipStream_t st = p->streams[q];
-        uint8_t* d = p->slot[q];
-        // the staging of this slot was last read by the copy issued kDepth chunks ago
-        HEC_HIP(hipStreamSynchronize(st));
-        for (uint32_t s = 0; s < c; ++s) {
-            const uint32_t mask = h_present_masks[s0 + s] & full;
-            p->mask_host[q][s] = mask;
-            const int present = __builtin_popcount(mask);
-            if (present < k) {
-                ++bad;
-                continue;
+        },
+        [&](uint32_t c, int q, uint32_t) {
+            uint8_t* d = p->slot[q];
+            return run_apply(gd->decode_dense, uint32_t(k), d, dstripe, Lp, d, dstripe, Lp, L16, c, p->mask_dev[q],
+                             nullptr, p->streams[q]);
+        },
+        [&](uint32_t s0, uint32_t c, int q) -> int {
+            for (uint32_t s = 0; s < c; ++s) {
+                const uint32_t mask = p->mask_host[q][s];
+                if (__builtin_popcount(mask) < k) continue;
+                // D2H the erased shards, merged into runs
+                HEC_TRY(for_bit_runs(~mask & full, n, n, [&](int i, int count) -> int {
+                    HEC_HIP(copy2d(host_shard(s0 + s, i), shard_stride, dev_shard(q, s, i), Lp, shard_len,
+                                   uint64_t(count), hipMemcpyDeviceToHost, p->streams[q]));
+                    return HEC_OK;
+                }));
             }
-            if (present == n) continue;
-            // H2D only the first k present shards (the ones the decode reads),
-            // merged into runs of adjacent shard ids.
-            int used = 0;
-            for (int i = 0; i < n && used < k;) {
-                if (!((mask >> i) & 1)) {
-                    ++i;
-                    continue;
-                }
-                int j = i;
-                while (j < n && ((mask >> j) & 1) && used + (j - i) < k) ++j;
-                HEC_HIP(copy2d(d + s * dstripe + uint64_t(i) * Lp, Lp,
-                               h_shards + (s0 + s) * stripe_stride + uint64_t(i) * shard_stride, shard_stride,
-                               shard_len, uint64_t(j - i), hipMemcpyHostToDevice, st));
-                used += j - i;
-                i = j;
-            }
-        }
-        HEC_HIP(hipMemcpyAsync(p->mask_dev[q], p->mask_host[q], c * 4, hipMemcpyHostToDevice, st));
-        if ((rc = run_apply(gd->decode_dense, uint32_t(k), d, dstripe, Lp, d, dstripe, Lp,
-                            (shard_len + 15) / 16 * 16, c, p->mask_dev[q], nullptr, st)))
-            return rc;
-        for (uint32_t s = 0; s < c; ++s) {
-            const uint32_t mask = p->mask_host[q][s];
-            if (__builtin_popcount(mask) < k) continue;
-            for (int i = 0; i < n;) {  // D2H the erased shards, merged into runs
-                if ((mask >> i) & 1) {
-                    ++i;
-                    continue;
-                }
-                int j = i;
-                while (j < n && !((mask >> j) & 1)) ++j;
-                HEC_HIP(copy2d(h_shards + (s0 + s) * stripe_stride + uint64_t(i) * shard_stride, shard_stride,
-                               d + s * dstripe + uint64_t(i) * Lp, Lp, shard_len, uint64_t(j - i),
-                               hipMemcpyDeviceToHost, st));
-                i = j;
-            }
-        }
-    }
-    for (int q = 0; q < kDepth; ++q) HEC_HIP(hipStreamSynchronize(p->streams[q]));
-    if (n_bad_stripes) *n_bad_stripes = bad;
-    return HEC_OK;
+            return HEC_OK;
+        }));
 }
 
 int hec_host_encode_batch_multi(const hec_rs_t* rs, const int* devices, size_t n_devices, const uint8_t* h_data,
                                 uint64_t data_stripe_stride, uint64_t data_shard_stride, uint8_t* h_parity,
                                 uint64_t parity_stripe_stride, uint64_t parity_shard_stride, uint64_t shard_len,
                                 uint32_t n_stripes) {
-    if (!rs || !h_data || !h_parity) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
-    int rc;
-    if ((rc = check_strided("data", uint32_t(rs->k), data_stripe_stride, data_shard_stride, shard_len, n_stripes)) ||
-        (rc = check_strided("parity", uint32_t(rs->m), parity_stripe_stride, parity_shard_stride, shard_len,
-                            n_stripes)))
-        return rc;
+    HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
+    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
+                                 parity_shard_stride, shard_len, n_stripes));
     return run_device_ranges(devices, n_devices, n_stripes, [&](uint32_t s0, uint32_t c, size_t) {
         return hec_host_encode_batch(rs, h_data + s0 * data_stripe_stride, data_stripe_stride, data_shard_stride,
                                      h_parity + s0 * parity_stripe_stride, parity_stripe_stride, parity_shard_stride,
@@ -565,13 +500,11 @@ int hec_host_encode_batch_multi(const hec_rs_t* rs, const int* devices, size_t n
 int hec_host_reconstruct_batch_multi(const hec_rs_t* rs, const int* devices, size_t n_devices, uint8_t* h_shards,
                                      uint64_t stripe_stride, uint64_t shard_stride, uint64_t shard_len,
                                      uint32_t n_stripes, const uint32_t* h_present_masks, uint32_t* n_bad_stripes) {
-    if (!rs || !h_shards || !h_present_masks) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    HEC_TRY(check_batch_args(rs, h_shards, h_present_masks, shard_len));
     if (n_bad_stripes) *n_bad_stripes = 0;
-    int rc;
-    if ((rc = check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes))) return rc;
+    HEC_TRY(check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes));
     std::vector<uint32_t> bad(std::max<size_t>(n_devices, 1), 0);
-    rc = run_device_ranges(devices, n_devices, n_stripes, [&](uint32_t s0, uint32_t c, size_t r) {
+    int rc = run_device_ranges(devices, n_devices, n_stripes, [&](uint32_t s0, uint32_t c, size_t r) {
         return hec_host_reconstruct_batch(rs, h_shards + s0 * stripe_stride, stripe_stride, shard_stride, shard_len, c,
                                           h_present_masks + s0, &bad[r]);
     });
@@ -597,12 +530,7 @@ int hec_host_staging_stats(int* n_pipelines, uint64_t* pinned_bytes, uint64_t* d
     int dev;
     int rc = current_device(&dev);
     if (rc) return rc;
-    SlotPool<Pipeline>* pool = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(pipeline_reg_mu());
-        auto it = pipeline_reg().find(dev);
-        if (it != pipeline_reg().end()) pool = it->second.get();
-    }
+    SlotPool<Pipeline>* pool = per_device<SlotPool<Pipeline>>(dev, /*create=*/false);
     int n = 0;
     uint64_t pinned = 0, devb = 0;
     if (pool) {

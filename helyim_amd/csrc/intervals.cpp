@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <thread>
 
@@ -22,102 +21,46 @@ namespace {
 // for the previous call's kernel (a back-to-back encode / reconstruct stream
 // keeps the GPU fed while the host builds the next map).
 struct MetaSlot {
-    uint8_t* h = nullptr;
-    uint8_t* d = nullptr;
-    size_t cap = 0;
+    PinnedBuf<> h;
+    DeviceBuf<> d;
     hipEvent_t free = nullptr;  // recorded after the kernel that read this slot
     int reserve(size_t bytes) {
         if (free) HEC_HIP(hipEventSynchronize(free));
         else HEC_HIP(hipEventCreateWithFlags(&free, hipEventDisableTiming));
-        if (bytes <= cap) return HEC_OK;
-        if (h) HEC_HIP(hipHostFree(h));
-        if (d) HEC_HIP(hipFree(d));
-        h = d = nullptr;
-        cap = 0;
-        const size_t want = std::max(bytes, size_t(1) << 20);
-        HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&h), want));
-        HEC_HIP(hipMalloc(reinterpret_cast<void**>(&d), want));
-        cap = want;
-        return HEC_OK;
+        HEC_TRY(h.reserve(bytes, kMetaFloor));
+        return d.reserve(bytes, kMetaFloor);
     }
 };
 constexpr int kMetaSlots = 4;
 
+// One slot of the per-device pool of ragged scratch (SlotPool, hec_internal.hpp).
 struct RaggedScratch {
     std::mutex mu;
     hipStream_t stream = nullptr;
     MetaSlot slots[kMetaSlots];  // device-API ragged calls
     unsigned next_slot = 0;
     Completion done;             // small host calls (compact_reconstruct_104)
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t cap = 0;
-    uint8_t* hmeta = nullptr;
-    uint8_t* dmeta = nullptr;
-    size_t mcap = 0;
+    PinnedBuf<> host, hmeta;     // compact payload and its metadata,
+    DeviceBuf<> dev, dmeta;      // and their device copies
     int init() {
         HEC_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         return HEC_OK;
     }
     int reserve(size_t bytes, size_t meta) {
-        if (bytes > cap && bytes > 0) {
-            if (host) HEC_HIP(hipHostFree(host));
-            if (dev) HEC_HIP(hipFree(dev));
-            host = dev = nullptr;
-            cap = 0;
-            const size_t want = std::max(bytes, size_t(16) << 20);
-            HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&host), want));
-            HEC_HIP(hipMalloc(reinterpret_cast<void**>(&dev), want));
-            cap = want;
-        }
-        if (meta > mcap) {
-            if (hmeta) HEC_HIP(hipHostFree(hmeta));
-            if (dmeta) HEC_HIP(hipFree(dmeta));
-            hmeta = dmeta = nullptr;
-            mcap = 0;
-            const size_t want = std::max(meta, size_t(1) << 20);
-            HEC_TRY(pinned_alloc(reinterpret_cast<void**>(&hmeta), want));
-            HEC_HIP(hipMalloc(reinterpret_cast<void**>(&dmeta), want));
-            mcap = want;
-        }
-        return HEC_OK;
+        HEC_TRY(host.reserve(bytes, kStagingFloor));
+        HEC_TRY(dev.reserve(bytes, kStagingFloor));
+        HEC_TRY(hmeta.reserve(meta, kMetaFloor));
+        return dmeta.reserve(meta, kMetaFloor);
     }
-    // Compact staging above 64 MiB in a burst slot (index >= kWarmSlots) is
-    // freed when its call ends (ScratchTrim's rule, hec_internal.hpp).
-    void trim_large() {
-        constexpr size_t kKeep = size_t(64) << 20;
-        if (cap <= kKeep) return;
+    // A burst slot frees its compact payload above kStagingKeep when its call
+    // ends (Scratch's rule); the metadata stays.
+    void end_call(bool burst) {
+        if (!burst || host.cap <= kStagingKeep) return;
         (void)hipStreamSynchronize(stream);  // an error return may leave copies in flight
-        (void)hipHostFree(host);
-        (void)hipFree(dev);
-        host = dev = nullptr;
-        cap = 0;
+        host.release();
+        dev.release();
     }
 };
-struct RaggedTrim {
-    RaggedScratch* sc;
-    bool on;
-    ~RaggedTrim() {
-        if (on) sc->trim_large();
-    }
-};
-
-// Per-device pool of ragged scratch slots (see SlotPool, hec_internal.hpp).
-int lease_ragged(Lease<RaggedScratch>& out) {
-    static std::mutex mu;
-    static auto* reg = new std::map<int, std::unique_ptr<SlotPool<RaggedScratch>>>();  // process lifetime
-    int dev;
-    int rc = current_device(&dev);
-    if (rc) return rc;
-    SlotPool<RaggedScratch>* pool;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto& p = (*reg)[dev];
-        if (!p) p.reset(new SlotPool<RaggedScratch>());
-        pool = p.get();
-    }
-    return pool->lease(out);
-}
 
 }  // namespace
 
@@ -132,23 +75,22 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     for (size_t j = 0; j < jobs.size(); ++j) {
         if (__builtin_popcount(jobs[j].mask) < k || jobs[j].len == 0 || jobs[j].len > 0xFFFFFFFFull)
             return fail(HEC_ERR_INVALID_ARGUMENT, "compact job without k survivors");
-        lay[j].Lp = (jobs[j].len + 15) / 16 * 16;
+        lay[j].Lp = round_up(jobs[j].len, 16);
         lay[j].off = total;
-        total += (uint64_t(k) * lay[j].Lp + 255) / 256 * 256;  // compact inputs: the first k present shards
+        total += round_up(uint64_t(k) * lay[j].Lp, 256);  // compact inputs: the first k present shards
     }
     if (jobs.empty()) return HEC_OK;
     const uint64_t in_total = total;
     for (size_t j = 0; j < jobs.size(); ++j) {  // compact outputs: the erased shards, ascending
         lay[j].out_off = total;
-        total += (uint64_t(n - __builtin_popcount(jobs[j].mask)) * lay[j].Lp + 255) / 256 * 256;
+        total += round_up(uint64_t(n - __builtin_popcount(jobs[j].mask)) * lay[j].Lp, 256);
     }
     GeomDevice* gd;
     int rc = geom_device(rs, &gd);
     if (rc) return rc;
     Lease<RaggedScratch> lease;
-    if ((rc = lease_ragged(lease))) return rc;
+    if ((rc = lease_slot(lease))) return rc;
     RaggedScratch* sc = lease.sc;
-    const RaggedTrim trim{sc, lease.index >= kWarmSlots};  // before the lease lets go
     std::vector<RaggedItem> items(jobs.size());
     std::vector<uint32_t> block_item;
     for (size_t j = 0; j < jobs.size(); ++j) {
@@ -158,17 +100,15 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
         block_item.insert(block_item.end(), chunks, uint32_t(j));
     }
     const size_t items_bytes = items.size() * sizeof(RaggedItem);
-    const size_t meta = (items_bytes + 255) / 256 * 256 + block_item.size() * 4;
+    const size_t map_off = round_up(items_bytes, 256);
+    const size_t meta = map_off + block_item.size() * 4;
     if ((rc = sc->reserve(total, meta))) return rc;
     if ((rc = ensure_dense_decode(rs, gd, sc->stream))) return rc;
     // survivors the decode reads (the first k present shards) -> slots 0..k-1
     // The fills may run on host-pool workers, whose failure detail and values
     // are thread-local to them: the first failure's (code, detail, values) is
     // captured on its thread and re-raised on the caller's.
-    std::mutex err_mu;
-    int first_err = HEC_OK;
-    std::string err_detail;
-    ErrorValues err_values;
+    ErrorSlot err;
     // one task per (job, slot): a single large interval's 10 survivor reads run
     // in parallel too
     auto fill_one = [&](size_t t) {
@@ -179,14 +119,7 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
             if ((jobs[j].mask >> i) & 1) {
                 if (used == want) {
                     const int r = fill(j, used, i, sc->host + lay[j].off + used * lay[j].Lp);
-                    if (r) {
-                        std::lock_guard<std::mutex> g(err_mu);
-                        if (first_err == HEC_OK) {
-                            first_err = r;
-                            err_detail = hec_last_error_detail();
-                            err_values = last_error_values();
-                        }
-                    }
+                    if (r) err.capture(r);
                     return;
                 }
                 ++used;
@@ -196,7 +129,7 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
         parallel_io_for(jobs.size() * size_t(k), in_total, fill_one);
     else
         parallel_for(jobs.size() * size_t(k), in_total, fill_one);
-    if (first_err) return fail_with(first_err, err_detail, err_values);
+    if ((rc = err.raise())) return rc;
     // zero-copy: the kernel reads the packed survivors and writes the rebuilt
     // shards in the pinned staging itself (no H2D / D2H of the payload)
     uint8_t* zh = zero_copy_enabled() ? pinned_device_ptr(sc->host) : nullptr;
@@ -212,10 +145,9 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
         ra.one = items[0];
     } else {
         std::memcpy(sc->hmeta, items.data(), items_bytes);
-        const size_t map_off = (items_bytes + 255) / 256 * 256;
         std::memcpy(sc->hmeta + map_off, block_item.data(), block_item.size() * 4);
         HEC_HIP(hipMemcpyAsync(sc->dmeta, sc->hmeta, meta, hipMemcpyHostToDevice, sc->stream));
-        ra.items = reinterpret_cast<const RaggedItem*>(sc->dmeta);
+        ra.items = reinterpret_cast<const RaggedItem*>(sc->dmeta.p);
         ra.block_item = reinterpret_cast<const uint32_t*>(sc->dmeta + map_off);
     }
     // small zero-copy calls: completion from the kernel's own signal
@@ -371,16 +303,16 @@ int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs
     int rc = geom_device(rs, &gd);
     if (rc) return rc;
     Lease<RaggedScratch> lease;
-    if ((rc = lease_ragged(lease))) return rc;
+    if ((rc = lease_slot(lease))) return rc;
     RaggedScratch* sc = lease.sc;
     const size_t items_bytes = size_t(n) * sizeof(RaggedItem);
-    const size_t map_off = (items_bytes + 255) / 256 * 256;
+    const size_t map_off = round_up(items_bytes, 256);
     const size_t meta = map_off + n_blocks * 4;
     MetaSlot& slot = sc->slots[sc->next_slot++ % kMetaSlots];
     if ((rc = slot.reserve(meta))) return rc;  // waits for this slot's previous kernel only
     if (decode && (rc = ensure_dense_decode(rs, gd, sc->stream))) return rc;
     // items and workgroup map written straight into the pinned slot
-    RaggedItem* items = reinterpret_cast<RaggedItem*>(slot.h);
+    RaggedItem* items = reinterpret_cast<RaggedItem*>(slot.h.p);
     uint32_t* block_item = reinterpret_cast<uint32_t*>(slot.h + map_off);
     uint32_t first = 0;
     for (uint32_t j = 0; j < n; ++j) {
@@ -393,7 +325,7 @@ int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs
     HEC_HIP(hipMemcpyAsync(slot.d, slot.h, meta, hipMemcpyHostToDevice, stream));
     RaggedArgs ra{};
     ra.base = d_base;
-    ra.items = reinterpret_cast<const RaggedItem*>(slot.d);
+    ra.items = reinterpret_cast<const RaggedItem*>(slot.d.p);
     ra.block_item = reinterpret_cast<const uint32_t*>(slot.d + map_off);
     ra.n_blocks = uint32_t(n_blocks);
     ra.tabs = decode ? gd->decode_dense.tabs : gd->encode.tabs;

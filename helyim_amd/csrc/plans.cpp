@@ -1,0 +1,215 @@
+// Coding plans and the per-device state of one geometry: the host-side plan
+// list and its device copy, the decode plan of an erasure pattern, the encode
+// plan and dense decode LUT shared by all contexts of a geometry, and the
+// launch of one plan set over a strided batch.
+#include <tuple>
+
+#include "hec_internal.hpp"
+
+namespace hec {
+
+// ---------------------------------------------------------------------------
+// Plans
+// ---------------------------------------------------------------------------
+uint32_t HostPlans::add(const Mat& coefs, const std::vector<uint32_t>& in_ids,
+                        const std::vector<uint32_t>& out_ids) {
+    DevPlan p{};
+    p.nin = uint32_t(in_ids.size());
+    p.nout = uint32_t(out_ids.size());
+    p.tab_off = uint32_t(tabs.size());
+    p.idx_off = uint32_t(idx.size());
+    p.tab_rows = fixed_rows ? fixed_rows : p.nout;
+    for (uint32_t i = 0; i < p.nin; ++i)
+        for (uint32_t r = 0; r < p.tab_rows; ++r) {
+            uint32_t t[kTabWords];
+            perm_tables(r < p.nout ? coefs.at(int(r), int(i)) : uint8_t(0), t);
+            tabs.insert(tabs.end(), t, t + kTabWords);
+        }
+    idx.insert(idx.end(), in_ids.begin(), in_ids.end());
+    idx.insert(idx.end(), out_ids.begin(), out_ids.end());
+    plans.push_back(p);
+    return uint32_t(plans.size() - 1);
+}
+
+uint32_t HostPlans::add_noop(uint32_t nin) {
+    DevPlan p{nin, 0, uint32_t(tabs.size()), uint32_t(idx.size()), fixed_rows, {0, 0, 0}};
+    tabs.insert(tabs.end(), size_t(nin) * fixed_rows * kTabWords, 0u);
+    plans.push_back(p);
+    return uint32_t(plans.size() - 1);
+}
+
+template <typename T>
+static int grow_upload(DeviceBuf<T>& d, const std::vector<T>& src, hipStream_t s) {
+    if (src.empty()) return HEC_OK;
+    HEC_TRY(d.reserve(src.size() * sizeof(T)));
+    HEC_HIP(hipMemcpyAsync(d, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    return HEC_OK;
+}
+
+int DevicePlanSet::upload(const HostPlans& hp, const std::vector<uint32_t>* lut_host, hipStream_t s) {
+    HEC_TRY(grow_upload(plans, hp.plans, s));
+    HEC_TRY(grow_upload(tabs, hp.tabs, s));
+    HEC_TRY(grow_upload(idx, hp.idx, s));
+    if (lut_host) HEC_TRY(grow_upload(lut, *lut_host, s));
+    // Host vectors may be freed by the caller right after: make the copies land.
+    HEC_HIP(hipStreamSynchronize(s));
+    return HEC_OK;
+}
+
+void DevicePlanSet::release() {
+    plans.release();
+    tabs.release();
+    idx.release();
+    lut.release();
+}
+
+// upstream reconstruct_internal: first k present shards -> sub-matrix ->
+// inverse; missing data rows = inverse rows; missing parity rows = parity
+// row x inverse (composed, bit-identical to upstream's second pass since the
+// reconstructed data bytes are unique).
+int decode_plan(const hec_rs* rs, const uint8_t* present, bool data_only, Mat& coefs,
+                std::vector<uint32_t>& in_ids, std::vector<uint32_t>& out_ids, bool* noop) {
+    const int k = rs->k, n = rs->n;
+    int npresent = 0;
+    for (int i = 0; i < n; ++i) npresent += present[i] ? 1 : 0;
+    *noop = false;
+    in_ids.clear();
+    out_ids.clear();
+    if (npresent == n) {
+        *noop = true;
+        return HEC_OK;
+    }
+    if (npresent < k) return fail(HEC_ERR_TOO_FEW_SHARDS_PRESENT, "");
+    std::vector<uint32_t> miss;
+    for (int i = 0; i < n; ++i) {
+        if (present[i]) {
+            if (int(in_ids.size()) < k) in_ids.push_back(uint32_t(i));
+        } else {
+            miss.push_back(uint32_t(i));
+        }
+    }
+    Mat sub(k, k);
+    for (int r = 0; r < k; ++r)
+        for (int c = 0; c < k; ++c) sub.at(r, c) = rs->matrix.at(int(in_ids[r]), c);
+    Mat inv;
+    if (!mat_invert(sub, inv)) return fail(HEC_ERR_INVALID_ARGUMENT, "singular decode matrix");
+    for (uint32_t i : miss)
+        if (!(data_only && int(i) >= k)) out_ids.push_back(i);
+    coefs = Mat(int(out_ids.size()), k);
+    const Gf& g = gf();
+    for (size_t r = 0; r < out_ids.size(); ++r) {
+        const int id = int(out_ids[r]);
+        if (id < k) {
+            for (int c = 0; c < k; ++c) coefs.at(int(r), c) = inv.at(id, c);
+        } else {
+            for (int c = 0; c < k; ++c) {
+                uint8_t acc = 0;
+                for (int t = 0; t < k; ++t) acc ^= g.mul[rs->matrix.at(id, t)][inv.at(t, c)];
+                coefs.at(int(r), c) = acc;
+            }
+        }
+    }
+    if (out_ids.empty()) *noop = true;
+    return HEC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Per-device geometry state
+// ---------------------------------------------------------------------------
+static std::mutex g_geom_mu;
+static std::map<std::tuple<int, int, int>, std::unique_ptr<GeomDevice>> g_geom;
+
+int geom_device(const hec_rs* rs, GeomDevice** out) {
+    int dev;
+    int rc = current_device(&dev);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_geom_mu);
+    auto key = std::make_tuple(dev, rs->k, rs->m);
+    auto it = g_geom.find(key);
+    if (it != g_geom.end()) {
+        *out = it->second.get();
+        return HEC_OK;
+    }
+    std::unique_ptr<GeomDevice> gd(new GeomDevice());
+    const bool is104 = rs->k == 10 && rs->m == 4;
+    HostPlans hp;
+    if (is104) hp.fixed_rows = 4;
+    Mat par(rs->m, rs->k);
+    for (int r = 0; r < rs->m; ++r)
+        for (int c = 0; c < rs->k; ++c) par.at(r, c) = rs->matrix.at(rs->k + r, c);
+    std::vector<uint32_t> in_ids, out_ids;
+    for (int i = 0; i < rs->k; ++i) in_ids.push_back(uint32_t(i));
+    for (int j = 0; j < rs->m; ++j) out_ids.push_back(uint32_t(j));
+    hp.add(par, in_ids, out_ids);
+    if ((rc = gd->encode.upload(hp, nullptr, nullptr))) return rc;
+    gd->encode.fast104 = is104;
+    *out = gd.get();
+    g_geom[key] = std::move(gd);
+    return HEC_OK;
+}
+
+int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_geom_mu);
+    if (gd->decode_ready) return HEC_OK;
+    const int n = rs->n, k = rs->k;
+    if (n > 16) return fail(HEC_ERR_INVALID_ARGUMENT, "device-mask reconstruct needs total shards <= 16");
+    HostPlans hp;
+    const bool is104 = k == 10 && rs->m == 4;
+    if (is104) hp.fixed_rows = 4;
+    std::vector<uint32_t> lut(size_t(1) << n, kNoPlan);
+    const uint32_t noop = hp.add_noop(uint32_t(k));
+    uint8_t present[16];
+    Mat coefs;
+    std::vector<uint32_t> in_ids, out_ids;
+    for (uint32_t mask = 0; mask < (1u << n); ++mask) {
+        const int pc = __builtin_popcount(mask);
+        if (pc < k) continue;
+        if (pc == n) {
+            lut[mask] = noop;
+            continue;
+        }
+        for (int i = 0; i < n; ++i) present[i] = (mask >> i) & 1;
+        bool is_noop = false;
+        int rc = decode_plan(rs, present, false, coefs, in_ids, out_ids, &is_noop);
+        if (rc) return rc;
+        lut[mask] = hp.add(coefs, in_ids, out_ids);
+    }
+    int rc = gd->decode_dense.upload(hp, &lut, s);
+    if (rc) return rc;
+    gd->decode_dense.fast104 = is104;
+    gd->decode_dense.lut_bits = uint32_t(n);
+    gd->decode_ready = true;
+    return HEC_OK;
+}
+
+int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uint64_t in_stripe,
+              uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
+              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
+              hipStream_t s, Completion* done, bool over_pcie) {
+    ApplyArgs a{};
+    if (done) HEC_TRY(done->arm(s, &a.done_count, &a.done_flag, &a.done_seq));
+    a.in_base = in_base;
+    a.in_stripe = in_stripe;
+    a.in_shard = in_shard;
+    a.out_base = out_base;
+    a.out_stripe = out_stripe;
+    a.out_shard = out_shard;
+    a.len = len;
+    a.n_stripes = n_stripes;
+    a.plans = ps.plans;
+    a.tabs = ps.tabs;
+    a.idx = ps.idx;
+    a.masks = masks;
+    a.lut = ps.lut;
+    a.bad_count = bad;
+    a.fast104 = ps.fast104 ? 1u : 0u;
+    a.mask_limit = ps.lut_bits ? ((1u << ps.lut_bits) - 1u) : 0u;
+    if (masks && !ps.lut) return fail(HEC_ERR_INVALID_ARGUMENT, "per-stripe masks need a decode LUT");
+    const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(in_base)) | in_stripe | in_shard |
+                           uint64_t(reinterpret_cast<uintptr_t>(out_base)) | out_stripe | out_shard;
+    const bool aligned = (align % 16) == 0;
+    HEC_HIP(launch_apply(a, int(nin), aligned, over_pcie && !masks, s));
+    return HEC_OK;
+}
+
+}  // namespace hec

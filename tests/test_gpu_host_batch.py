@@ -71,6 +71,40 @@ def test_host_reconstruct_every_pattern(gpu, pin):
             assert np.array_equal(a[s], good.numpy()[s]), p
 
 
+def test_host_reconstruct_across_chunks(gpu):
+    """A pageable reconstruct that reuses its staging: 14 x 65792 B per stripe
+    puts 109 stripes in a 96 MiB chunk, so 340 stripes are chunks of 109, 109,
+    109 and 13 -- both pinned slots (zero_copy) and all three copy streams
+    (copy_pipeline) are reused and the last chunk is short. Stripe s loses
+    s % 6 shards; the stripes at the chunk edges (108 | 109, 217 | 218) lose
+    4, 0, 5 and 4. Rebuildable stripes come back exact, unrecoverable ones are
+    counted and left byte for byte as they were."""
+    import helyim_amd as H
+    import helyim_amd.batch as B
+    rs = H.ReedSolomon(10, 4)
+    S, L = 340, 65536 + 5
+    t = _host_stripes(S, L, pin=False)
+    B.host_encode_batch(rs, t)
+    good = t.clone().numpy()
+    assert np.array_equal(good[:, 10:], corc.encode_stripes(np.ascontiguousarray(good[:, :10])))
+    erasures = [s % 6 for s in range(S)]
+    erasures[108], erasures[109], erasures[217], erasures[218] = 4, 0, 5, 4
+    rng = np.random.default_rng(340)
+    a = t.numpy()
+    masks = np.full(S, (1 << 14) - 1, dtype=np.uint32)
+    for s, e in enumerate(erasures):
+        for i in rng.choice(14, e, replace=False):
+            a[s, int(i)] = 0x5A
+            masks[s] &= ~np.uint32(1 << int(i))
+    before = a.copy()
+    bad = B.host_reconstruct_batch(rs, t, masks)
+    assert bad == sum(1 for e in erasures if e == 5)
+    for s, e in enumerate(erasures):
+        assert np.array_equal(a[s], good[s] if e <= 4 else before[s]), (s, e)
+    lost = [s for s, e in enumerate(erasures) if e == 5]
+    assert all(int((before[s] == 0x5A).all(axis=1).sum()) == 5 for s in lost)
+
+
 def test_mixed_workload_lengths(gpu):
     """BASELINE config 5 shape: shard lengths 64 KiB..4 MiB, 0..4 erasures."""
     import torch

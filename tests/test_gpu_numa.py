@@ -203,7 +203,7 @@ def test_multi_device_batch_pages_follow_their_ranges(monkeypatch):
 
 def test_host_worker_pool_threads_sit_on_the_gpus_node():
     """Each device's host worker pool binds its workers to that GPU's NUMA
-    node (hec_api.cpp HostPool), whichever thread first needed it: after a
+    node (host_pool.cpp HostPool), whichever thread first needed it: after a
     pageable host batch (staging copies on the pool), at least the 15 workers
     of device 0's pool run on exactly the CPUs hec_bind_thread_to_device(0)
     gives a thread here."""

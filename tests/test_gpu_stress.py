@@ -27,7 +27,7 @@ def test_burst_slots_trim_large_staging_and_stay_exact(gpu):
     """12 threads of large per-call encodes / reconstructs (6 MiB shards: 84 MiB
     of per-call device staging) and large batched degraded reads (112 MiB of
     compact staging): slots beyond the first two of each pool free staging
-    above 64 MiB when their call ends (ScratchTrim / RaggedTrim), and the next
+    above 64 MiB when their call ends (the slots' end_call), and the next
     call on the slot reserves again. Every result is checked against the C
     oracle."""
     import threading
