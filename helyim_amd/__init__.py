@@ -26,7 +26,20 @@ from .ec import (  # noqa: F401
     read_ec_data, read_ec_needle, read_ec_needles, generate_ec_files, rebuild_ec_files,
     rebuild_ecx_file, save_volume_info, to_ext, ec_shard_filename, ec_shard_base_filename, volume_ec_shards_generate, volume_ec_shards_rebuild,
     write_data_file, write_ec_files, write_index_file_from_ec_index, write_sorted_file_from_index,
+    verify_ec_files,
 )
+
+
+_BATCH_VERIFY = ("verify_batch", "verify_batch_sep", "host_verify_batch", "verify_kernel_name")
+
+
+def __getattr__(name):
+    # the batch verify calls live in helyim_amd.batch, which needs torch:
+    # re-exported on first use so that importing helyim_amd does not
+    if name in _BATCH_VERIFY:
+        from . import batch
+        return getattr(batch, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def version() -> str:

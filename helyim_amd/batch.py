@@ -83,6 +83,61 @@ def reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: tor
                                         _stream_ptr(stream)))
 
 
+def _verify_args(S: int, mismatch: torch.Tensor, bad_stripes: torch.Tensor):
+    """Result tensors of a device verify -> (mismatch, bad_stripes pointer)."""
+    if mismatch is None:
+        mismatch = torch.empty(S, dtype=torch.int32, device="cuda")
+    elif not (mismatch.is_cuda and mismatch.dtype in (torch.int32, torch.uint32) and mismatch.is_contiguous()
+              and mismatch.numel() >= S):
+        raise ValueError("mismatch must be a contiguous 32-bit CUDA tensor with at least one word per stripe")
+    _check_device(mismatch)
+    if bad_stripes is not None:
+        if not (bad_stripes.is_cuda and bad_stripes.dtype in (torch.int32, torch.uint32)
+                and bad_stripes.numel() >= 1):
+            raise ValueError("bad_stripes must be a 32-bit CUDA tensor")
+        _check_device(bad_stripes)
+    return mismatch, (bad_stripes.data_ptr() if bad_stripes is not None else None)
+
+
+def verify_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                 bad_stripes: torch.Tensor = None, stream=None) -> torch.Tensor:
+    """Scrub ``stripes[S, total, L]`` on the device (hec_gpu_verify_batch): word s
+    of the returned int32 ``[S]`` tensor (``mismatch``, allocated when not
+    given) has bit j set when parity shard j of stripe s differs from the
+    parity of its data shards; 0 = clean. bad_stripes (32-bit CUDA word,
+    accumulated): plus one per stripe with a non-zero word. Nothing else is
+    written. Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    k = rs.data_shard_count()
+    S, n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    check(lib.hec_gpu_verify_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), bad,
+                                   _stream_ptr(stream)))
+    return mismatch
+
+
+def verify_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, mismatch: torch.Tensor = None,
+                     bad_stripes: torch.Tensor = None, stream=None) -> torch.Tensor:
+    """verify_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
+    _check_stripes(data, rs, rs.data_shard_count())
+    _check_stripes(parity, rs, rs.parity_shard_count())
+    S, k, L = data.shape
+    if parity.shape[0] != S or parity.shape[2] != L:
+        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    check(lib.hec_gpu_verify_batch(rs.handle, data.data_ptr(), data.stride(0), data.stride(1),
+                                   parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
+                                   mismatch.data_ptr(), bad, _stream_ptr(stream)))
+    return mismatch
+
+
+def verify_kernel_name(L: int) -> str:
+    """The kernel an aligned RS(10,4) verify_batch of this shard length runs (hec_verify_kernel_name)."""
+    return lib.hec_verify_kernel_name(L).decode()
+
+
 def _check_host(t: torch.Tensor, rs: ReedSolomon):
     if t.dtype != torch.uint8 or t.is_cuda or t.dim() != 3 or t.stride(2) != 1:
         raise TypeError("expected a host uint8 tensor [stripes, shards, L] with contiguous shards")
@@ -137,6 +192,21 @@ def host_reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks
         check(lib.hec_host_reconstruct_batch_multi(rs.handle, arr, nd, stripes.data_ptr(), stripes.stride(0),
                                                    stripes.stride(1), L, S, m.ctypes.data, ctypes.byref(bad)))
     return int(bad.value)
+
+
+def host_verify_batch(rs: ReedSolomon, stripes: torch.Tensor):
+    """Scrub host-memory stripes[S, total, L] on the GPU (hec_host_verify_batch):
+    returns the uint32 ``[S]`` numpy array of mismatch words (verify_batch's
+    contract). Only the words come back over PCIe; the stripes are not written."""
+    import numpy as np
+    _check_host(stripes, rs)
+    k = rs.data_shard_count()
+    S, n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    words = np.zeros(max(S, 1), dtype=np.uint32)
+    check(lib.hec_host_verify_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, words.ctypes.data, None))
+    return words[:S]
 
 
 DESC_DTYPE = None

@@ -22,7 +22,7 @@ using namespace hec;
 
 extern "C" {
 
-const char* hec_version(void) { return "libhec 0.1.0 (gfx950)"; }
+const char* hec_version(void) { return "libhec 0.2.0 (gfx950)"; }
 
 int hec_device_count(int* count) {
     if (!count) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
@@ -53,6 +53,7 @@ int hec_get_device(int* device) {
 
 const char* hec_encode_kernel_name(uint64_t shard_len) { return encode_kernel_name(shard_len, false); }
 const char* hec_decode_kernel_name(uint64_t shard_len) { return decode_kernel_name(shard_len); }
+const char* hec_verify_kernel_name(uint64_t shard_len) { return verify_kernel_name(shard_len); }
 const char* hec_host_encode_kernel_name(uint64_t shard_len) {
     return encode_kernel_name(shard_len, true);
 }
@@ -91,6 +92,22 @@ int hec_gpu_reconstruct_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t st
     HEC_TRY(ensure_dense_decode(rs, gd, s));
     return run_apply(gd->decode_dense, uint32_t(rs->k), d_shards, stripe_stride, shard_stride, d_shards,
                      stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks, d_bad_stripes, s);
+}
+
+int hec_gpu_verify_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
+                         uint64_t data_shard_stride, const uint8_t* d_parity, uint64_t parity_stripe_stride,
+                         uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch,
+                         uint32_t* d_bad_stripes, void* stream) {
+    HEC_TRY(check_batch_args(rs, d_data, d_parity, shard_len));
+    HEC_TRY(check_verify_args(rs, d_mismatch));
+    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
+                                 parity_shard_stride, shard_len, n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    return run_verify(gd->encode, uint32_t(rs->k), d_data, data_stripe_stride, data_shard_stride, d_parity,
+                      parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, d_mismatch, d_bad_stripes,
+                      static_cast<hipStream_t>(stream));
 }
 
 int hec_gpu_fill_splitmix(uint8_t* d_base, uint64_t stripe_stride, uint64_t bytes_per_stripe, uint32_t n_stripes,

@@ -419,4 +419,21 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
               uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
               hipStream_t s, Completion* done = nullptr, bool over_pcie = false);
 
+// Verify the stored parity of a strided batch against ps's encode plan (plan
+// 0), asynchronously on s: mismatch[0, n_stripes) (device words) are cleared
+// on s, then bit j of mismatch[st] is set when parity shard j of stripe st
+// differs within its len bytes; bad (optional device word) += stripes with a
+// non-zero word. len is the true shard length, never a rounded-up one: pad
+// bytes would be compared. At most 32 parity shards (the caller checks).
+int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint64_t data_stripe,
+               uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len,
+               uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s);
+// The verify entry points' extra argument checks, after check_batch_args.
+inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
+    if (!mismatch) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (rs->m > 32)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "verify needs at most 32 parity shards (one result bit each)");
+    return HEC_OK;
+}
+
 }  // namespace hec

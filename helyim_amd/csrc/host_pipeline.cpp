@@ -483,6 +483,104 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
         }));
 }
 
+int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t data_stripe_stride,
+                          uint64_t data_shard_stride, const uint8_t* h_parity, uint64_t parity_stripe_stride,
+                          uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes, uint32_t* h_mismatch,
+                          uint32_t* n_bad_stripes) {
+    HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
+    HEC_TRY(check_verify_args(rs, h_mismatch));
+    if (n_bad_stripes) *n_bad_stripes = 0;
+    if (n_stripes == 0) return HEC_OK;
+    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
+                                 parity_shard_stride, shard_len, n_stripes));
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<Pipeline> p;
+    HEC_TRY(lease_slot(p));
+    const int k = rs->k, m = rs->m, n = rs->n;
+    auto finish = [&](int rc) {
+        if (!rc && n_bad_stripes)
+            for (uint32_t s = 0; s < n_stripes; ++s) *n_bad_stripes += h_mismatch[s] ? 1u : 0u;
+        return rc;
+    };
+    // The result words always live in device memory (the pipeline's mask
+    // words): the kernels' atomics stay on the device, and only the words
+    // cross PCIe back. Every launch gets the true shard_len, never a length
+    // rounded up to the staging pitch: the pad bytes of a reused slot hold
+    // garbage, and a verify compares what an encode merely overwrites.
+    uint8_t *zd, *zp;
+    if (host_device_view(h_data, batch_span(data_stripe_stride, data_shard_stride, k, shard_len, n_stripes), &zd) &&
+        host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
+                         &zp)) {
+        HEC_TRY(p->reserve(0, n_stripes));
+        HEC_TRY(run_verify(gd->encode, uint32_t(k), zd, data_stripe_stride, data_shard_stride, zp,
+                           parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, p->mask_dev[0], nullptr,
+                           p->streams[0]));
+        HEC_HIP(hipMemcpyAsync(p->mask_host[0], p->mask_dev[0], size_t(n_stripes) * 4, hipMemcpyDeviceToHost,
+                               p->streams[0]));
+        HEC_HIP(hipStreamSynchronize(p->streams[0]));
+        std::memcpy(h_mismatch, p->mask_host[0], size_t(n_stripes) * 4);
+        return finish(HEC_OK);
+    }
+    const uint64_t Lp = round_up(shard_len, 256);  // staging shard pitch
+    const uint32_t C = chunk_stripes(Lp, n, n_stripes);
+    const uint64_t dstripe = uint64_t(n) * Lp;
+    auto host_shard = [&](uint32_t s, int i) {
+        return i < k ? h_data + s * data_stripe_stride + uint64_t(i) * data_shard_stride
+                     : h_parity + s * parity_stripe_stride + uint64_t(i - k) * parity_shard_stride;
+    };
+    if (zero_copy_enabled()) {
+        // Pageable memory: all 14 shards of a chunk are packed into a pinned
+        // slot the kernel reads over PCIe; nothing but the words comes back.
+        HEC_TRY(p->reserve(0, C));
+        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
+        uint8_t* zs[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
+        if (zs[0] && zs[1])
+            return finish(two_slot_loop(
+                p.sc, n_stripes, C,
+                [&](uint32_t s0, uint32_t c, int q) {
+                    uint8_t* h = p->hslot[q];
+                    parallel_for(size_t(c) * n, uint64_t(c) * n * shard_len, [&](size_t t) {
+                        const uint32_t s = uint32_t(t / n);
+                        const int i = int(t % n);
+                        std::memcpy(h + s * dstripe + uint64_t(i) * Lp, host_shard(s0 + s, i), shard_len);
+                    });
+                },
+                [&](uint32_t c, int q) -> int {
+                    HEC_TRY(run_verify(gd->encode, uint32_t(k), zs[q], dstripe, Lp, zs[q] + uint64_t(k) * Lp, dstripe,
+                                       Lp, shard_len, c, p->mask_dev[q], nullptr, p->streams[0]));
+                    HEC_HIP(hipMemcpyAsync(p->mask_host[q], p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
+                                           p->streams[0]));
+                    return HEC_OK;
+                },
+                [&](uint32_t s0, uint32_t c, int q) {
+                    std::memcpy(h_mismatch + s0, p->mask_host[q], size_t(c) * 4);
+                }));
+    }
+    HEC_TRY(p->reserve(size_t(C) * dstripe, C));
+    return finish(copy_loop(
+        p.sc, n_stripes, C,
+        [&](uint32_t s0, uint32_t c, int q) -> int {
+            for (uint32_t s = 0; s < c; ++s) {  // 14-shard H2D: data then parity of stripe s -> [s][0..n)
+                HEC_HIP(copy2d(p->slot[q] + s * dstripe, Lp, host_shard(s0 + s, 0), data_shard_stride, shard_len,
+                               uint64_t(k), hipMemcpyHostToDevice, p->streams[q]));
+                HEC_HIP(copy2d(p->slot[q] + s * dstripe + uint64_t(k) * Lp, Lp, host_shard(s0 + s, k),
+                               parity_shard_stride, shard_len, uint64_t(m), hipMemcpyHostToDevice, p->streams[q]));
+            }
+            return HEC_OK;
+        },
+        [&](uint32_t c, int q, uint32_t) {
+            uint8_t* d = p->slot[q];
+            return run_verify(gd->encode, uint32_t(k), d, dstripe, Lp, d + uint64_t(k) * Lp, dstripe, Lp, shard_len, c,
+                              p->mask_dev[q], nullptr, p->streams[q]);
+        },
+        [&](uint32_t s0, uint32_t c, int q) -> int {  // D2H of the words only
+            HEC_HIP(hipMemcpyAsync(h_mismatch + s0, p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
+                                   p->streams[q]));
+            return HEC_OK;
+        }));
+}
+
 int hec_host_encode_batch_multi(const hec_rs_t* rs, const int* devices, size_t n_devices, const uint8_t* h_data,
                                 uint64_t data_stripe_stride, uint64_t data_shard_stride, uint8_t* h_parity,
                                 uint64_t parity_stripe_stride, uint64_t parity_shard_stride, uint64_t shard_len,

@@ -212,4 +212,32 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
     return HEC_OK;
 }
 
+int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint64_t data_stripe,
+               uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len,
+               uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s) {
+    if (n_stripes == 0) return HEC_OK;
+    VerifyArgs v{};
+    ApplyArgs& a = v.a;
+    a.in_base = data;
+    a.in_stripe = data_stripe;
+    a.in_shard = data_shard;
+    a.out_base = const_cast<uint8_t*>(parity);  // only read
+    a.out_stripe = parity_stripe;
+    a.out_shard = parity_shard;
+    a.len = len;
+    a.n_stripes = n_stripes;
+    a.plans = ps.plans;
+    a.tabs = ps.tabs;
+    a.idx = ps.idx;
+    a.bad_count = bad;
+    a.fast104 = ps.fast104 ? 1u : 0u;
+    v.mismatch = mismatch;
+    const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(data)) | data_stripe | data_shard |
+                           uint64_t(reinterpret_cast<uintptr_t>(parity)) | parity_stripe | parity_shard;
+    // the kernels only ever OR bits in: stale words must not leak through
+    HEC_HIP(hipMemsetAsync(mismatch, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_verify(v, int(nin), (align % 16) == 0, s));
+    return HEC_OK;
+}
+
 }  // namespace hec

@@ -759,6 +759,221 @@ hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pci
 }
 
 // ---------------------------------------------------------------------------
+// Parity verify (scrub): the encode with its stores replaced by a compare.
+// A stripe's 14 shards are read once, the parity is recomputed in registers
+// and XORed with the stored parity; what leaves the chip is one word per
+// stripe. Each lane keeps one "differs" flag per parity row (the OR of its
+// XORed dwords), a ballot per row makes the wave's bit set, and lane 0 of the
+// wave ORs it into mismatch[stripe] only when it is non-zero, so clean data
+// costs no write traffic and no LDS. The word is zero at launch (the host
+// clears it on the same stream): the atomicOr that finds it zero is the
+// stripe's first report, whatever chunk, wave or row group it comes from, and
+// counts the stripe into bad_count exactly once.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void report_mismatch(uint32_t* word, uint32_t* bad_count, uint32_t bits) {
+    if (bits != 0 && (threadIdx.x & 63u) == 0) {
+        if (atomicOr(word, bits) == 0 && bad_count) atomicAdd(bad_count, 1u);
+    }
+}
+
+// Bit-sliced RS(10,4) verify: rs104_bs_chunk's loads and XOR program, plus the
+// four stored parity streams; the computed planes are transposed back and
+// compared with the stored bytes. One 8 KiB column range per workgroup, the
+// encode's workgroup -> (stripe, chunk) map. The parity loads are written with
+// the data loads and left to the scheduler, which issues them after the XOR
+// program: 171 VGPRs, no scratch, 2 waves/SIMD as the encode. Pinned up front
+// with a sched_barrier (28 loads in flight, 196 VGPRs) it measured no
+// different within the run-to-run spread (profiles/verify/
+// ab_parity_load_placement.jsonl).
+template <typename OffT>
+__global__ __launch_bounds__(kThreads) void rs104_bs_verify_kernel(VerifyArgs v) {
+    constexpr int K = 10, R = 4;
+    const ApplyArgs& a = v.a;
+    uint32_t stripe, chunk;
+    fast_item(a, a.chunks_per_stripe, stripe, chunk);
+    const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
+    const uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+    const OffT base = OffT(chunk) * OffT(kBsChunk) + OffT(threadIdx.x * 16);
+    uint32_t p[K * 8];
+    u32x4 d[K][2], s[R][2];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        d[i][0] = load_at(in_b + uint64_t(i) * a.in_shard, base);
+        d[i][1] = load_at(in_b + uint64_t(i) * a.in_shard, base + OffT(kThreads * 16));
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        s[j][0] = load_at(par_b + uint64_t(j) * a.out_shard, base);
+        s[j][1] = load_at(par_b + uint64_t(j) * a.out_shard, base + OffT(kThreads * 16));
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            p[8 * i + w] = d[i][0][w];
+            p[8 * i + 4 + w] = d[i][1][w];
+        }
+#pragma unroll
+    for (int i = 0; i < K; ++i) transpose8(p + 8 * i);
+    uint32_t q[R * 8];
+    rs104_encode_planes(p, q);
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        transpose8(q + 8 * j);
+        uint32_t x = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) x |= (q[8 * j + w] ^ s[j][0][w]) | (q[8 * j + 4 + w] ^ s[j][1][w]);
+        bits |= (__ballot(x != 0) != 0 ? 1u : 0u) << j;
+    }
+    report_mismatch(v.mismatch + stripe, a.bad_count, bits);
+}
+
+// One group of R (<= 4) parity rows of the encode plan over one 16-byte
+// vector per lane, as apply_group, with the stores replaced by loads of the
+// stored rows: returns bit r set when row r of the group differs in this
+// lane's vector. The last vector of a shard goes through load_tail for data
+// and parity alike, which zero-fills from a.len on: the recomputed parity of
+// zero bytes is zero, so bytes at or past a.len compare equal whatever the
+// memory there holds.
+template <int K, int R, bool ALIGNED>
+__device__ __forceinline__ uint32_t verify_group(const ApplyArgs& a, const uint8_t* in_b, const uint8_t* par_b,
+                                                 cu32p in_ids, cu32p out_ids, cu32p tab, uint32_t nin,
+                                                 uint32_t tab_row_stride, uint64_t chunk_off) {
+    const uint64_t o = chunk_off + threadIdx.x * kVecBytes;
+    if (o >= a.len) return 0;
+    const uint64_t avail = a.len - o;
+    u32x4 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = u32x4{0, 0, 0, 0};
+    uint32_t differs = 0;
+    if (avail >= kVecBytes) {
+        if constexpr (K > 0) {
+            u32x4 d[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) d[i] = load_full(in_b + uint64_t(in_ids[i]) * a.in_shard + o, ALIGNED);
+#pragma unroll
+            for (int i = 0; i < K; ++i) gf_mac<R>(acc, d[i], tab + i * tab_row_stride);
+        } else {
+            for (uint32_t i = 0; i < nin; ++i) {
+                const u32x4 d = load_full(in_b + uint64_t(in_ids[i]) * a.in_shard + o, ALIGNED);
+                gf_mac<R>(acc, d, tab + i * tab_row_stride);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32x4 x = acc[r] ^ load_full(par_b + uint64_t(out_ids[r]) * a.out_shard + o, ALIGNED);
+            differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
+        }
+    } else {
+        for (uint32_t i = 0; i < nin; ++i) {
+            const u32x4 d = load_tail(in_b + uint64_t(in_ids[i]) * a.in_shard + o, avail);
+            gf_mac<R>(acc, d, tab + i * tab_row_stride);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32x4 x = acc[r] ^ load_tail(par_b + uint64_t(out_ids[r]) * a.out_shard + o, avail);
+            differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
+        }
+    }
+    return differs;
+}
+
+// Generic verify (any codec with at most 32 parity shards, unaligned bases and
+// strides, any length): rs_apply_kernel's grid-stride over (stripe, 4 KiB
+// chunk) items and its row groups, over the encode plan (plan 0).
+template <int K, bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs v) {
+    const ApplyArgs& a = v.a;
+    const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
+    const uint64_t first = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
+    const __attribute__((address_space(4))) DevPlan* pp = as_const(a.plans);
+    const DevPlan p{pp->nin, pp->nout, pp->tab_off, pp->idx_off, pp->tab_rows, {0, 0, 0}};
+    cu32p in_ids = as_const(a.idx) + p.idx_off;
+    cu32p out_ids = in_ids + p.nin;
+    cu32p tab = as_const(a.tabs) + p.tab_off;
+    const uint32_t row_stride = p.tab_rows * 5;  // words per input
+    for (uint64_t item = first; item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        const uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+        const uint64_t chunk_off = uint64_t(chunk) * (kThreads * kVecBytes);
+        uint32_t differs = 0;  // this lane: bit j = parity row j differs in its vector
+        for (uint32_t g = 0; g < p.nout; g += 4) {
+            const uint32_t R = p.nout - g < 4 ? p.nout - g : 4;
+            cu32p tg = tab + g * 5;
+            uint32_t f;
+            switch (R) {
+                case 4: f = verify_group<K, 4, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+                case 3: f = verify_group<K, 3, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+                case 2: f = verify_group<K, 2, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+                default: f = verify_group<K, 1, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+            }
+            differs |= f << g;
+        }
+        uint32_t bits = 0;
+        for (uint32_t j = 0; j < p.nout; ++j) bits |= (__ballot((differs >> j) & 1u) != 0 ? 1u : 0u) << j;
+        report_mismatch(v.mismatch + stripe, a.bad_count, bits);
+    }
+}
+
+constexpr const char* kBsVerifyName = "rs104_bs_verify_kernel (bit-sliced)";
+constexpr const char* kGenericVerifyName = "rs_verify_kernel<10> (table lookup)";
+
+// An aligned RS(10,4) verify runs bit-sliced when the shard length is a
+// multiple of 8 KiB and one stripe's chunks fit a launch.
+static bool verify_bitsliced(uint64_t len) { return len % kBsChunk == 0 && len / kBsChunk <= kMaxLaunchBlocks; }
+
+const char* verify_kernel_name(uint64_t len) {
+    if (len == 0) return kNoLaunch;
+    return verify_bitsliced(len) ? kBsVerifyName : kGenericVerifyName;
+}
+
+template <int K, bool ALIGNED>
+static hipError_t launch_verify_t(VerifyArgs v, hipStream_t stream) {
+    ApplyArgs& a = v.a;
+    const uint64_t chunk = uint64_t(kThreads) * kVecBytes;
+    a.chunks_per_stripe = uint32_t((a.len + chunk - 1) / chunk);
+    a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
+    if (a.n_items == 0) return hipSuccess;
+    const uint64_t grid = std::min<uint64_t>(a.n_items, kMaxLaunchBlocks);  // grid-stride covers the rest
+    hipLaunchKernelGGL((rs_verify_kernel<K, ALIGNED>), dim3(uint32_t(grid)), dim3(kThreads), 0, stream, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t stream) {
+    const ApplyArgs& a = v.a;
+    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
+    if (a.fast104 && aligned && verify_bitsliced(a.len)) {
+        // one chunk per workgroup and no grid-stride loop: batches past one
+        // launch's workgroup limit go in stripe ranges, as launch_apply's
+        const uint64_t per_stripe = a.len / kBsChunk;
+        const uint32_t step = uint32_t(std::min<uint64_t>(kMaxLaunchBlocks / per_stripe, a.n_stripes));
+        const bool off32 = a.len <= 0xFFFFFFFFull;
+        for (uint32_t s0 = 0; s0 < a.n_stripes; s0 += step) {
+            VerifyArgs b = v;
+            b.a.n_stripes = std::min(step, a.n_stripes - s0);
+            b.a.in_base += uint64_t(s0) * a.in_stripe;
+            b.a.out_base += uint64_t(s0) * a.out_stripe;
+            b.mismatch += s0;
+            set_fast_map(b.a, kBsChunk, false);
+            if (off32)
+                hipLaunchKernelGGL((rs104_bs_verify_kernel<uint32_t>), dim3(uint32_t(b.a.n_items)), dim3(kThreads), 0,
+                                   stream, b);
+            else
+                hipLaunchKernelGGL((rs104_bs_verify_kernel<uint64_t>), dim3(uint32_t(b.a.n_items)), dim3(kThreads), 0,
+                                   stream, b);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    if (nin == 10) return aligned ? launch_verify_t<10, true>(v, stream) : launch_verify_t<10, false>(v, stream);
+    return aligned ? launch_verify_t<0, true>(v, stream) : launch_verify_t<0, false>(v, stream);
+}
+
+// ---------------------------------------------------------------------------
 // splitmix64 synthetic stripes (deterministic bench / test inputs)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void fill_splitmix_kernel(uint8_t* base, uint64_t stripe_stride,

@@ -118,6 +118,22 @@ const char* encode_kernel_name(uint64_t len, bool over_pcie);
 // Same for an aligned in-place RS(10,4) device batch reconstruct.
 const char* decode_kernel_name(uint64_t len);
 
+// Parity verify (scrub) of a strided batch: the encode plan's parity is
+// recomputed in registers and compared with the stored parity; nothing but
+// the result words is written. a: the encode's arguments with out_* naming
+// the STORED parity (read only) and bad_count the optional count of stripes
+// with a non-zero word. mismatch[s] bit j = parity shard j of stripe s differs
+// in at least one of its a.len bytes; the words must be zero at launch.
+struct VerifyArgs {
+    ApplyArgs a;
+    uint32_t* mismatch;
+};
+// a.len is the TRUE shard length: bytes at or past it take no part (a length
+// rounded up for a pitch would compare pad bytes).
+hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t stream);
+// Name of the kernel an aligned RS(10,4) device verify of this shard length runs.
+const char* verify_kernel_name(uint64_t len);
+
 // splitmix64 byte stream per stripe (bench/test data generator):
 // stripe s: bytes_per_stripe bytes at base + s*stripe_stride, word n (n>=1) =
 // mix(seed_base + s + n*gamma), little endian.

@@ -1,0 +1,210 @@
+// Scrub of a volume's shard files base.ec00 .. base.ec13 (hec_verify_ec_files).
+//
+// RS parity is bytewise: byte o of every parity file is a function of byte o
+// of the ten data files, whatever large / small block geometry laid the .dat
+// out over them. The scrub therefore treats the 14 files as 14 equal-length
+// byte streams cut into column blocks of block_size bytes, and needs no
+// geometry. Chunks of whole blocks are pread into two pinned slots (shard
+// major: [14][chunk columns]); the verify kernels read a slot in place over
+// PCIe while the preads of the next chunk fill the other slot, and only one
+// word per block comes back. The files are opened read-only.
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cstdio>
+#include <cstring>
+
+#include "hec_internal.hpp"
+
+namespace hec {
+namespace {
+
+constexpr int K = 10, M = 4, N = 14;
+constexpr uint64_t kChunkCols = 4ull << 20;  // target bytes per shard of one chunk (14 x that per slot)
+constexpr uint64_t kReadPiece = 1ull << 20;  // bytes of one pread task
+
+struct Fd {
+    int fd = -1;
+    ~Fd() {
+        if (fd >= 0) ::close(fd);
+    }
+};
+
+// One slot of the per-device pool of scrubs (SlotPool): its stream, the two
+// pinned chunk slots and the result words of each.
+struct Scrub {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    PinnedBuf<> slot[2];
+    DeviceBuf<uint32_t> words_dev[2];
+    PinnedBuf<uint32_t> words_host[2];
+    hipEvent_t done[2] = {};
+    int init() {
+        HEC_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (auto& e : done) HEC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return HEC_OK;
+    }
+    int reserve(size_t slot_bytes, size_t n_words) {
+        HEC_TRY(reserve_all(slot, slot_bytes));
+        HEC_TRY(reserve_all(words_dev, n_words * 4));
+        return reserve_all(words_host, n_words * 4);
+    }
+    void end_call(bool burst) {
+        if (stream && hipStreamSynchronize(stream) != hipSuccess) (void)hipGetLastError();
+        if (!burst) return;
+        for (auto& s : slot) s.release();
+    }
+    ~Scrub() {  // only a slot whose init() failed is ever destroyed
+        if (stream) (void)hipStreamDestroy(stream);
+        for (auto e : done)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+std::string shard_name(const std::string& base, int i) {
+    char ext[8];
+    std::snprintf(ext, sizeof ext, ".ec%02d", i);
+    return base + ext;
+}
+
+// n bytes of fd at off into dst; a file that ends early is a short read
+// (HEC_ERR_IO without an OS error).
+void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, uint64_t n, uint64_t off) {
+    while (n > 0) {
+        const ssize_t r = ::pread(fd, dst, n, off_t(off));
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            ErrorValues v;
+            v.os_errno = errno;
+            err.set(HEC_ERR_IO, "read " + name + ": " + std::strerror(errno), v);
+            return;
+        }
+        if (r == 0) {
+            err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off));
+            return;
+        }
+        dst += r;
+        off += uint64_t(r);
+        n -= uint64_t(r);
+    }
+}
+
+int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
+                         uint64_t* n_blocks) {
+    // files and sizes first: these failures need no device
+    Fd fd[N];
+    std::string names[N];
+    uint64_t size = 0;
+    for (int i = 0; i < N; ++i) {
+        names[i] = shard_name(base, i);
+        fd[i].fd = ::open(names[i].c_str(), O_RDONLY);
+        if (fd[i].fd < 0) {
+            if (errno == ENOENT) return fail(HEC_ERR_SHARD_NOT_FOUND, "no shard file " + names[i]);
+            return fail_errno(HEC_ERR_IO, "open " + names[i], errno);
+        }
+    }
+    for (int i = 0; i < N; ++i) {
+        struct stat st;
+        if (::fstat(fd[i].fd, &st) != 0) return fail_errno(HEC_ERR_IO, "stat " + names[i], errno);
+        if (i == 0) size = uint64_t(st.st_size);
+        if (uint64_t(st.st_size) != size)
+            return fail_values(HEC_ERR_UNEXPECTED_EC_SHARD_SIZE,
+                               "ec shard size expected " + std::to_string(size) + " but actually is " +
+                                   std::to_string(st.st_size) + " (" + names[i] + ")",
+                               size, uint64_t(st.st_size));
+    }
+    if (size == 0) return HEC_OK;
+
+    struct Rs {
+        hec_rs_t* rs = nullptr;
+        ~Rs() { hec_rs_free(rs); }
+    } codec;
+    HEC_TRY(hec_rs_new(K, M, &codec.rs));
+    GeomDevice* gd;
+    HEC_TRY(geom_device(codec.rs, &gd));
+    Lease<Scrub> sc;
+    HEC_TRY(lease_slot(sc));
+    StreamDrain drain{sc->stream};  // the kernels read the slots: idle before the lease ends, error returns too
+
+    const uint64_t per_chunk = std::max<uint64_t>(1, kChunkCols / block);  // blocks per chunk
+    const uint64_t cols = per_chunk * block;                               // columns per chunk
+    const uint64_t pitch = round_up(std::min(cols, round_up(size, block)), 256);
+    HEC_TRY(sc->reserve(size_t(N) * pitch, size_t(per_chunk)));
+    uint8_t* zs[2] = {pinned_device_ptr(sc->slot[0]), pinned_device_ptr(sc->slot[1])};
+    if (!zs[0] || !zs[1]) return fail(HEC_ERR_HIP, "pinned scrub slots are not addressable by the device");
+
+    const uint64_t total_blocks = (size + block - 1) / block;
+    const uint64_t n_chunks = (size + cols - 1) / cols;
+    size_t found = 0;
+    auto chunk_len = [&](uint64_t c) { return std::min(cols, size - c * cols); };
+    // results of chunk c (its words are in words_host[c & 1] once done[c & 1] fired)
+    auto collect = [&](uint64_t c) -> int {
+        const int q = int(c & 1);
+        HEC_HIP(hipEventSynchronize(sc->done[q]));
+        const uint64_t len = chunk_len(c), nb = (len + block - 1) / block;
+        for (uint64_t b = 0; b < nb; ++b) {
+            const uint32_t w = sc->words_host[q][b];
+            if (!w) continue;
+            if (found < cap) {
+                bad[found].offset = c * cols + b * block;
+                bad[found].length = uint32_t(std::min(block, len - b * block));
+                bad[found].parity_mask = w;
+            }
+            ++found;
+        }
+        return HEC_OK;
+    };
+    ErrorSlot err;
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        const int q = int(c & 1);
+        if (c >= 2) HEC_TRY(collect(c - 2));  // the kernel of chunk c - 2 has left this slot
+        const uint64_t off = c * cols, len = chunk_len(c);
+        const uint64_t pieces = (len + kReadPiece - 1) / kReadPiece;
+        uint8_t* h = sc->slot[q];
+        parallel_io_for(size_t(N * pieces), uint64_t(N) * len, [&](size_t t) {
+            const int i = int(t / pieces);
+            const uint64_t p0 = (t % pieces) * kReadPiece;
+            read_exact(err, fd[i].fd, names[i], h + uint64_t(i) * pitch + p0, std::min(kReadPiece, len - p0),
+                       off + p0);
+        });
+        if (err.failed()) return err.raise();
+        // whole blocks in one launch, a shorter last block in its own: every
+        // launch compares exactly the bytes read, never the slot's stale rest
+        const uint64_t full = len / block, tail = len - full * block;
+        uint32_t* wd = sc->words_dev[q];
+        if (full)
+            HEC_TRY(run_verify(gd->encode, K, zs[q], block, pitch, zs[q] + uint64_t(K) * pitch, block, pitch, block,
+                               uint32_t(full), wd, nullptr, sc->stream));
+        if (tail)
+            HEC_TRY(run_verify(gd->encode, K, zs[q] + full * block, block, pitch,
+                               zs[q] + uint64_t(K) * pitch + full * block, block, pitch, tail, 1, wd + full, nullptr,
+                               sc->stream));
+        HEC_HIP(hipMemcpyAsync(sc->words_host[q], wd, size_t(full + (tail ? 1 : 0)) * 4, hipMemcpyDeviceToHost,
+                               sc->stream));
+        HEC_HIP(hipEventRecord(sc->done[q], sc->stream));
+    }
+    if (n_chunks >= 2) HEC_TRY(collect(n_chunks - 2));
+    HEC_TRY(collect(n_chunks - 1));
+    if (n_bad) *n_bad = found;
+    if (n_blocks) *n_blocks = total_blocks;
+    return HEC_OK;
+}
+
+}  // namespace
+}  // namespace hec
+
+extern "C" {
+
+int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
+                        uint64_t* n_blocks) {
+    if (n_bad) *n_bad = 0;
+    if (n_blocks) *n_blocks = 0;
+    if (!base_filename || (cap && !bad)) return hec::fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t block = block_size ? block_size : HEC_SMALL_BLOCK_SIZE;
+    if (block % 4096 != 0 || block > 0xFFFFF000ull)
+        return hec::fail(HEC_ERR_INVALID_ARGUMENT, "block_size must be a multiple of 4096 below 4 GiB");
+    return hec::verify_ec_files_impl(base_filename, block, bad, cap, n_bad, n_blocks);
+}
+
+}  // extern "C"

@@ -58,6 +58,29 @@ def rebuild_ec_files(base_filename: str) -> List[int]:
     return [int(ids[i]) for i in range(n.value)]
 
 
+class _ScrubBad(ctypes.Structure):
+    """include/hec.h ``hec_scrub_bad``."""
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint32), ("parity_mask", ctypes.c_uint32)]
+
+
+def verify_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024):
+    """Scrub base.ec00 .. base.ec13 on the GPU (hec_verify_ec_files): the files
+    are checked as 14 byte streams in column blocks of ``block_size`` bytes
+    (0 = 1 MiB). Returns ``(n_blocks, n_bad, bad)``: blocks checked, blocks
+    whose stored parity differs from their data's (the total), and the first
+    ``min(cap, n_bad)`` of them as ``(offset, length, parity_mask)`` in
+    ascending offset (bit j of the mask = .ec(10+j) differs). Reads only."""
+    if cap < 0:
+        raise ValueError("negative cap")
+    bad = (_ScrubBad * cap)() if cap else None
+    n_bad, n_blocks = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    check_ec(lib.hec_verify_ec_files(base_filename.encode(), block_size, bad, cap, ctypes.byref(n_bad),
+                                     ctypes.byref(n_blocks)))
+    got = min(cap, n_bad.value)
+    return (int(n_blocks.value), int(n_bad.value),
+            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask)) for i in range(got)])
+
+
 # --- EC volume files around the shards (helyim-ec host-side byte formats) ---
 
 def write_sorted_file_from_index(base_filename: str, ext: str = ".ecx") -> None:

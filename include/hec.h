@@ -218,6 +218,30 @@ int hec_gpu_reconstruct_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t st
                               const uint32_t* d_present_masks, uint32_t* d_bad_stripes,
                               void* stream);
 
+/* Verify (scrub) n_stripes stripes: the batched, on-device form of
+ * ReedSolomon::verify. Reads the data shards from d_data and the STORED parity
+ * shards from d_parity (layouts as hec_gpu_encode_batch), recomputes the parity
+ * in registers and compares. Result contract: d_mismatch[s] (device, 32-bit
+ * words) gets bit j set when parity shard j of stripe s differs, in at least
+ * one of its shard_len bytes, from the parity of that stripe's data shards; a
+ * clean stripe gives 0. The call overwrites words [0, n_stripes): it clears
+ * them on `stream` before the launch, so stale contents never leak through.
+ * It writes no other byte anywhere: not a shard, not a gap, not word
+ * n_stripes. *d_bad_stripes (device word, optional, accumulated): plus one per
+ * stripe with a non-zero word, counted exactly once however many chunks or
+ * parity shards of it mismatch. Bytes at or past shard_len (pads of a pitch,
+ * gaps) take no part in the comparison. Any codec with at most 32 parity
+ * shards (more: HEC_ERR_INVALID_ARGUMENT), any strides and lengths; RS(10,4)
+ * with 16-byte-aligned bases and strides and shard_len a multiple of 8 KiB
+ * runs bit-sliced (hec_verify_kernel_name). Argument errors as
+ * hec_gpu_encode_batch plus a null d_mismatch, all before any device work;
+ * n_stripes == 0 returns HEC_OK and writes nothing. */
+int hec_gpu_verify_batch(const hec_rs_t* rs,
+                         const uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                         const uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                         uint64_t shard_len, uint32_t n_stripes,
+                         uint32_t* d_mismatch, uint32_t* d_bad_stripes, void* stream);
+
 /* ---- host-memory batches (the path helyim runs: bytes start and end in host
  * memory, encoder.rs:169-195 / 263-304) -------------------------------------
  * Same strided layout as above but on HOST pointers; synchronous on return.
@@ -239,6 +263,18 @@ int hec_host_encode_batch(const hec_rs_t* rs,
 int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride,
                                uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
                                const uint32_t* h_present_masks, uint32_t* n_bad_stripes);
+/* hec_gpu_verify_batch on host memory, with its result contract: h_mismatch
+ * (host, n_stripes words) is overwritten, *n_bad_stripes (optional) is SET to
+ * the number of stripes with a non-zero word. Only the result words come back
+ * over PCIe: pinned GPU-addressable data and parity are read in place
+ * (zero copy), pageable memory is packed, all shards of a chunk, into the
+ * pinned slots, and with hec_set_host_zero_copy(0) the shards are copied H2D.
+ * The three paths give identical words. Neither buffer is written. */
+int hec_host_verify_batch(const hec_rs_t* rs,
+                          const uint8_t* h_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                          const uint8_t* h_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                          uint64_t shard_len, uint32_t n_stripes,
+                          uint32_t* h_mismatch, uint32_t* n_bad_stripes);
 
 /* One host batch spread over several GPUs of this process (SURVEY.md §8e:
  * contiguous stripe ranges per GPU; helyim's volume server is one process,
@@ -299,6 +335,32 @@ int hec_write_ec_files_ex(const char* base_filename, uint64_t buf_size, uint64_t
  * 244-307): recreates every missing .ecNN. rebuilt_ids (capacity 14) receives
  * the rebuilt shard ids in ascending order, *n_rebuilt their count. */
 int hec_rebuild_ec_files(const char* base_filename, uint32_t* rebuilt_ids, size_t* n_rebuilt);
+
+/* Scrub of base.ec00 .. base.ec13 (no reference counterpart: helyim never
+ * checks its shards). RS parity is bytewise -- byte o of every parity file is
+ * a function of byte o of the ten data files, whatever block geometry wrote
+ * them -- so the 14 files are checked as 14 equal-length streams cut into
+ * column blocks of block_size bytes (0 = 1 MiB; otherwise a non-zero multiple
+ * of 4096 below 4 GiB, else HEC_ERR_INVALID_ARGUMENT; two pinned slots of
+ * about 14 x max(block_size, 4 MiB) bytes are staged). The last block may be
+ * shorter. *n_blocks = blocks checked; *n_bad = blocks whose stored parity
+ * differs from their data's (the total, even past cap); the first
+ * min(cap, *n_bad) of them go to bad[] in ascending offset: offset in the
+ * shard files, length of the block, parity_mask (bit j = .ec(10+j) differs, as
+ * hec_gpu_verify_batch's word). bad may be NULL when cap is 0. Files are
+ * opened read-only and none is written. Errors, the first three before any
+ * device work: any of the 14 files missing -> HEC_ERR_SHARD_NOT_FOUND (detail
+ * names it); sizes not all equal -> HEC_ERR_UNEXPECTED_EC_SHARD_SIZE with
+ * hec_last_error_values = (size of .ec00, size of the first file that
+ * differs); a short read or OS error -> HEC_ERR_IO with its errno. Empty
+ * files: HEC_OK, zero blocks. */
+typedef struct hec_scrub_bad {
+    uint64_t offset;
+    uint32_t length;
+    uint32_t parity_mask;
+} hec_scrub_bad;
+int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap,
+                        size_t* n_bad, uint64_t* n_blocks);
 
 /* ---- EC volume files around the shards (host-side byte formats) ----------- */
 /* write_sorted_file_from_index(base, ext) (encoder.rs:21-37): replay base.idx
@@ -455,6 +517,8 @@ const char* hec_version(void);
 const char* hec_encode_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned in-place RS(10,4) device batch reconstruct. */
 const char* hec_decode_kernel_name(uint64_t shard_len);
+/* Same for a 16-byte-aligned RS(10,4) device batch verify. */
+const char* hec_verify_kernel_name(uint64_t shard_len);
 /* Kernel hec_gpu_encode_ragged (decode = 0) or hec_gpu_reconstruct_ragged
  * (decode != 0) runs on these descriptors: the same choice the launch makes
  * (static string). */

@@ -52,6 +52,16 @@ pub struct hec_stripe_desc {
     pub present_mask: u32,
 }
 
+/// One column block of the shard files whose stored parity differs
+/// (`hec_verify_ec_files`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct hec_scrub_bad {
+    pub offset: u64,
+    pub length: u32,
+    pub parity_mask: u32,
+}
+
 pub const HEC_OK: c_int = 0;
 pub const HEC_ERR_TOO_FEW_SHARDS_PRESENT: c_int = 10;
 pub const HEC_ERR_IO: c_int = 32;
@@ -118,6 +128,14 @@ extern "C" {
                                      shard_stride: u64, shard_len: u64, n_stripes: u32,
                                      d_present_masks: *const u32, d_bad_stripes: *mut u32,
                                      stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_verify_batch(rs: *const hec_rs_t, d_data: *const u8, data_stripe_stride: u64,
+                                data_shard_stride: u64, d_parity: *const u8, parity_stripe_stride: u64,
+                                parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                d_mismatch: *mut u32, d_bad_stripes: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_host_verify_batch(rs: *const hec_rs_t, h_data: *const u8, data_stripe_stride: u64,
+                                 data_shard_stride: u64, h_parity: *const u8, parity_stripe_stride: u64,
+                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                 h_mismatch: *mut u32, n_bad_stripes: *mut u32) -> c_int;
     pub fn hec_host_encode_batch(rs: *const hec_rs_t, h_data: *const u8, data_stripe_stride: u64,
                                  data_shard_stride: u64, h_parity: *mut u8, parity_stripe_stride: u64,
                                  parity_shard_stride: u64, shard_len: u64, n_stripes: u32) -> c_int;
@@ -145,6 +163,8 @@ extern "C" {
                                  small_block_size: u64) -> c_int;
     pub fn hec_rebuild_ec_files(base_filename: *const c_char, rebuilt_ids: *mut u32, n_rebuilt: *mut usize)
                                 -> c_int;
+    pub fn hec_verify_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_bad, cap: usize,
+                               n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
     pub fn hec_write_sorted_file_from_index(base_filename: *const c_char, ext: *const c_char) -> c_int;
     pub fn hec_rebuild_ecx_file(base_filename: *const c_char) -> c_int;
     pub fn hec_save_volume_info(filename: *const c_char, version: u32) -> c_int;
@@ -195,5 +215,6 @@ extern "C" {
     pub fn hec_version() -> *const c_char;
     pub fn hec_encode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_decode_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_ragged_kernel_name(descs: *const hec_stripe_desc, n_stripes: u32, decode: c_int) -> *const c_char;
 }

@@ -451,6 +451,30 @@ pub fn rebuild_ec_files(base_filename: &str) -> Result<Vec<u32>, EcShardError> {
     }
 }
 
+/// One column block of the shard files whose stored parity differs from its
+/// data's: byte offset in the shard files, length, bit j = `.ec(10+j)` differs.
+pub type ScrubBad = sys::hec_scrub_bad;
+
+/// Scrub `base.ec00`..`base.ec13` on the GPU (`hec_verify_ec_files`; no helyim
+/// counterpart). `block_size` 0 = 1 MiB column blocks. Returns the number of
+/// blocks checked, the number of bad blocks (the total) and the first
+/// `min(cap, bad)` of them in ascending offset. Reads only; a missing shard
+/// file comes back as `ErasureCoding(Error::Device(49, ..))`.
+pub fn verify_ec_files(base_filename: &str, block_size: u64, cap: usize)
+                       -> Result<(u64, usize, Vec<ScrubBad>), EcShardError> {
+    let c = cstr(base_filename)?;
+    let mut bad = vec![ScrubBad::default(); cap];
+    let (mut n_bad, mut n_blocks) = (0usize, 0u64);
+    let p = if cap == 0 { std::ptr::null_mut() } else { bad.as_mut_ptr() };
+    match unsafe { sys::hec_verify_ec_files(c.as_ptr(), block_size, p, cap, &mut n_bad, &mut n_blocks) } {
+        0 => {
+            bad.truncate(n_bad.min(cap));
+            Ok((n_blocks, n_bad, bad))
+        }
+        code => Err(file_err(code)),
+    }
+}
+
 /// Pinned host memory for the host-batch calls, freed on drop
 /// (`hec_host_alloc` / `hec_host_alloc_multi` + `hec_host_free`). Pinned
 /// batches are coded zero-copy.

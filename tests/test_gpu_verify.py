@@ -1,0 +1,452 @@
+"""Batched parity verify (scrub) on the GPU: hec_gpu_verify_batch,
+hec_host_verify_batch and hec_verify_ec_files against the C oracle.
+
+The expected word of a stripe always comes from the oracle: CReedSolomon(k,
+m).encode on a copy of the stripe's current data shards, bit j =
+any(oracle_parity[j] != stored_parity[j]) -- which also covers data-shard
+corruption without assuming which coefficients are non-zero. Shards live in
+tests/footprint.py arenas of seeded random bytes, so gaps, slack and the pads
+past a shard's end are garbage: a verify that compares a byte at or past
+shard_len reports a false mismatch here. Every device call is also a footprint
+check: the arenas must come back byte for byte, the result word at index S
+untouched."""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import footprint as F
+from oracle import corc
+
+pytestmark = pytest.mark.gpu
+
+INVALID_ARGUMENT, EC_SHARD_SIZE, SHARD_NOT_FOUND = 66, 34, 49
+SENTINEL = 0x5A5AA5A5
+LENGTHS = (8192, 16384, 8192 + 2048, 4096 + 16, 1000, 17, 1)
+
+
+def layouts(k, m, L, S):
+    """(name, data layout, parity layout): stripe-major with a 48-byte shard
+    gap, shard-major, data and parity in separate arenas, an odd base."""
+    n = k + m
+    a = F.stripe_major(n, L, S, F.r16(L) + 48, 16)
+    b = F.shard_major(n, L, S, F.r16(L) + 16, 48)
+    d = F.stripe_major(n, L, S, F.r16(L) + 16, 16, base=F.SLACK + 3)
+    yield "stripe-major gap 48", a.sub(0, k), a.sub(k, m)
+    yield "shard-major", b.sub(0, k), b.sub(k, m)
+    yield "separate arenas", F.stripe_major(k, L, S, F.r16(L) + 48, 16), \
+        F.shard_major(m, L, S, F.r16(L) + 16, 48, arena=1)
+    yield "odd base", d.sub(0, k), d.sub(k, m)
+
+
+@functools.lru_cache(maxsize=None)
+def clean_case(k, m, L, S, which):
+    """A layout and its arenas with correct parity everywhere (never modified:
+    tests corrupt copies). -> (name, data, par, stripes, arenas)."""
+    name, data, par = list(layouts(k, m, L, S))[which]
+    stripes = F.stripes_of(data, par)
+    rng = np.random.default_rng(1000 * L + 10 * S + which + 7 * k + m)
+    raw = [F.random_arena(sz, rng) for sz in F.arena_sizes(stripes)]
+    arenas = F.plan_encode(raw, stripes, k, m).expected  # the raw bytes with the oracle's parity in place
+    for a in arenas:
+        a.setflags(write=False)
+    return name, data, par, stripes, arenas
+
+
+def copies(arenas):
+    return [np.array(a, copy=True) for a in arenas]
+
+
+def shard_of(arenas, stripes, s, i):
+    a, o = stripes[s].locs[i]
+    return arenas[a][o:o + stripes[s].L]
+
+
+def oracle_words(arenas, stripes, k, m):
+    rs = corc.CReedSolomon(k, m)
+    words = []
+    for s, st in enumerate(stripes):
+        bufs = [shard_of(arenas, stripes, s, i).copy() for i in range(k)] + \
+               [np.zeros(st.L, np.uint8) for _ in range(m)]
+        rs.encode(bufs)
+        words.append(sum(1 << j for j in range(m) if (bufs[k + j] != shard_of(arenas, stripes, s, k + j)).any()))
+    return words
+
+
+def device_verify(rs, arenas, stripes, data, par, preset_bad=7):
+    """Run hec_gpu_verify_batch on the arenas -> (words [S], bad_stripes).
+    Asserts the footprint: arenas unchanged, word S untouched."""
+    import torch
+    import helyim_amd as H
+    S = data.S
+    devs = [torch.from_numpy(a).cuda() for a in arenas]
+    assert all(d.data_ptr() % 256 == 0 for d in devs)
+    res = torch.full((S + 1,), -1, dtype=torch.int32, device="cuda")  # 0xFFFFFFFF: stale words must not leak
+    res[S] = SENTINEL
+    bad = torch.full((1,), preset_bad, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    rc = H.lib.hec_gpu_verify_batch(rs.handle, devs[data.arena].data_ptr() + data.base, data.stripe_stride,
+                                    data.shard_stride, devs[par.arena].data_ptr() + par.base, par.stripe_stride,
+                                    par.shard_stride, data.L, S, res.data_ptr(), bad.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, (rc, H._lib.last_detail())
+    torch.cuda.synchronize()
+    F.assert_unchanged(arenas, [d.cpu().numpy() for d in devs], stripes)
+    out = res.cpu().numpy().view(np.uint32)
+    assert int(out[S]) == SENTINEL
+    return [int(w) for w in out[:S]], int(bad.item())
+
+
+def flip_positions(L):
+    return sorted({p for p in (0, L - 1, 4095, 4096, 16 * 255, 8191, 8192) if 0 <= p < L})
+
+
+# ---- device batches --------------------------------------------------------------
+@pytest.mark.parametrize("L", LENGTHS)
+def test_clean_batch_every_layout(gpu, L):
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    for which in range(4):
+        name, data, par, stripes, arenas = clean_case(10, 4, L, 5, which)
+        words, bad = device_verify(rs, copies(arenas), stripes, data, par)
+        assert words == [0] * 5, (name, [hex(w) for w in words])
+        assert bad == 7, name
+
+
+@pytest.mark.parametrize("L", LENGTHS)
+def test_single_byte_flips(gpu, L):
+    """One flipped byte per stripe, one stripe of each launch left clean: every
+    position of interest in every parity shard (word exactly 1 << j) and in
+    data shards 0, 4 and 9 (the oracle's word), on the aligned stripe-major
+    layout and on the odd base (the generic kernel's unaligned path)."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    S = 5
+    combos = [(shard, pos) for shard in (10, 11, 12, 13, 0, 4, 9) for pos in flip_positions(L)]
+    for which in (0, 3):
+        name, data, par, stripes, arenas = clean_case(10, 4, L, S, which)
+        for b0 in range(0, len(combos), S - 1):
+            batch = combos[b0:b0 + S - 1]
+            clean_stripe = (b0 // (S - 1)) % S
+            targets = [s for s in range(S) if s != clean_stripe][:len(batch)]
+            work = copies(arenas)
+            for s, (shard, pos) in zip(targets, batch):
+                shard_of(work, stripes, s, shard)[pos] ^= 0x40
+            want = oracle_words(work, stripes, 10, 4)
+            for s, (shard, pos) in zip(targets, batch):
+                if shard >= 10:
+                    assert want[s] == 1 << (shard - 10)
+                else:
+                    assert want[s] != 0
+            assert [want[s] for s in range(S) if s not in targets] == [0] * (S - len(targets))
+            words, bad = device_verify(rs, work, stripes, data, par)
+            assert words == want, (name, batch, [hex(w) for w in words], [hex(w) for w in want])
+            assert bad == 7 + len(batch), (name, batch)
+
+
+def test_single_bit_flips_reach_every_bit_plane(gpu):
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    S = 9
+    name, data, par, stripes, arenas = clean_case(10, 4, 8192, S, 0)
+    assert H.lib.hec_verify_kernel_name(8192).decode().startswith("rs104_bs_verify_kernel")
+    work = copies(arenas)
+    for bit in range(8):
+        shard_of(work, stripes, bit, 12)[4097 + 16 * bit] ^= 1 << bit
+    want = oracle_words(work, stripes, 10, 4)
+    assert want == [1 << 2] * 8 + [0]
+    words, bad = device_verify(rs, work, stripes, data, par)
+    assert words == want and bad == 7 + 8
+
+
+@pytest.mark.parametrize("which", [0, 3])
+def test_bad_stripes_counts_a_stripe_exactly_once(gpu, which):
+    """Stripe 0 is corrupted in three different 8 KiB chunks and two parity
+    shards, stripe 2 once: bad_stripes goes 7 -> 9."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    L = 4 * 8192
+    name, data, par, stripes, arenas = clean_case(10, 4, L, 3, which)
+    work = copies(arenas)
+    for shard, pos in ((11, 5), (11, 8192 + 4100), (13, 3 * 8192 + 8191), (13, 77)):
+        shard_of(work, stripes, 0, shard)[pos] ^= 0xFF
+    shard_of(work, stripes, 2, 10)[L - 1] ^= 1
+    want = oracle_words(work, stripes, 10, 4)
+    assert want == [0b1010, 0, 0b0001]
+    words, bad = device_verify(rs, work, stripes, data, par)
+    assert words == want and bad == 9, (name, words, bad)
+
+
+@pytest.mark.parametrize("k,m", [(5, 5), (3, 2), (17, 3), (4, 32)])
+@pytest.mark.parametrize("L", [4096, 100])
+def test_other_codecs_take_the_generic_kernel(gpu, k, m, L):
+    """Clean, then one flip per parity shard (stripe j: parity shard j; the
+    last stripe stays clean)."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(k, m)
+    S = m + 1
+    for which in (0, 3):
+        name, data, par, stripes, arenas = clean_case(k, m, L, S, which)
+        words, bad = device_verify(rs, copies(arenas), stripes, data, par)
+        assert words == [0] * S and bad == 7, name
+        work = copies(arenas)
+        for j in range(m):
+            shard_of(work, stripes, j, k + j)[(37 * j + L - 1) % L] ^= 0x81
+        want = oracle_words(work, stripes, k, m)
+        assert want == [1 << j for j in range(m)] + [0]
+        words, bad = device_verify(rs, work, stripes, data, par)
+        assert words == want and bad == 7 + m, (name, [hex(w) for w in words])
+
+
+def test_more_than_32_parity_shards_is_refused(gpu):
+    import torch
+    import helyim_amd as H
+    rs = H.ReedSolomon(4, 33)
+    t = torch.zeros(37 * 64, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(2, dtype=torch.int32, device="cuda")
+    assert H.lib.hec_gpu_verify_batch(rs.handle, t.data_ptr(), 37 * 64, 64, t.data_ptr() + 4 * 64, 37 * 64, 64, 64, 1,
+                                      res.data_ptr(), None, None) == INVALID_ARGUMENT
+
+
+def test_encode_then_verify_in_stream_order(gpu):
+    """encode_batch then verify_batch on one non-default stream, no synchronise between."""
+    import torch
+    import helyim_amd as H
+    from helyim_amd import batch
+    rs = H.ReedSolomon(10, 4)
+    g = torch.Generator(device="cuda").manual_seed(11)
+    t = torch.randint(0, 256, (6, 14, 16384), dtype=torch.uint8, device="cuda", generator=g)
+    res = torch.full((6,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    batch.encode_batch(rs, t, stream=s)
+    out = H.verify_batch(rs, t, mismatch=res, stream=s)
+    s.synchronize()
+    assert out is res and res.cpu().tolist() == [0] * 6
+    # and the Python mirror's other shapes: allocated result, separate buffers
+    t[3, 11, 9000] ^= 0x10
+    torch.cuda.synchronize()
+    assert H.verify_batch(rs, t).cpu().tolist() == [0, 0, 0, 2, 0, 0]
+    data, par = t[:, :10].contiguous(), t[:, 10:].contiguous()
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    assert H.verify_batch_sep(rs, data, par, bad_stripes=bad).cpu().tolist() == [0, 0, 0, 2, 0, 0]
+    assert int(bad.item()) == 1
+    with pytest.raises(ValueError):
+        H.verify_batch(rs, t, mismatch=torch.zeros(5, dtype=torch.int32, device="cuda"))
+    with pytest.raises(ValueError):
+        H.verify_batch(rs, t, mismatch=torch.zeros(6, dtype=torch.int64, device="cuda"))
+
+
+def test_kernel_names(gpu):
+    import helyim_amd as H
+    assert H.verify_kernel_name(1 << 20) == "rs104_bs_verify_kernel (bit-sliced)"
+    assert H.verify_kernel_name(1000).startswith("rs_verify_kernel")
+    assert H.verify_kernel_name(0).startswith("none")
+
+
+# ---- host batches ----------------------------------------------------------------
+def host_words(rs, base_ptr, L, S, pitch):
+    import helyim_amd as H
+    words = (ctypes.c_uint32 * (S + 1))(*([0xFFFFFFFF] * S + [SENTINEL]))
+    n_bad = ctypes.c_uint32(1234)  # set, not accumulated
+    rc = H.lib.hec_host_verify_batch(rs.handle, base_ptr, 14 * pitch, pitch, base_ptr + 10 * pitch, 14 * pitch, pitch,
+                                     L, S, words, ctypes.byref(n_bad))
+    assert rc == 0, (rc, H._lib.last_detail())
+    assert words[S] == SENTINEL
+    return [int(w) for w in words[:S]], int(n_bad.value)
+
+
+@pytest.mark.parametrize("L", [8192, 1000])
+def test_host_batch_three_paths_agree(gpu, L):
+    import torch
+    import helyim_amd as H
+    from helyim_amd import batch
+    rs = H.ReedSolomon(10, 4)
+    S, pitch = 3, F.r16(L) + 48
+    rng = np.random.default_rng(L)
+    image = rng.integers(0, 256, S * 14 * pitch, dtype=np.uint8)  # garbage in the shard gaps too
+    view = image.reshape(S, 14, pitch)
+    for s in range(S):
+        bufs = [view[s, i, :L].copy() for i in range(10)] + [np.zeros(L, np.uint8) for _ in range(4)]
+        corc.CReedSolomon(10, 4).encode(bufs)
+        for j in range(4):
+            view[s, 10 + j, :L] = bufs[10 + j]
+    dirty = image.copy()
+    dv = dirty.reshape(S, 14, pitch)
+    dv[0, 12, L - 1] ^= 0x01
+    dv[2, 4, 0] ^= 0x80
+    stripes = F.stripes_of(F.stripe_major(14, L, S, pitch, 0, base=0))
+    want = oracle_words([dirty], stripes, 10, 4)
+    assert want[0] == 1 << 2 and want[1] == 0 and want[2] != 0
+
+    pinned = H.HostBuffer(image.nbytes)
+    results = {}
+    try:
+        for label, img in (("clean", image), ("dirty", dirty)):
+            expect = [0] * S if label == "clean" else want
+            # pinned, GPU-addressable memory: read in place
+            pinned.array[:] = img
+            assert batch.host_zero_copy(pinned.tensor((S, 14, pitch)))
+            results[label, "pinned"] = host_words(rs, pinned.ptr, L, S, pitch)
+            assert (pinned.array == img).all()
+            # pageable memory through the pinned slots; for the short length a
+            # full-size batch of random stripes goes first, so the reused slots
+            # hold garbage where this call's pads fall
+            page = img.copy()
+            if L == 1000:
+                big = rng.integers(0, 256, S * 14 * 8192, dtype=np.uint8)
+                w, nb = host_words(rs, big.ctypes.data, 8192, S, 8192)
+                assert all(w) and nb == S
+            results[label, "pageable"] = host_words(rs, page.ctypes.data, L, S, pitch)
+            assert (page == img).all()
+            assert H.lib.hec_set_host_zero_copy(0) == 0
+            try:
+                if L == 1000:  # the same for the device slots of the copy pipeline
+                    assert all(host_words(rs, big.ctypes.data, 8192, S, 8192)[0])
+                results[label, "copies"] = host_words(rs, page.ctypes.data, L, S, pitch)
+            finally:
+                assert H.lib.hec_set_host_zero_copy(1) == 0
+            for path in ("pinned", "pageable", "copies"):
+                assert results[label, path] == (expect, sum(1 for w in expect if w)), (label, path, results)
+        t = torch.from_numpy(dirty).view(S, 14, pitch)[:, :, :L]
+        assert batch.host_verify_batch(rs, t).tolist() == want
+    finally:
+        H.lib.hec_set_host_zero_copy(1)
+        pinned.close()
+
+
+# ---- shard files -----------------------------------------------------------------
+BLOCK = 4096
+
+
+@pytest.fixture(scope="module")
+def shard_files(tmp_path_factory):
+    """Oracle-written shard files of a seeded .dat: small geometry, each shard
+    a few hundred KiB and not a multiple of the 4096-byte scrub block."""
+    d = tmp_path_factory.mktemp("scrub")
+    base = str(d / "7")
+    large, small = 64 * 1001, 1001  # three large rows, then 58 small ones: 250250 bytes per shard
+    open(base + ".dat", "wb").write(corc.splitmix64_bytes(99, 10 * large * 3 + 10 * small * 57 + 123).tobytes())
+    assert corc.write_ec_files(base, small, large, small) == 0
+    files = [open(base + ".ec%02d" % i, "rb").read() for i in range(14)]
+    size = len(files[0])
+    assert all(len(f) == size for f in files) and 200_000 < size < 500_000
+    assert size % BLOCK > 1 and (size % BLOCK) % 16 != 0  # a short last block with a ragged tail
+    return base, files, size
+
+
+def scrub_copy(shard_files, tmp_path):
+    base, files, size = shard_files
+    new = str(tmp_path / "v")
+    for i, f in enumerate(files):
+        open(new + ".ec%02d" % i, "wb").write(f)
+    return new, [bytearray(f) for f in files], size
+
+
+def flip(base, shard, offset):
+    with open(base + ".ec%02d" % shard, "r+b") as f:
+        f.seek(offset)
+        b = f.read(1)
+        f.seek(offset)
+        f.write(bytes([b[0] ^ 0x5A]))
+
+
+def file_oracle_mask(files, lo, hi):
+    rs = corc.CReedSolomon(10, 4)
+    bufs = [np.frombuffer(bytes(files[i][lo:hi]), np.uint8).copy() for i in range(10)] + \
+           [np.zeros(hi - lo, np.uint8) for _ in range(4)]
+    rs.encode(bufs)
+    return sum(1 << j for j in range(4)
+               if (bufs[10 + j] != np.frombuffer(bytes(files[10 + j][lo:hi]), np.uint8)).any())
+
+
+def test_files_clean_and_read_only(gpu, shard_files, tmp_path):
+    import helyim_amd as H
+    base, files, size = scrub_copy(shard_files, tmp_path)
+    for i in range(14):
+        os.utime(base + ".ec%02d" % i, ns=(10**18, 10**18 + i))
+    before = [os.stat(base + ".ec%02d" % i).st_mtime_ns for i in range(14)]
+    n_blocks, n_bad, bad = H.verify_ec_files(base, BLOCK)
+    assert (n_blocks, n_bad, bad) == (-(-size // BLOCK), 0, [])
+    # the default 1 MiB block: one short block
+    assert H.verify_ec_files(base) == (1, 0, [])
+    assert [os.stat(base + ".ec%02d" % i).st_mtime_ns for i in range(14)] == before
+    assert [open(base + ".ec%02d" % i, "rb").read() for i in range(14)] == [bytes(f) for f in files]
+
+
+def test_files_flips_are_located(gpu, shard_files, tmp_path):
+    import helyim_amd as H
+    base, files, size = scrub_copy(shard_files, tmp_path)
+    x = 5 * BLOCK + 1234
+    flip(base, 3, x)
+    files[3][x] ^= 0x5A
+    lo = x // BLOCK * BLOCK
+    mask = file_oracle_mask(files, lo, lo + BLOCK)
+    assert mask != 0
+    assert H.verify_ec_files(base, BLOCK) == (-(-size // BLOCK), 1, [(lo, BLOCK, mask)])
+    # the short last block
+    last = size // BLOCK * BLOCK
+    flip(base, 12, size - 1)
+    files[12][size - 1] ^= 0x5A
+    assert H.verify_ec_files(base, BLOCK) == (-(-size // BLOCK), 2, [(lo, BLOCK, mask), (last, size - last, 1 << 2)])
+    # a third bad block, cap 2: the total and the first two in ascending offset
+    flip(base, 10, 0)
+    n_blocks, n_bad, bad = H.verify_ec_files(base, BLOCK, cap=2)
+    assert (n_bad, bad) == (3, [(0, BLOCK, 1), (lo, BLOCK, mask)])
+    assert H.verify_ec_files(base, BLOCK, cap=0) == (n_blocks, 3, [])
+    # 8 KiB blocks take the bit-sliced kernel for the whole blocks
+    got = H.verify_ec_files(base, 2 * BLOCK)
+    l2 = x // (2 * BLOCK) * (2 * BLOCK)
+    last2 = size // (2 * BLOCK) * (2 * BLOCK)
+    assert got == (-(-size // (2 * BLOCK)), 3, [(0, 2 * BLOCK, 1), (l2, 2 * BLOCK, mask),
+                                                (last2, size - last2, 1 << 2)])
+
+
+def test_files_longer_than_the_two_slots(gpu, tmp_path):
+    """Shards of 8 MiB and a ragged rest: three chunks of the scrub's 4 MiB
+    column range, so both pinned slots are reused and the results of a chunk
+    are collected while later ones are in flight. Parity is bytewise, so the
+    files are the oracle's encode of ten random streams, no block geometry."""
+    import helyim_amd as H
+    block, size = 65536, (8 << 20) + 300_000 + 7
+    rng = np.random.default_rng(2024)
+    bufs = [rng.integers(0, 256, size, dtype=np.uint8) for _ in range(10)] + [np.zeros(size, np.uint8) for _ in range(4)]
+    corc.CReedSolomon(10, 4).encode(bufs)
+    hits = [(11, 5), (2, (4 << 20) - 1), (13, (4 << 20)), (10, (8 << 20) + 12345), (12, size - 1)]
+    want = {}
+    for shard, off in hits:
+        bufs[shard][off] ^= 0x33
+    for shard, off in hits:
+        lo = off // block * block
+        want[lo] = (lo, min(block, size - lo), file_oracle_mask(bufs, lo, min(lo + block, size)))
+    base = str(tmp_path / "big")
+    for i in range(14):
+        bufs[i].tofile(base + ".ec%02d" % i)
+    assert want[0][2] == 1 << 1 and want[size // block * block] == (size // block * block, size % block, 1 << 2)
+    assert H.verify_ec_files(base, block) == (-(-size // block), len(want), [want[k] for k in sorted(want)])
+    # 1 MiB blocks: four blocks per chunk; the same bytes, coarser
+    n_blocks, n_bad, bad = H.verify_ec_files(base)
+    assert (n_blocks, n_bad) == (9, 4) and [b[0] >> 20 for b in bad] == [0, 3, 4, 8]
+    assert bad[3] == (8 << 20, size - (8 << 20), file_oracle_mask(bufs, 8 << 20, size))
+
+
+def test_files_errors(gpu, shard_files, tmp_path):
+    import helyim_amd as H
+    base, files, size = scrub_copy(shard_files, tmp_path)
+    lib = H.lib
+    nb, nbl = ctypes.c_size_t(9), ctypes.c_uint64(9)
+    assert lib.hec_verify_ec_files(base.encode(), 1000, None, 0, ctypes.byref(nb), ctypes.byref(nbl)) == INVALID_ARGUMENT
+    os.truncate(base + ".ec05", size - 1)
+    assert lib.hec_verify_ec_files(base.encode(), BLOCK, None, 0, ctypes.byref(nb), ctypes.byref(nbl)) == EC_SHARD_SIZE
+    assert H._lib.last_values()[:2] == (size, size - 1)
+    with pytest.raises(H.UnexpectedEcShardSize):
+        H.verify_ec_files(base, BLOCK)
+    os.remove(base + ".ec13")
+    assert lib.hec_verify_ec_files(base.encode(), BLOCK, None, 0, ctypes.byref(nb), ctypes.byref(nbl)) == SHARD_NOT_FOUND
+    assert ".ec13" in H._lib.last_detail()
+    empty = str(tmp_path / "e")
+    for i in range(14):
+        open(empty + ".ec%02d" % i, "wb").close()
+    assert H.verify_ec_files(empty, BLOCK) == (0, 0, [])
