@@ -33,7 +33,7 @@
 #include <chrono>
 #include <thread>
 
-#include "hec_internal.hpp"
+#include "file_util.hpp"
 
 namespace hec {
 namespace {
@@ -43,27 +43,6 @@ constexpr int kSlots = 3;                      // pipeline depth (profiles/r01/a
 constexpr uint64_t kBatchBytes = 256ull << 20;  // data bytes per GPU job
 constexpr uint64_t kLargeSlice = 16ull << 20;   // per-shard slice of a large row
 constexpr int kIoThreads = 16;
-
-std::string shard_name(const std::string& base, int i) {
-    char ext[8];
-    std::snprintf(ext, sizeof ext, ".ec%02d", i);  // to_ext, helyim-ec/src/lib.rs:84-86
-    return base + ext;
-}
-
-struct Fd {
-    int fd = -1;
-    ~Fd() {
-        if (fd >= 0) ::close(fd);
-    }
-};
-
-// An I/O failure (errno) as the first-error record of the pipeline's threads.
-void io_error(ErrorSlot& e, const std::string& what) {
-    const int err = errno;
-    ErrorValues v;
-    v.os_errno = err;
-    e.set(HEC_ERR_IO, what + ": " + std::strerror(err), v);
-}
 
 // ---------------------------------------------------------------------------
 // Small fixed thread pool with fork/join task groups.
@@ -128,20 +107,14 @@ class Pool {
     bool stop_ = false;
 };
 
-// pread that loops over short reads and zero-fills past EOF (encoder.rs:169-189).
+// pread_full that zero-fills past EOF (encoder.rs:169-189).
 bool pread_zero(int fd, uint8_t* dst, uint64_t len, uint64_t off, ErrorSlot& e) {
-    uint64_t got = 0;
-    while (got < len) {
-        ssize_t r = ::pread(fd, dst + got, len - got, off_t(off + got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            io_error(e, "read");
-            return false;
-        }
-        if (r == 0) break;
-        got += uint64_t(r);
+    const ssize_t got = pread_full(fd, dst, len, off);
+    if (got < 0) {
+        io_error(e, "read");
+        return false;
     }
-    if (got < len) std::memset(dst + got, 0, len - got);
+    std::memset(dst + got, 0, len - uint64_t(got));
     return true;
 }
 
@@ -375,11 +348,6 @@ int lease_pipeline(uint64_t host_bytes, uint64_t dev_bytes, FileLease& out) {
     return out.pipe->ensure(host_bytes, dev_bytes);
 }
 
-struct Rs104 {
-    hec_rs_t* rs = nullptr;
-    ~Rs104() { hec_rs_free(rs); }
-};
-
 // Reserve the final size of freshly created output files, one fallocate per
 // file on its own thread, while the first jobs are read and coded: the
 // returned future gates the pipeline's writes. FALLOC_FL_KEEP_SIZE leaves the
@@ -474,7 +442,7 @@ static int write_ec_files_impl(const std::string& base, uint64_t buf_size, uint6
     if (::fstat(dat.fd, &st) != 0) return fail_errno(HEC_ERR_IO, "stat .dat", errno);
     int64_t remaining = int64_t(st.st_size);
 
-    Rs104 rs;  // ReedSolomon::new(10, 4) (encoder.rs:208-209)
+    RsGuard rs;  // ReedSolomon::new(10, 4) (encoder.rs:208-209)
     int rc = hec_rs_new(K, M, &rs.rs);
     if (rc) return rc;
     if (buf_size == 0) return fail(HEC_ERR_INVALID_ARGUMENT, "zero buffer size");
@@ -583,7 +551,7 @@ static int rebuild_ec_files_impl(const std::string& base, uint32_t* ids, size_t*
     // the present files' sizes exactly as the reference's read_at sequence
     // decides them: n = min(1 MiB, size - offset); stop at the first n == 0;
     // every n must equal the first one (UnexpectedEcShardSize).
-    Rs104 rs;
+    RsGuard rs;
     int rc = hec_rs_new(K, M, &rs.rs);
     if (rc) return rc;
     const uint64_t SB = HEC_SMALL_BLOCK_SIZE;

@@ -19,29 +19,15 @@
 #include <string>
 #include <vector>
 
-#include "hec_internal.hpp"
+#include "file_util.hpp"
 
 namespace hec {
 namespace {
 
 constexpr uint64_t kEntry = 16;  // NEEDLE_ENTRY_SIZE: u64 id, u32 offset/8, i32 size, big endian
 
-int io(const std::string& what) { return fail_errno(HEC_ERR_IO, what, errno); }
 int eof(const std::string& what) { return fail(HEC_ERR_IO, what + ": failed to fill whole buffer"); }
 
-struct File {
-    int fd = -1;
-    ~File() {
-        if (fd >= 0) ::close(fd);
-    }
-};
-
-uint64_t be64(const uint8_t* p) {
-    uint64_t v = 0;
-    for (int i = 0; i < 8; ++i) v = (v << 8) | p[i];
-    return v;
-}
-uint32_t be32(const uint8_t* p) { return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3]; }
 void put_be64(uint8_t* p, uint64_t v) {
     for (int i = 7; i >= 0; --i, v >>= 8) p[i] = uint8_t(v);
 }
@@ -53,20 +39,11 @@ bool read_all(int fd, std::vector<uint8_t>& out) {
     struct stat st;
     if (::fstat(fd, &st) != 0) return false;
     out.resize(size_t(st.st_size));
-    size_t got = 0;
-    while (got < out.size()) {
-        ssize_t r = ::pread(fd, out.data() + got, out.size() - got, off_t(got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return false;
-        }
-        if (r == 0) break;
-        got += size_t(r);
-    }
-    out.resize(got);
+    const ssize_t got = pread_full(fd, out.data(), out.size(), 0);
+    if (got < 0) return false;
+    out.resize(size_t(got));  // a file that shrank since the fstat
     return true;
 }
-
 
 bool write_all(int fd, const uint8_t* p, size_t n) {
     while (n) {
@@ -116,7 +93,7 @@ extern "C" {
 int hec_write_sorted_file_from_index(const char* base_filename, const char* ext) {
     if (!base_filename || !ext) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     const std::string base(base_filename);
-    File idx;
+    Fd idx;
     idx.fd = ::open((base + ".idx").c_str(), O_RDONLY);
     if (idx.fd < 0) return io("open " + base + ".idx");
     std::vector<uint8_t> buf;
@@ -134,7 +111,7 @@ int hec_write_sorted_file_from_index(const char* base_filename, const char* ext)
             live[key] = {off, size};
     }
     if (buf.size() % kEntry) return eof("read .idx entry");
-    File out;
+    Fd out;
     out.fd = ::open((base + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (out.fd < 0) return io("open " + base + ext);
     std::vector<uint8_t> o(live.size() * kEntry);
@@ -165,7 +142,7 @@ int hec_rebuild_ecx_file(const char* base_filename) {
         }
         return HEC_OK;
     }
-    File ecx, j;
+    Fd ecx, j;
     ecx.fd = ::open((base + ".ecx").c_str(), O_RDWR);
     if (ecx.fd < 0) return io("open " + base + ".ecx");
     struct stat st;
@@ -182,7 +159,7 @@ int hec_rebuild_ecx_file(const char* base_filename) {
         uint64_t lo = 0, hi = n_entries;
         while (lo < hi) {
             const uint64_t mid = (lo + hi) / 2;
-            ssize_t r = ::pread(ecx.fd, e, kEntry, off_t(mid * kEntry));
+            const ssize_t r = pread_full(ecx.fd, e, kEntry, mid * kEntry);
             if (r != ssize_t(kEntry)) return r < 0 ? io("read .ecx") : eof("read .ecx");
             const uint64_t key = be64(e);
             if (key == want) {
@@ -204,7 +181,7 @@ int hec_rebuild_ecx_file(const char* base_filename) {
 // (volume.proto:75-79), fields in declaration order.
 int hec_save_volume_info(const char* filename, uint32_t version) {
     if (!filename) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    File f;
+    Fd f;
     f.fd = ::open(filename, O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (f.fd < 0) return io(std::string("open ") + filename);
     const std::string json = "{\"files\":[],\"version\":" + std::to_string(version) + ",\"replication\":\"\"}";
@@ -218,14 +195,14 @@ int hec_save_volume_info(const char* filename, uint32_t version) {
 int hec_find_data_filesize(const char* base_filename, uint64_t* out) {
     if (!base_filename || !out) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     const std::string base(base_filename);
-    File ec0;
+    Fd ec0;
     ec0.fd = ::open((base + ".ec00").c_str(), O_RDONLY);
     if (ec0.fd < 0) return io("open " + base + ".ec00");
     uint8_t sb[8];
-    ssize_t r = ::pread(ec0.fd, sb, 8, 0);
+    const ssize_t r = pread_full(ec0.fd, sb, 8, 0);
     if (r != 8) return r < 0 ? io("read superblock") : eof("read superblock");
     if (sb[3] > 6) return fail(HEC_ERR_IO, "Ttl error: invalid unit");
-    File ecx;
+    Fd ecx;
     ecx.fd = ::open((base + ".ecx").c_str(), O_RDONLY);
     if (ecx.fd < 0) return io("open " + base + ".ecx");
     std::vector<uint8_t> buf;
@@ -249,31 +226,21 @@ int hec_find_data_filesize(const char* base_filename, uint64_t* out) {
 int hec_write_data_file(const char* base_filename, int64_t data_filesize) {
     if (!base_filename) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     const std::string base(base_filename);
-    File dat;
+    Fd dat;
     dat.fd = ::open((base + ".dat").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (dat.fd < 0) return io("open " + base + ".dat");
-    File in[10];
+    Fd in[10];
     for (int i = 0; i < 10; ++i) {
-        char ext[8];
-        std::snprintf(ext, sizeof ext, ".ec%02d", i);
-        in[i].fd = ::open((base + ext).c_str(), O_RDONLY);
-        if (in[i].fd < 0) return io("open " + base + ext);
+        in[i].fd = ::open(shard_name(base, i).c_str(), O_RDONLY);
+        if (in[i].fd < 0) return io("open " + shard_name(base, i));
     }
     uint64_t pos[10] = {0};
     std::vector<uint8_t> buf(size_t(16) << 20);
     auto copy = [&](int i, uint64_t n) -> int {
         while (n) {
             const size_t c = size_t(std::min<uint64_t>(n, buf.size()));
-            size_t got = 0;
-            while (got < c) {
-                ssize_t r = ::pread(in[i].fd, buf.data() + got, c - got, off_t(pos[i] + got));
-                if (r < 0) {
-                    if (errno == EINTR) continue;
-                    return io("read shard");
-                }
-                if (r == 0) return eof("read shard");  // read_exact
-                got += size_t(r);
-            }
+            const ssize_t got = pread_full(in[i].fd, buf.data(), c, pos[i]);
+            if (got != ssize_t(c)) return got < 0 ? io("read shard") : eof("read shard");  // read_exact
             if (!write_all(dat.fd, buf.data(), c)) return io("write .dat");
             pos[i] += c;
             n -= c;
@@ -303,7 +270,7 @@ int hec_write_data_file(const char* base_filename, int64_t data_filesize) {
 int hec_write_index_file_from_ec_index(const char* base_filename) {
     if (!base_filename) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     const std::string base(base_filename);
-    File ecx, idx;
+    Fd ecx, idx;
     ecx.fd = ::open((base + ".ecx").c_str(), O_RDONLY);
     if (ecx.fd < 0) return io("open " + base + ".ecx");
     idx.fd = ::open((base + ".idx").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -320,7 +287,7 @@ int hec_write_index_file_from_ec_index(const char* base_filename) {
         }
         return HEC_OK;
     }
-    File j;
+    Fd j;
     j.fd = ::open(ecj.c_str(), O_RDONLY);
     if (j.fd < 0) return io("open " + ecj);
     std::vector<uint8_t> ids;

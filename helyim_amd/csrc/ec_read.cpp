@@ -24,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "hec_internal.hpp"
+#include "file_util.hpp"
 
 namespace hec {
 namespace {
@@ -32,22 +32,6 @@ namespace {
 constexpr uint64_t kDataShards = 10;  // DATA_SHARDS_COUNT
 constexpr int kTotalShards = 14;
 constexpr uint64_t kEntry = 16;  // NEEDLE_ENTRY_SIZE
-
-int io(const std::string& what) { return fail_errno(HEC_ERR_IO, what, errno); }
-
-
-uint64_t be64(const uint8_t* p) {
-    uint64_t v = 0;
-    for (int i = 0; i < 8; ++i) v = (v << 8) | p[i];
-    return v;
-}
-uint32_t be32(const uint8_t* p) { return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3]; }
-
-std::string shard_name(const std::string& base, int id) {
-    char ext[8];
-    std::snprintf(ext, sizeof ext, ".ec%02d", id);
-    return base + ext;
-}
 
 // The base.ecNN files of one volume, opened once per call (missing = -1).
 struct Shards {
@@ -81,21 +65,6 @@ struct Shards {
         return -1;
     }
 };
-
-// pread until n bytes or EOF; returns bytes read or -1
-ssize_t pread_full(int fd, uint8_t* p, size_t n, uint64_t off) {
-    size_t got = 0;
-    while (got < n) {
-        ssize_t r = ::pread(fd, p + got, n - got, off_t(off + got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return -1;
-        }
-        if (r == 0) break;
-        got += size_t(r);
-    }
-    return ssize_t(got);
-}
 
 // locate_offset (locate.rs:74-94) + locate_offset_within_blocks (:96-100)
 void locate_offset(uint64_t large, uint64_t small, uint64_t data_size, uint64_t offset, uint64_t* block_index,

@@ -182,12 +182,11 @@ int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
     return HEC_OK;
 }
 
-int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uint64_t in_stripe,
-              uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
-              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
-              hipStream_t s, Completion* done, bool over_pcie) {
-    ApplyArgs a{};
-    if (done) HEC_TRY(done->arm(s, &a.done_count, &a.done_flag, &a.done_seq));
+// The coding arguments every strided launch shares, from a plan set and the
+// batch's layout. Returns whether every base and stride is 16-byte aligned.
+static bool fill_args(ApplyArgs& a, const DevicePlanSet& ps, const uint8_t* in_base, uint64_t in_stripe,
+                      uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard, uint64_t len,
+                      uint32_t n_stripes, uint32_t* bad) {
     a.in_base = in_base;
     a.in_stripe = in_stripe;
     a.in_shard = in_shard;
@@ -199,15 +198,25 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
     a.plans = ps.plans;
     a.tabs = ps.tabs;
     a.idx = ps.idx;
-    a.masks = masks;
-    a.lut = ps.lut;
     a.bad_count = bad;
     a.fast104 = ps.fast104 ? 1u : 0u;
-    a.mask_limit = ps.lut_bits ? ((1u << ps.lut_bits) - 1u) : 0u;
-    if (masks && !ps.lut) return fail(HEC_ERR_INVALID_ARGUMENT, "per-stripe masks need a decode LUT");
     const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(in_base)) | in_stripe | in_shard |
                            uint64_t(reinterpret_cast<uintptr_t>(out_base)) | out_stripe | out_shard;
-    const bool aligned = (align % 16) == 0;
+    return (align % 16) == 0;
+}
+
+int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uint64_t in_stripe,
+              uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
+              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
+              hipStream_t s, Completion* done, bool over_pcie) {
+    ApplyArgs a{};
+    if (done) HEC_TRY(done->arm(s, &a.done_count, &a.done_flag, &a.done_seq));
+    const bool aligned =
+        fill_args(a, ps, in_base, in_stripe, in_shard, out_base, out_stripe, out_shard, len, n_stripes, bad);
+    a.masks = masks;
+    a.lut = ps.lut;
+    a.mask_limit = ps.lut_bits ? ((1u << ps.lut_bits) - 1u) : 0u;
+    if (masks && !ps.lut) return fail(HEC_ERR_INVALID_ARGUMENT, "per-stripe masks need a decode LUT");
     HEC_HIP(launch_apply(a, int(nin), aligned, over_pcie && !masks, s));
     return HEC_OK;
 }
@@ -217,26 +226,12 @@ int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint6
                uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s) {
     if (n_stripes == 0) return HEC_OK;
     VerifyArgs v{};
-    ApplyArgs& a = v.a;
-    a.in_base = data;
-    a.in_stripe = data_stripe;
-    a.in_shard = data_shard;
-    a.out_base = const_cast<uint8_t*>(parity);  // only read
-    a.out_stripe = parity_stripe;
-    a.out_shard = parity_shard;
-    a.len = len;
-    a.n_stripes = n_stripes;
-    a.plans = ps.plans;
-    a.tabs = ps.tabs;
-    a.idx = ps.idx;
-    a.bad_count = bad;
-    a.fast104 = ps.fast104 ? 1u : 0u;
     v.mismatch = mismatch;
-    const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(data)) | data_stripe | data_shard |
-                           uint64_t(reinterpret_cast<uintptr_t>(parity)) | parity_stripe | parity_shard;
+    const bool aligned = fill_args(v.a, ps, data, data_stripe, data_shard, const_cast<uint8_t*>(parity) /* only read */,
+                                   parity_stripe, parity_shard, len, n_stripes, bad);
     // the kernels only ever OR bits in: stale words must not leak through
     HEC_HIP(hipMemsetAsync(mismatch, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_verify(v, int(nin), (align % 16) == 0, s));
+    HEC_HIP(launch_verify(v, int(nin), aligned, s));
     return HEC_OK;
 }
 

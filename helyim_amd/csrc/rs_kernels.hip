@@ -21,6 +21,9 @@
 //  * The encode of shard lengths that are a multiple of 8 KiB is bit-sliced
 //    (rs104_bs_encode_kernel): the fixed parity matrix as a generated XOR
 //    program over bit planes, half the table multiply's VALU work.
+//  * The parity verify (scrub) kernels have no coding body of their own:
+//    rs104_bs_chunk and apply_group take a compile-time VERIFY flag that
+//    turns their stores into a compare with the stored rows.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -34,6 +37,7 @@
 
 #include "rs_kernels.hpp"
 #include "bitslice.hpp"
+#include "launch_split.hpp"
 
 namespace hec {
 
@@ -184,16 +188,23 @@ __device__ __forceinline__ void gf_mac2(V (&acc)[R], const V d0, const V d1, cu3
 // K > 0: compile-time input count (all K loads issued before any math);
 // K == 0: runtime nin loop. Lanes whose vector crosses the end of the shard
 // take the byte-wise tail path (only in the last chunk of a stripe).
-template <int K, int R, bool ALIGNED>
-__device__ __forceinline__ void apply_group(const ApplyArgs& a, const uint8_t* in_b, uint8_t* out_b,
-                                            cu32p in_ids, cu32p out_ids, cu32p tab, uint32_t nin,
-                                            uint32_t tab_row_stride, uint64_t chunk_off) {
+// VERIFY: the rows at out_b are the STORED rows and are only read; bit r of
+// the result is set when row r of the group differs in this lane's vector
+// (the encode form returns 0). The last vector of a shard goes through
+// load_tail for data and stored rows alike, which zero-fills from a.len on:
+// the recomputed parity of zero bytes is zero, so bytes at or past a.len
+// compare equal whatever the memory there holds.
+template <int K, int R, bool ALIGNED, bool VERIFY = false>
+__device__ __forceinline__ uint32_t apply_group(const ApplyArgs& a, const uint8_t* in_b, uint8_t* out_b,
+                                                cu32p in_ids, cu32p out_ids, cu32p tab, uint32_t nin,
+                                                uint32_t tab_row_stride, uint64_t chunk_off) {
     const uint64_t o = chunk_off + threadIdx.x * kVecBytes;
-    if (o >= a.len) return;
+    if (o >= a.len) return 0;
     const uint64_t avail = a.len - o;
     u32x4 acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = u32x4{0, 0, 0, 0};
+    uint32_t differs = 0;
     if (avail >= kVecBytes) {
         if constexpr (K > 0) {
             u32x4 d[K];
@@ -208,14 +219,63 @@ __device__ __forceinline__ void apply_group(const ApplyArgs& a, const uint8_t* i
             }
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) store_full(out_b + uint64_t(out_ids[r]) * a.out_shard + o, acc[r], ALIGNED);
+        for (int r = 0; r < R; ++r) {
+            uint8_t* row = out_b + uint64_t(out_ids[r]) * a.out_shard + o;
+            if constexpr (VERIFY) {
+                const u32x4 x = acc[r] ^ load_full(row, ALIGNED);
+                differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
+            } else {
+                store_full(row, acc[r], ALIGNED);
+            }
+        }
     } else {
         for (uint32_t i = 0; i < nin; ++i) {
             const u32x4 d = load_tail(in_b + uint64_t(in_ids[i]) * a.in_shard + o, avail);
             gf_mac<R>(acc, d, tab + i * tab_row_stride);
         }
-        for (int r = 0; r < R; ++r) store_tail(out_b + uint64_t(out_ids[r]) * a.out_shard + o, acc[r], avail);
+        for (int r = 0; r < R; ++r) {
+            uint8_t* row = out_b + uint64_t(out_ids[r]) * a.out_shard + o;
+            if constexpr (VERIFY) {
+                const u32x4 x = acc[r] ^ load_tail(row, avail);
+                differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
+            } else {
+                store_tail(row, acc[r], avail);
+            }
+        }
     }
+    return differs;
+}
+
+// The row groups of one plan over one (stripe, 4 KiB chunk) item: four output
+// rows at a time through apply_group, the last group with what is left.
+// Returns the lane's mismatch bits (bit j = output row j), 0 for the encode.
+template <int K, bool ALIGNED, bool VERIFY = false>
+__device__ __forceinline__ uint32_t apply_rows(const ApplyArgs& a, const uint8_t* in_b, uint8_t* out_b, cu32p in_ids,
+                                               cu32p out_ids, cu32p tab, const DevPlan& p, uint32_t row_stride,
+                                               uint64_t chunk_off) {
+    uint32_t differs = 0;
+    for (uint32_t g = 0; g < p.nout; g += 4) {
+        const uint32_t R = p.nout - g < 4 ? p.nout - g : 4;
+        cu32p tg = tab + g * 5;
+        uint32_t f;
+        switch (R) {
+            case 4: f = apply_group<K, 4, ALIGNED, VERIFY>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+            case 3: f = apply_group<K, 3, ALIGNED, VERIFY>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+            case 2: f = apply_group<K, 2, ALIGNED, VERIFY>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+            default: f = apply_group<K, 1, ALIGNED, VERIFY>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
+        }
+        if constexpr (VERIFY) differs |= f << g;
+    }
+    return differs;
+}
+
+// First item of a workgroup's grid-stride loop. XCD-aware chunk mapping:
+// workgroups b, b+8, b+16, ... are dealt to one XCD (MI355X_MICROARCH.md,
+// dispatch), so a bijective remap hands them consecutive chunks. Speed only:
+// correctness never depends on placement.
+__device__ __forceinline__ uint64_t stride_first_item() {
+    const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
 }
 
 // Completion signal of a launch for a host that spins on pinned memory
@@ -242,12 +302,7 @@ __device__ __forceinline__ void signal_done(uint32_t* count, uint32_t* flag, uin
 // ad-hoc host plans): grid-stride over (stripe, 4 KiB chunk) items.
 template <int K, bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void rs_apply_kernel(ApplyArgs a) {
-    // XCD-aware chunk mapping: workgroups b, b+8, b+16, ... are dealt to one
-    // XCD (MI355X_MICROARCH.md, dispatch), so a bijective remap hands them
-    // consecutive chunks. Speed only: correctness never depends on placement.
-    const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
-    const uint64_t first = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
-    for (uint64_t item = first; item < a.n_items; item += gridDim.x) {
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
         const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
         const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
         uint32_t pid = 0;
@@ -268,16 +323,7 @@ __global__ __launch_bounds__(kThreads) void rs_apply_kernel(ApplyArgs a) {
         cu32p tab = as_const(a.tabs) + p.tab_off;
         const uint32_t row_stride = p.tab_rows * 5;  // words per input
         const uint64_t chunk_off = uint64_t(chunk) * (kThreads * kVecBytes);
-        for (uint32_t g = 0; g < p.nout; g += 4) {
-            const uint32_t R = p.nout - g < 4 ? p.nout - g : 4;
-            cu32p tg = tab + g * 5;
-            switch (R) {
-                case 4: apply_group<K, 4, ALIGNED>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                case 3: apply_group<K, 3, ALIGNED>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                case 2: apply_group<K, 2, ALIGNED>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                default: apply_group<K, 1, ALIGNED>(a, in_b, out_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-            }
-        }
+        apply_rows<K, ALIGNED>(a, in_b, out_b, in_ids, out_ids, tab, p, row_stride, chunk_off);
     }
     if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
 }
@@ -508,18 +554,45 @@ __global__ __launch_bounds__(kThreads) void rs104_narrow_kernel(ApplyArgs a) {
 // the math hides at lower occupancy (170 VGPRs, 2 waves/SIMD).
 // ---------------------------------------------------------------------------
 // One 8 KiB column range (`chunk`) of one stripe: inputs 0..9 at in_b, parity
-// 0..3 at out_b.
-template <typename OffT = uint64_t>
-__device__ __forceinline__ void rs104_bs_chunk(const uint8_t* in_b, uint8_t* out_b, uint64_t in_shard,
-                                               uint64_t out_shard, uint32_t chunk) {
+// 0..3 at out_b. VERIFY: out_b holds the STORED parity, which is read and
+// compared instead of written; the result is the wave's mismatch bits (bit j =
+// parity row j differs somewhere in the wave's 2 KiB), 0 for the encode. The
+// parity loads are written with the data loads and left to the scheduler,
+// which issues them after the XOR program: 171 VGPRs, no scratch, 2 waves/SIMD
+// as the encode. Pinned up front with a sched_barrier (28 loads in flight, 196
+// VGPRs) it measured no different within the run-to-run spread
+// (profiles/verify/ab_parity_load_placement.jsonl).
+// out_off is added to out_b here. The verify hands over its stripe offset
+// this way: with the stripe's parity pointer formed in the caller's argument
+// list (the same IR but for the place of that one add) the backend schedules
+// the parity address math ahead of the data loads, a different instruction
+// stream that ran 9.21-9.50 ms against 8.81-8.95 in three alternating
+// processes each (profiles/verify/refactor_ab.jsonl, ab "by_pointer"; a second
+// session's process-to-process spread was as wide as that gap, so the timing
+// alone does not settle it). In this form the verify kernel's instructions are
+// those of the separate kernel it replaces, up to the operand order of
+// commutative ops (profiles/verify/refactor_isa.md). The encode callers pass
+// their pointer and no offset, as they always have.
+template <typename OffT = uint64_t, bool VERIFY = false>
+__device__ __forceinline__ uint32_t rs104_bs_chunk(const uint8_t* in_b, uint8_t* out_b, uint64_t in_shard,
+                                                   uint64_t out_shard, uint32_t chunk, uint64_t out_off = 0) {
     constexpr int K = 10, R = 4;
+    out_b += out_off;
     const OffT base = OffT(chunk) * OffT(kBsChunk) + OffT(threadIdx.x * 16);
     uint32_t p[K * 8];
     u32x4 d[K][2];
+    [[maybe_unused]] u32x4 s[R][2];
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         d[i][0] = load_at(in_b + uint64_t(i) * in_shard, base);
         d[i][1] = load_at(in_b + uint64_t(i) * in_shard, base + OffT(kThreads * 16));
+    }
+    if constexpr (VERIFY) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            s[j][0] = load_at(out_b + uint64_t(j) * out_shard, base);
+            s[j][1] = load_at(out_b + uint64_t(j) * out_shard, base + OffT(kThreads * 16));
+        }
     }
 #pragma unroll
     for (int i = 0; i < K; ++i)
@@ -532,13 +605,22 @@ __device__ __forceinline__ void rs104_bs_chunk(const uint8_t* in_b, uint8_t* out
     for (int i = 0; i < K; ++i) transpose8(p + 8 * i);
     uint32_t q[R * 8];
     rs104_encode_planes(p, q);
+    uint32_t bits = 0;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         transpose8(q + 8 * j);
-        store_at(out_b + uint64_t(j) * out_shard, base, u32x4{q[8 * j], q[8 * j + 1], q[8 * j + 2], q[8 * j + 3]});
-        store_at(out_b + uint64_t(j) * out_shard, base + OffT(kThreads * 16),
-                 u32x4{q[8 * j + 4], q[8 * j + 5], q[8 * j + 6], q[8 * j + 7]});
+        if constexpr (VERIFY) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) x |= (q[8 * j + w] ^ s[j][0][w]) | (q[8 * j + 4 + w] ^ s[j][1][w]);
+            bits |= (__ballot(x != 0) != 0 ? 1u : 0u) << j;
+        } else {
+            store_at(out_b + uint64_t(j) * out_shard, base, u32x4{q[8 * j], q[8 * j + 1], q[8 * j + 2], q[8 * j + 3]});
+            store_at(out_b + uint64_t(j) * out_shard, base + OffT(kThreads * 16),
+                     u32x4{q[8 * j + 4], q[8 * j + 5], q[8 * j + 6], q[8 * j + 7]});
+        }
     }
+    return bits;
 }
 
 template <typename OffT>
@@ -582,19 +664,25 @@ __global__ __launch_bounds__(kThreads) void rs104_bs_ragged_kernel(RaggedArgs a)
     if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
 }
 
-hipError_t launch_rs104_bs_ragged(const RaggedArgs& a, hipStream_t stream) {
-    for (uint64_t b0 = 0; b0 < a.n_blocks; b0 += kMaxLaunchBlocks) {  // see kMaxLaunchBlocks
+// A ragged batch through `kern`, in launches of at most kMaxLaunchBlocks
+// workgroups (launch_split.hpp).
+static hipError_t launch_ragged(void (*kern)(RaggedArgs), const RaggedArgs& a, hipStream_t stream) {
+    for (uint64_t i = 0, n = n_ranges(a.n_blocks, kMaxLaunchBlocks); i < n; ++i) {
+        const BlockLaunch l = block_launch(a.n_blocks, kMaxLaunchBlocks, i);
         RaggedArgs r = a;
-        r.block_base = uint32_t(b0);
-        if (b0 + kMaxLaunchBlocks < a.n_blocks) r.done_flag = nullptr;  // the last launch signals
-        const uint32_t nb = uint32_t(std::min<uint64_t>(kMaxLaunchBlocks, a.n_blocks - b0));
-        r.map_q8 = nb / 8;
-        r.map_r8 = nb % 8;
-        hipLaunchKernelGGL(rs104_bs_ragged_kernel, dim3(nb), dim3(kThreads), 0, stream, r);
+        r.block_base = l.block_base;
+        r.map_q8 = l.map_q8;
+        r.map_r8 = l.map_r8;
+        if (!l.last) r.done_flag = nullptr;  // the last launch signals
+        hipLaunchKernelGGL(kern, dim3(l.n_blocks), dim3(kThreads), 0, stream, r);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_rs104_bs_ragged(const RaggedArgs& a, hipStream_t stream) {
+    return launch_ragged(rs104_bs_ragged_kernel, a, stream);
 }
 
 // Ragged batches: every stripe has its own length, shard stride and mask
@@ -614,23 +702,8 @@ __global__ __launch_bounds__(kThreads) void rs104_ragged_kernel(RaggedArgs a) {
 }
 
 hipError_t launch_rs104_ragged(const RaggedArgs& a, bool decode, hipStream_t stream) {
-    for (uint64_t b0 = 0; b0 < a.n_blocks; b0 += kMaxLaunchBlocks) {  // see kMaxLaunchBlocks
-        RaggedArgs r = a;
-        r.block_base = uint32_t(b0);
-        if (b0 + kMaxLaunchBlocks < a.n_blocks) r.done_flag = nullptr;  // the last launch signals
-        const dim3 grid(uint32_t(std::min<uint64_t>(kMaxLaunchBlocks, a.n_blocks - b0)));
-        r.map_q8 = grid.x / 8;
-        r.map_r8 = grid.x % 8;
-        if (decode && a.compact)
-            hipLaunchKernelGGL((rs104_ragged_kernel<true, true>), grid, dim3(kThreads), 0, stream, r);
-        else if (decode)
-            hipLaunchKernelGGL((rs104_ragged_kernel<true, false>), grid, dim3(kThreads), 0, stream, r);
-        else
-            hipLaunchKernelGGL((rs104_ragged_kernel<false, false>), grid, dim3(kThreads), 0, stream, r);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    if (!decode) return launch_ragged(rs104_ragged_kernel<false, false>, a, stream);
+    return launch_ragged(a.compact ? rs104_ragged_kernel<true, true> : rs104_ragged_kernel<true, false>, a, stream);
 }
 
 // The kernel an aligned RS(10,4) batch with the fast plan layout runs, shared
@@ -686,48 +759,59 @@ static void set_fast_map(ApplyArgs& a, uint32_t chunk_bytes, bool round_up) {
     a.cps_shift = f.shift;
 }
 
-template <bool DEC>
-static hipError_t launch_rs104(ApplyArgs a, Rs104Kind kind, hipStream_t stream) {
-    const bool off32 = a.len <= 0xFFFFFFFFull;
-    switch (kind) {
-        case Rs104Kind::Bitslice:
-            set_fast_map(a, kBsChunk, false);
-            if (a.n_items == 0) return hipSuccess;
-            if (off32)
-                hipLaunchKernelGGL((rs104_bs_encode_kernel<uint32_t>), dim3(uint32_t(a.n_items)), dim3(kThreads), 0,
-                                   stream, a);
-            else
-                hipLaunchKernelGGL((rs104_bs_encode_kernel<uint64_t>), dim3(uint32_t(a.n_items)), dim3(kThreads), 0,
-                                   stream, a);
-            break;
-        case Rs104Kind::Narrow:
-            set_fast_map(a, kNarrowChunk, false);
-            if (a.n_items == 0) return hipSuccess;
-            hipLaunchKernelGGL((rs104_narrow_kernel<DEC>), dim3(uint32_t(a.n_items)), dim3(kThreads), 0, stream, a);
-            break;
-        default:
-            set_fast_map(a, kThreads * kVecBytes, true);
-            if (a.n_items == 0) return hipSuccess;
-            if (off32)
-                hipLaunchKernelGGL((rs104_kernel<DEC, uint32_t>), dim3(uint32_t(a.n_items)), dim3(kThreads), 0,
-                                   stream, a);
-            else
-                hipLaunchKernelGGL((rs104_kernel<DEC, uint64_t>), dim3(uint32_t(a.n_items)), dim3(kThreads), 0,
-                                   stream, a);
-            break;
-    }
+// The coding arguments of either kernel argument struct.
+static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
+static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
+
+// A fast-mapped batch (set_fast_map), one workgroup per item: k32 where every
+// byte offset inside a shard fits 32 bits, k64 for shards of 4 GiB and more.
+template <typename Args>
+static hipError_t launch_items(void (*k32)(Args), void (*k64)(Args), Args v, hipStream_t stream) {
+    const ApplyArgs& a = apply_args(v);
+    if (a.n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(a.len <= 0xFFFFFFFFull ? k32 : k64, dim3(uint32_t(a.n_items)), dim3(kThreads), 0, stream, v);
     return hipGetLastError();
 }
 
-template <int K, bool ALIGNED>
-static hipError_t launch_t(ApplyArgs a, hipStream_t stream) {
+template <bool DEC>
+static hipError_t launch_rs104(ApplyArgs a, Rs104Kind kind, hipStream_t stream) {
+    switch (kind) {
+        case Rs104Kind::Bitslice:
+            set_fast_map(a, kBsChunk, false);
+            return launch_items(rs104_bs_encode_kernel<uint32_t>, rs104_bs_encode_kernel<uint64_t>, a, stream);
+        case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
+            set_fast_map(a, kNarrowChunk, false);
+            return launch_items(rs104_narrow_kernel<DEC>, rs104_narrow_kernel<DEC>, a, stream);
+        default:
+            set_fast_map(a, kThreads * kVecBytes, true);
+            return launch_items(rs104_kernel<DEC, uint32_t>, rs104_kernel<DEC, uint64_t>, a, stream);
+    }
+}
+
+// A grid-stride kernel (rs_apply_kernel / rs_verify_kernel) over the batch's
+// (stripe, 4 KiB chunk) items.
+template <typename Args>
+static hipError_t launch_stride(void (*kern)(Args), Args v, hipStream_t stream) {
+    ApplyArgs& a = apply_args(v);
     const uint64_t chunk = uint64_t(kThreads) * kVecBytes;
     a.chunks_per_stripe = uint32_t((a.len + chunk - 1) / chunk);
     a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
     if (a.n_items == 0) return hipSuccess;
     const uint64_t grid = std::min<uint64_t>(a.n_items, kMaxLaunchBlocks);  // grid-stride covers the rest
-    hipLaunchKernelGGL((rs_apply_kernel<K, ALIGNED>), dim3(uint32_t(grid)), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(kern, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, v);
     return hipGetLastError();
+}
+
+// The arguments of one stripe range of a batch (launch_split.hpp): bases and
+// masks advanced to its first stripe. The launches share a stream, so only the
+// last range signals completion.
+static ApplyArgs stripe_range(ApplyArgs a, Range r) {
+    a.in_base += uint64_t(r.first) * a.in_stripe;
+    a.out_base += uint64_t(r.first) * a.out_stripe;
+    if (a.masks) a.masks += r.first;
+    a.n_stripes = r.count;
+    if (!r.last) a.done_flag = nullptr;
+    return a;
 }
 
 hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pcie, hipStream_t stream) {
@@ -738,15 +822,9 @@ hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pci
     const uint64_t per_stripe = (a.len + 4095) / 4096;
     const uint64_t items = per_stripe * a.n_stripes;
     if (a.fast104 && items > kMaxLaunchBlocks && a.n_stripes > 1 && per_stripe <= kMaxLaunchBlocks) {
-        const uint32_t step = uint32_t(kMaxLaunchBlocks / per_stripe);
-        for (uint32_t s0 = 0; s0 < a.n_stripes; s0 += step) {
-            ApplyArgs b = a;
-            b.n_stripes = std::min(step, a.n_stripes - s0);
-            if (s0 + step < a.n_stripes) b.done_flag = nullptr;  // same stream: the last launch signals
-            b.in_base += uint64_t(s0) * a.in_stripe;
-            b.out_base += uint64_t(s0) * a.out_stripe;
-            if (b.masks) b.masks += s0;
-            hipError_t e = launch_apply(b, nin, aligned, over_pcie, stream);
+        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
+        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
+            hipError_t e = launch_apply(stripe_range(a, range_at(a.n_stripes, step, i)), nin, aligned, over_pcie, stream);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -754,8 +832,8 @@ hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pci
     const Rs104Kind kind = rs104_pick(a.len, a.n_stripes, a.masks != nullptr, over_pcie && !a.masks);
     if (a.fast104 && aligned && kind != Rs104Kind::Apply)
         return a.masks ? launch_rs104<true>(a, kind, stream) : launch_rs104<false>(a, kind, stream);
-    if (nin == 10) return aligned ? launch_t<10, true>(a, stream) : launch_t<10, false>(a, stream);
-    return aligned ? launch_t<0, true>(a, stream) : launch_t<0, false>(a, stream);
+    if (nin == 10) return launch_stride(aligned ? rs_apply_kernel<10, true> : rs_apply_kernel<10, false>, a, stream);
+    return launch_stride(aligned ? rs_apply_kernel<0, true> : rs_apply_kernel<0, false>, a, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -776,117 +854,28 @@ __device__ __forceinline__ void report_mismatch(uint32_t* word, uint32_t* bad_co
     }
 }
 
-// Bit-sliced RS(10,4) verify: rs104_bs_chunk's loads and XOR program, plus the
-// four stored parity streams; the computed planes are transposed back and
-// compared with the stored bytes. One 8 KiB column range per workgroup, the
-// encode's workgroup -> (stripe, chunk) map. The parity loads are written with
-// the data loads and left to the scheduler, which issues them after the XOR
-// program: 171 VGPRs, no scratch, 2 waves/SIMD as the encode. Pinned up front
-// with a sched_barrier (28 loads in flight, 196 VGPRs) it measured no
-// different within the run-to-run spread (profiles/verify/
-// ab_parity_load_placement.jsonl).
+// Bit-sliced RS(10,4) verify: rs104_bs_chunk<OffT, VERIFY> (the encode's loads
+// and XOR program plus the four stored parity streams). One 8 KiB column range
+// per workgroup, the encode's workgroup -> (stripe, chunk) map.
 template <typename OffT>
 __global__ __launch_bounds__(kThreads) void rs104_bs_verify_kernel(VerifyArgs v) {
-    constexpr int K = 10, R = 4;
     const ApplyArgs& a = v.a;
     uint32_t stripe, chunk;
     fast_item(a, a.chunks_per_stripe, stripe, chunk);
-    const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
-    const uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
-    const OffT base = OffT(chunk) * OffT(kBsChunk) + OffT(threadIdx.x * 16);
-    uint32_t p[K * 8];
-    u32x4 d[K][2], s[R][2];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        d[i][0] = load_at(in_b + uint64_t(i) * a.in_shard, base);
-        d[i][1] = load_at(in_b + uint64_t(i) * a.in_shard, base + OffT(kThreads * 16));
-    }
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        s[j][0] = load_at(par_b + uint64_t(j) * a.out_shard, base);
-        s[j][1] = load_at(par_b + uint64_t(j) * a.out_shard, base + OffT(kThreads * 16));
-    }
-#pragma unroll
-    for (int i = 0; i < K; ++i)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            p[8 * i + w] = d[i][0][w];
-            p[8 * i + 4 + w] = d[i][1][w];
-        }
-#pragma unroll
-    for (int i = 0; i < K; ++i) transpose8(p + 8 * i);
-    uint32_t q[R * 8];
-    rs104_encode_planes(p, q);
-    uint32_t bits = 0;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        transpose8(q + 8 * j);
-        uint32_t x = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) x |= (q[8 * j + w] ^ s[j][0][w]) | (q[8 * j + 4 + w] ^ s[j][1][w]);
-        bits |= (__ballot(x != 0) != 0 ? 1u : 0u) << j;
-    }
+    const uint32_t bits =
+        rs104_bs_chunk<OffT, true>(a.in_base + uint64_t(stripe) * a.in_stripe, a.out_base, a.in_shard, a.out_shard,
+                                   chunk, uint64_t(stripe) * a.out_stripe);
     report_mismatch(v.mismatch + stripe, a.bad_count, bits);
-}
-
-// One group of R (<= 4) parity rows of the encode plan over one 16-byte
-// vector per lane, as apply_group, with the stores replaced by loads of the
-// stored rows: returns bit r set when row r of the group differs in this
-// lane's vector. The last vector of a shard goes through load_tail for data
-// and parity alike, which zero-fills from a.len on: the recomputed parity of
-// zero bytes is zero, so bytes at or past a.len compare equal whatever the
-// memory there holds.
-template <int K, int R, bool ALIGNED>
-__device__ __forceinline__ uint32_t verify_group(const ApplyArgs& a, const uint8_t* in_b, const uint8_t* par_b,
-                                                 cu32p in_ids, cu32p out_ids, cu32p tab, uint32_t nin,
-                                                 uint32_t tab_row_stride, uint64_t chunk_off) {
-    const uint64_t o = chunk_off + threadIdx.x * kVecBytes;
-    if (o >= a.len) return 0;
-    const uint64_t avail = a.len - o;
-    u32x4 acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = u32x4{0, 0, 0, 0};
-    uint32_t differs = 0;
-    if (avail >= kVecBytes) {
-        if constexpr (K > 0) {
-            u32x4 d[K];
-#pragma unroll
-            for (int i = 0; i < K; ++i) d[i] = load_full(in_b + uint64_t(in_ids[i]) * a.in_shard + o, ALIGNED);
-#pragma unroll
-            for (int i = 0; i < K; ++i) gf_mac<R>(acc, d[i], tab + i * tab_row_stride);
-        } else {
-            for (uint32_t i = 0; i < nin; ++i) {
-                const u32x4 d = load_full(in_b + uint64_t(in_ids[i]) * a.in_shard + o, ALIGNED);
-                gf_mac<R>(acc, d, tab + i * tab_row_stride);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const u32x4 x = acc[r] ^ load_full(par_b + uint64_t(out_ids[r]) * a.out_shard + o, ALIGNED);
-            differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
-        }
-    } else {
-        for (uint32_t i = 0; i < nin; ++i) {
-            const u32x4 d = load_tail(in_b + uint64_t(in_ids[i]) * a.in_shard + o, avail);
-            gf_mac<R>(acc, d, tab + i * tab_row_stride);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const u32x4 x = acc[r] ^ load_tail(par_b + uint64_t(out_ids[r]) * a.out_shard + o, avail);
-            differs |= ((x[0] | x[1] | x[2] | x[3]) != 0 ? 1u : 0u) << r;
-        }
-    }
-    return differs;
 }
 
 // Generic verify (any codec with at most 32 parity shards, unaligned bases and
 // strides, any length): rs_apply_kernel's grid-stride over (stripe, 4 KiB
-// chunk) items and its row groups, over the encode plan (plan 0).
+// chunk) items and its row groups (apply_rows<K, ALIGNED, VERIFY>), over the
+// encode plan (plan 0).
 template <int K, bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs v) {
     const ApplyArgs& a = v.a;
-    const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
-    const uint64_t first = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
+    const uint64_t first = stride_first_item();
     const __attribute__((address_space(4))) DevPlan* pp = as_const(a.plans);
     const DevPlan p{pp->nin, pp->nout, pp->tab_off, pp->idx_off, pp->tab_rows, {0, 0, 0}};
     cu32p in_ids = as_const(a.idx) + p.idx_off;
@@ -897,21 +886,11 @@ __global__ __launch_bounds__(kThreads) void rs_verify_kernel(VerifyArgs v) {
         const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
         const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
         const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
-        const uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+        uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;  // only read
         const uint64_t chunk_off = uint64_t(chunk) * (kThreads * kVecBytes);
-        uint32_t differs = 0;  // this lane: bit j = parity row j differs in its vector
-        for (uint32_t g = 0; g < p.nout; g += 4) {
-            const uint32_t R = p.nout - g < 4 ? p.nout - g : 4;
-            cu32p tg = tab + g * 5;
-            uint32_t f;
-            switch (R) {
-                case 4: f = verify_group<K, 4, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                case 3: f = verify_group<K, 3, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                case 2: f = verify_group<K, 2, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-                default: f = verify_group<K, 1, ALIGNED>(a, in_b, par_b, in_ids, out_ids + g, tg, p.nin, row_stride, chunk_off); break;
-            }
-            differs |= f << g;
-        }
+        // this lane: bit j = parity row j differs in its vector
+        const uint32_t differs =
+            apply_rows<K, ALIGNED, true>(a, in_b, par_b, in_ids, out_ids, tab, p, row_stride, chunk_off);
         uint32_t bits = 0;
         for (uint32_t j = 0; j < p.nout; ++j) bits |= (__ballot((differs >> j) & 1u) != 0 ? 1u : 0u) << j;
         report_mismatch(v.mismatch + stripe, a.bad_count, bits);
@@ -930,47 +909,24 @@ const char* verify_kernel_name(uint64_t len) {
     return verify_bitsliced(len) ? kBsVerifyName : kGenericVerifyName;
 }
 
-template <int K, bool ALIGNED>
-static hipError_t launch_verify_t(VerifyArgs v, hipStream_t stream) {
-    ApplyArgs& a = v.a;
-    const uint64_t chunk = uint64_t(kThreads) * kVecBytes;
-    a.chunks_per_stripe = uint32_t((a.len + chunk - 1) / chunk);
-    a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
-    if (a.n_items == 0) return hipSuccess;
-    const uint64_t grid = std::min<uint64_t>(a.n_items, kMaxLaunchBlocks);  // grid-stride covers the rest
-    hipLaunchKernelGGL((rs_verify_kernel<K, ALIGNED>), dim3(uint32_t(grid)), dim3(kThreads), 0, stream, v);
-    return hipGetLastError();
-}
-
 hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t stream) {
     const ApplyArgs& a = v.a;
     if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
     if (a.fast104 && aligned && verify_bitsliced(a.len)) {
         // one chunk per workgroup and no grid-stride loop: batches past one
         // launch's workgroup limit go in stripe ranges, as launch_apply's
-        const uint64_t per_stripe = a.len / kBsChunk;
-        const uint32_t step = uint32_t(std::min<uint64_t>(kMaxLaunchBlocks / per_stripe, a.n_stripes));
-        const bool off32 = a.len <= 0xFFFFFFFFull;
-        for (uint32_t s0 = 0; s0 < a.n_stripes; s0 += step) {
-            VerifyArgs b = v;
-            b.a.n_stripes = std::min(step, a.n_stripes - s0);
-            b.a.in_base += uint64_t(s0) * a.in_stripe;
-            b.a.out_base += uint64_t(s0) * a.out_stripe;
-            b.mismatch += s0;
+        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, a.len / kBsChunk);
+        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
+            const Range r = range_at(a.n_stripes, step, i);
+            VerifyArgs b{stripe_range(a, r), v.mismatch + r.first};
             set_fast_map(b.a, kBsChunk, false);
-            if (off32)
-                hipLaunchKernelGGL((rs104_bs_verify_kernel<uint32_t>), dim3(uint32_t(b.a.n_items)), dim3(kThreads), 0,
-                                   stream, b);
-            else
-                hipLaunchKernelGGL((rs104_bs_verify_kernel<uint64_t>), dim3(uint32_t(b.a.n_items)), dim3(kThreads), 0,
-                                   stream, b);
-            hipError_t e = hipGetLastError();
+            hipError_t e = launch_items(rs104_bs_verify_kernel<uint32_t>, rs104_bs_verify_kernel<uint64_t>, b, stream);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    if (nin == 10) return aligned ? launch_verify_t<10, true>(v, stream) : launch_verify_t<10, false>(v, stream);
-    return aligned ? launch_verify_t<0, true>(v, stream) : launch_verify_t<0, false>(v, stream);
+    if (nin == 10) return launch_stride(aligned ? rs_verify_kernel<10, true> : rs_verify_kernel<10, false>, v, stream);
+    return launch_stride(aligned ? rs_verify_kernel<0, true> : rs_verify_kernel<0, false>, v, stream);
 }
 
 // ---------------------------------------------------------------------------

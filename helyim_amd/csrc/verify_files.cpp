@@ -15,7 +15,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "hec_internal.hpp"
+#include "file_util.hpp"
 
 namespace hec {
 namespace {
@@ -23,13 +23,6 @@ namespace {
 constexpr int K = 10, M = 4, N = 14;
 constexpr uint64_t kChunkCols = 4ull << 20;  // target bytes per shard of one chunk (14 x that per slot)
 constexpr uint64_t kReadPiece = 1ull << 20;  // bytes of one pread task
-
-struct Fd {
-    int fd = -1;
-    ~Fd() {
-        if (fd >= 0) ::close(fd);
-    }
-};
 
 // One slot of the per-device pool of scrubs (SlotPool): its stream, the two
 // pinned chunk slots and the result words of each.
@@ -62,32 +55,14 @@ struct Scrub {
     }
 };
 
-std::string shard_name(const std::string& base, int i) {
-    char ext[8];
-    std::snprintf(ext, sizeof ext, ".ec%02d", i);
-    return base + ext;
-}
-
 // n bytes of fd at off into dst; a file that ends early is a short read
 // (HEC_ERR_IO without an OS error).
 void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, uint64_t n, uint64_t off) {
-    while (n > 0) {
-        const ssize_t r = ::pread(fd, dst, n, off_t(off));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            ErrorValues v;
-            v.os_errno = errno;
-            err.set(HEC_ERR_IO, "read " + name + ": " + std::strerror(errno), v);
-            return;
-        }
-        if (r == 0) {
-            err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off));
-            return;
-        }
-        dst += r;
-        off += uint64_t(r);
-        n -= uint64_t(r);
-    }
+    const ssize_t got = pread_full(fd, dst, n, off);
+    if (got < 0)
+        io_error(err, "read " + name);
+    else if (uint64_t(got) < n)  // the offset where the file ended
+        err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off + uint64_t(got)));
 }
 
 int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
@@ -116,10 +91,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad*
     }
     if (size == 0) return HEC_OK;
 
-    struct Rs {
-        hec_rs_t* rs = nullptr;
-        ~Rs() { hec_rs_free(rs); }
-    } codec;
+    RsGuard codec;
     HEC_TRY(hec_rs_new(K, M, &codec.rs));
     GeomDevice* gd;
     HEC_TRY(geom_device(codec.rs, &gd));

@@ -119,7 +119,8 @@ def main(argv=None):
                 "ms_max": round(float(np.max(v)), 4), "ms_rounds": [round(float(x), 4) for x in v]}
     a_med = float(np.median(times["a"]))
     result = {
-        "tool": "tools/bench_verify.py", "version": H.version(), "device": torch.cuda.get_device_name(0),
+        "tool": "tools/bench_verify.py", "lib": os.path.basename(H.LIB_PATH), "version": H.version(),
+        "device": torch.cuda.get_device_name(0),
         "stripes": S, "shard_len": L, "shard_pad": args.shard_pad, "rounds": args.rounds,
         "kernel": B.verify_kernel_name(L),
         "verify": dict(stats(times["a"]), GiBps_14_shards_read=round(nbytes / (a_med * 1e-3) / 2**30, 1),
