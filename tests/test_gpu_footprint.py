@@ -184,7 +184,7 @@ def test_device_reconstruct_footprint(gpu, L, kernel):
             check_gpu_reconstruct(rs, 10, 4, rng, *case)
 
 
-@pytest.mark.parametrize("k,m", [(3, 2), (12, 4)])
+@pytest.mark.parametrize("k,m", [(3, 2), (12, 4), (10, 6)])
 @pytest.mark.parametrize("L", [17, 4096 + 3])
 def test_device_footprint_other_geometries(gpu, k, m, L):
     """The same two calls on geometries the generic plan interpreter runs."""

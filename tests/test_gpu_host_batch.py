@@ -130,7 +130,8 @@ def test_mixed_workload_lengths(gpu):
         assert np.array_equal(good.numpy()[:, 10:], ref)
 
 
-@pytest.mark.parametrize("k,m,pin", [(3, 2, True), (6, 3, False), (12, 4, True), (8, 8, False)])
+@pytest.mark.parametrize("k,m,pin", [(3, 2, True), (6, 3, False), (12, 4, True), (8, 8, False), (10, 2, True),
+                                     (10, 6, False)])
 def test_host_batches_generic_geometry(gpu, k, m, pin):
     """Host batches on geometries other than RS(10,4) (pinned: zero copy or
     pipeline; pageable: pooled staging), seeded per-stripe erasures, against

@@ -179,11 +179,13 @@ def test_bad_stripes_counts_a_stripe_exactly_once(gpu, which):
     assert words == want and bad == 9, (name, words, bad)
 
 
-@pytest.mark.parametrize("k,m", [(5, 5), (3, 2), (17, 3), (4, 32)])
+@pytest.mark.parametrize("k,m", [(5, 5), (3, 2), (17, 3), (4, 32), (10, 2), (10, 6)])
 @pytest.mark.parametrize("L", [4096, 100])
 def test_other_codecs_take_the_generic_kernel(gpu, k, m, L):
     """Clean, then one flip per parity shard (stripe j: parity shard j; the
-    last stripe stays clean)."""
+    last stripe stays clean). RS(10,2) and RS(10,6) run rs_verify_kernel<10>
+    with 2 and 6 table rows; for RS(10,6) also parity shards 4 and 5 of one
+    stripe, the bits of the second row group."""
     import helyim_amd as H
     rs = H.ReedSolomon(k, m)
     S = m + 1
@@ -198,6 +200,68 @@ def test_other_codecs_take_the_generic_kernel(gpu, k, m, L):
         assert want == [1 << j for j in range(m)] + [0]
         words, bad = device_verify(rs, work, stripes, data, par)
         assert words == want and bad == 7 + m, (name, [hex(w) for w in words])
+        if (k, m) == (10, 6):
+            work = copies(arenas)
+            shard_of(work, stripes, 2, k + 4)[L - 1] ^= 0x04
+            shard_of(work, stripes, 2, k + 5)[0] ^= 0x40
+            want = oracle_words(work, stripes, k, m)
+            assert want == [0, 0, 0b110000] + [0] * (S - 3)
+            words, bad = device_verify(rs, work, stripes, data, par)
+            assert words == want and bad == 7 + 1, (name, [hex(w) for w in words])
+
+
+@pytest.mark.parametrize("L", [(1 << 32) - 8192, (1 << 32) + 8192, (1 << 32) + 4096 + 16])
+def test_verify_shard_len_near_4gib(gpu, L):
+    """Two-stripe verifies (112 GiB in HBM) at the edge of the 32-bit lane
+    offsets: 2^32 - 8 KiB runs the bit-sliced verify with 32-bit offsets up to
+    its last chunk, 2^32 + 8 KiB rs104_bs_verify_kernel<uint64_t>, 2^32 + 4 KiB
+    + 16 rs_verify_kernel<10, true> with chunk offsets above 2^32 and a
+    16-byte last chunk. The stored parity is encode_batch's, checked against
+    the C oracle on the first and last 64 KiB of every shard; every flipped
+    bit lies in one of those windows. A wrapped offset would compare other
+    bytes: a clean word, or the wrong bit."""
+    import torch
+    import helyim_amd as H
+    import helyim_amd.batch as B
+    rs = H.ReedSolomon(10, 4)
+    S, W = 2, 1 << 16
+    name = H.lib.hec_verify_kernel_name(L).decode()
+    assert name.startswith("rs104_bs_verify_kernel" if L % 8192 == 0 else "rs_verify_kernel<10>"), name
+    torch.cuda.empty_cache()
+    t = torch.empty((S, 14, L), dtype=torch.uint8, device="cuda")
+    B.fill_splitmix(t, 10 * L, 0x5EED6000)
+    t[:, 10:].zero_()
+    B.encode_batch(rs, t)
+    torch.cuda.synchronize()
+    for s in range(S):
+        for lo in (0, L - W):
+            c = t[s, :, lo:lo + W].cpu().numpy()
+            assert np.array_equal(c[10:], corc.encode_stripes(np.ascontiguousarray(c[None, :10]))[0]), (L, s, lo)
+    words = torch.full((S,), -1, dtype=torch.int32, device="cuda")
+    bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+
+    def verify():
+        words.fill_(-1)
+        H.verify_batch(rs, t, mismatch=words, bad_stripes=bad)
+        torch.cuda.synchronize()
+        return words.cpu().tolist(), int(bad.item())
+
+    assert verify() == ([0, 0], 7)
+    flips = [(0, 11, 0), (1, 13, L - 1)] + [(1, 10, o) for o in ((1 << 32) - 1, (1 << 32) + 5) if o < L]
+    assert all(o < W or o >= L - W for _, _, o in flips)
+    for s, i, o in flips:
+        t[s, i, o] ^= 0x08
+    assert verify() == ([0b0010, 0b1001 if len(flips) > 2 else 0b1000], 9)
+    for s, i, o in flips:
+        t[s, i, o] ^= 0x08
+    t[0, 9, L - 1] ^= 0x01
+    c = t[0, :, L - W:].cpu().numpy()
+    ref = corc.encode_stripes(np.ascontiguousarray(c[None, :10]))[0]
+    want = sum(1 << j for j in range(4) if (ref[j] != c[10 + j]).any())
+    assert want != 0
+    assert verify() == ([want, 0], 10)
+    del t
+    torch.cuda.empty_cache()
 
 
 def test_more_than_32_parity_shards_is_refused(gpu):
