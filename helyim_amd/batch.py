@@ -83,20 +83,29 @@ def reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: tor
                                         _stream_ptr(stream)))
 
 
+def _words_arg(S: int, t: torch.Tensor, name: str) -> torch.Tensor:
+    """A per-stripe result tensor (mismatch, suspects, present_masks): allocated when not given."""
+    if t is None:
+        t = torch.empty(S, dtype=torch.int32, device="cuda")
+    elif not (t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.is_contiguous() and t.numel() >= S):
+        raise ValueError(f"{name} must be a contiguous 32-bit CUDA tensor with at least one word per stripe")
+    _check_device(t)
+    return t
+
+
+def _counter_arg(t: torch.Tensor, name: str):
+    """An optional accumulated device word (bad_stripes, unrepaired) -> its pointer or None."""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.numel() >= 1):
+        raise ValueError(f"{name} must be a 32-bit CUDA tensor")
+    _check_device(t)
+    return t.data_ptr()
+
+
 def _verify_args(S: int, mismatch: torch.Tensor, bad_stripes: torch.Tensor):
     """Result tensors of a device verify -> (mismatch, bad_stripes pointer)."""
-    if mismatch is None:
-        mismatch = torch.empty(S, dtype=torch.int32, device="cuda")
-    elif not (mismatch.is_cuda and mismatch.dtype in (torch.int32, torch.uint32) and mismatch.is_contiguous()
-              and mismatch.numel() >= S):
-        raise ValueError("mismatch must be a contiguous 32-bit CUDA tensor with at least one word per stripe")
-    _check_device(mismatch)
-    if bad_stripes is not None:
-        if not (bad_stripes.is_cuda and bad_stripes.dtype in (torch.int32, torch.uint32)
-                and bad_stripes.numel() >= 1):
-            raise ValueError("bad_stripes must be a 32-bit CUDA tensor")
-        _check_device(bad_stripes)
-    return mismatch, (bad_stripes.data_ptr() if bad_stripes is not None else None)
+    return _words_arg(S, mismatch, "mismatch"), _counter_arg(bad_stripes, "bad_stripes")
 
 
 def verify_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
@@ -131,6 +140,68 @@ def verify_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, 
                                    parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
                                    mismatch.data_ptr(), bad, _stream_ptr(stream)))
     return mismatch
+
+
+def locate_corrupt_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                         suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, stream=None):
+    """verify_batch that also names the corrupt shard (hec_gpu_locate_corrupt_batch,
+    RS(10,4) only). Returns ``(mismatch, suspects)``, int32 ``[S]`` tensors
+    (allocated when not given): mismatch as verify_batch's; bit c of
+    suspects[s] set = shard c alone explains a byte column of stripe s (data
+    shards 0..9, parity shard j at bit 10 + j), ``helyim_amd.SUSPECT_UNEXPLAINED`` (bit
+    31) = a column no single shard explains; 0 = clean. With at most 3 wrong
+    shards in a column no intact shard is ever named. Nothing else is written.
+    Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    k = rs.data_shard_count()
+    S, n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    check(lib.hec_gpu_locate_corrupt_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(),
+                                           suspects.data_ptr(), bad, _stream_ptr(stream)))
+    return mismatch, suspects
+
+
+def locate_corrupt_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
+                             mismatch: torch.Tensor = None, suspects: torch.Tensor = None,
+                             bad_stripes: torch.Tensor = None, stream=None):
+    """locate_corrupt_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
+    _check_stripes(data, rs, rs.data_shard_count())
+    _check_stripes(parity, rs, rs.parity_shard_count())
+    S, k, L = data.shape
+    if parity.shape[0] != S or parity.shape[2] != L:
+        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    check(lib.hec_gpu_locate_corrupt_batch(rs.handle, data.data_ptr(), data.stride(0), data.stride(1),
+                                           parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
+                                           mismatch.data_ptr(), suspects.data_ptr(), bad, _stream_ptr(stream)))
+    return mismatch, suspects
+
+
+def repair_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                 suspects: torch.Tensor = None, present_masks: torch.Tensor = None,
+                 unrepaired: torch.Tensor = None, stream=None):
+    """Locate, then rebuild in place the shards locate names (hec_gpu_repair_batch,
+    RS(10,4) only). Returns ``(mismatch, suspects, present_masks)``, int32
+    ``[S]`` tensors (allocated when not given): a stripe whose suspects word
+    names 1 to 4 shards with bit 31 clear has them rebuilt from the others
+    (present mask ``0x3FFF & ~suspects``); any other stripe is left byte for
+    byte (mask ``0x3FFF``) and, when its word is non-zero, counted into
+    unrepaired (32-bit CUDA word, accumulated). Run verify_batch afterwards
+    for proof. Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    mismatch = _words_arg(S, mismatch, "mismatch")
+    left = _counter_arg(unrepaired, "unrepaired")
+    suspects = _words_arg(S, suspects, "suspects")
+    present_masks = _words_arg(S, present_masks, "present_masks")
+    check(lib.hec_gpu_repair_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S,
+                                   mismatch.data_ptr(), suspects.data_ptr(), present_masks.data_ptr(), left,
+                                   _stream_ptr(stream)))
+    return mismatch, suspects, present_masks
 
 
 def verify_kernel_name(L: int) -> str:

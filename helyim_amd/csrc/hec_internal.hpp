@@ -219,6 +219,9 @@ struct GeomDevice {
     DevicePlanSet encode;        // plan 0 = encode
     DevicePlanSet decode_dense;  // LUT over all 2^n present masks (n <= 16)
     bool decode_ready = false;
+    // RS(10,4) only: the locate kernel's ratio constants as one 3 x 10 plan,
+    // row j - 1, input c = P[j][c] / P[0][c] (P = the parity rows; run_locate)
+    DevicePlanSet locate;
 };
 int geom_device(const hec_rs* rs, GeomDevice** out);
 int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s);
@@ -433,6 +436,22 @@ inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
     if (!mismatch) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     if (rs->m > 32)
         return fail(HEC_ERR_INVALID_ARGUMENT, "verify needs at most 32 parity shards (one result bit each)");
+    return HEC_OK;
+}
+
+// Locate, asynchronously on s with no host synchronisation and no allocation:
+// run_verify over gd's encode plan (mismatch[], bad: exactly its contract),
+// then suspects[0, n_stripes) are cleared on s and the locate kernel reads the
+// flagged stripes again (rs_kernels.hpp launch_locate; the result contract is
+// hec.h's). gd: the RS(10,4) geometry (the caller checks the codec).
+int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
+               const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
+               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s);
+// The locate entry points' extra argument checks, after check_verify_args.
+inline int check_locate_args(const hec_rs* rs, const void* suspects) {
+    if (!suspects) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (rs->k != 10 || rs->m != 4)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "locate and repair are RS(10,4) only");
     return HEC_OK;
 }
 

@@ -143,6 +143,19 @@ int geom_device(const hec_rs* rs, GeomDevice** out) {
     hp.add(par, in_ids, out_ids);
     if ((rc = gd->encode.upload(hp, nullptr, nullptr))) return rc;
     gd->encode.fast104 = is104;
+    if (is104) {
+        // the locate kernel's constants: P[j][c] / P[0][c] for j = 1..3 (a
+        // syndrome v * P[:,c] has s[j] = s[0] times that ratio)
+        const Gf& g = gf();
+        Mat ratio(rs->m - 1, rs->k);
+        for (int c = 0; c < rs->k; ++c) {
+            if (par.at(0, c) == 0) return fail(HEC_ERR_INVALID_ARGUMENT, "zero entry in the parity matrix");
+            for (int j = 1; j < rs->m; ++j) ratio.at(j - 1, c) = g.mul[par.at(j, c)][g.inv(par.at(0, c))];
+        }
+        HostPlans rp;
+        rp.add(ratio, in_ids, {1, 2, 3});
+        if ((rc = gd->locate.upload(rp, nullptr, nullptr))) return rc;
+    }
     *out = gd.get();
     g_geom[key] = std::move(gd);
     return HEC_OK;
@@ -221,17 +234,45 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
     return HEC_OK;
 }
 
+// The arguments of a verify or locate launch over ps's encode plan; returns
+// fill_args' alignment.
+static bool fill_verify_args(VerifyArgs& v, const DevicePlanSet& ps, const uint8_t* data, uint64_t data_stripe,
+                             uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe,
+                             uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
+                             uint32_t* bad) {
+    v.mismatch = mismatch;
+    return fill_args(v.a, ps, data, data_stripe, data_shard, const_cast<uint8_t*>(parity) /* only read */,
+                     parity_stripe, parity_shard, len, n_stripes, bad);
+}
+
 int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint64_t data_stripe,
                uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len,
                uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s) {
     if (n_stripes == 0) return HEC_OK;
     VerifyArgs v{};
-    v.mismatch = mismatch;
-    const bool aligned = fill_args(v.a, ps, data, data_stripe, data_shard, const_cast<uint8_t*>(parity) /* only read */,
-                                   parity_stripe, parity_shard, len, n_stripes, bad);
+    const bool aligned = fill_verify_args(v, ps, data, data_stripe, data_shard, parity, parity_stripe, parity_shard,
+                                          len, n_stripes, mismatch, bad);
     // the kernels only ever OR bits in: stale words must not leak through
     HEC_HIP(hipMemsetAsync(mismatch, 0, size_t(n_stripes) * 4, s));
     HEC_HIP(launch_verify(v, int(nin), aligned, s));
+    return HEC_OK;
+}
+
+int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
+               const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
+               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s) {
+    if (n_stripes == 0) return HEC_OK;
+    // pass 1: the scrub itself (bit-sliced where it applies), at its own rate
+    HEC_TRY(run_verify(gd.encode, 10, data, data_stripe, data_shard, parity, parity_stripe, parity_shard, len,
+                       n_stripes, mismatch, bad, s));
+    // pass 2: only the stripes pass 1 flagged are read again (bad is pass 1's)
+    VerifyArgs v{};
+    const bool aligned = fill_verify_args(v, gd.encode, data, data_stripe, data_shard, parity, parity_stripe,
+                                          parity_shard, len, n_stripes, mismatch, nullptr);
+    v.suspects = suspects;
+    v.ratio_tabs = gd.locate.tabs;
+    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_locate(v, aligned, s));
     return HEC_OK;
 }
 

@@ -24,6 +24,9 @@
 //  * The parity verify (scrub) kernels have no coding body of their own:
 //    rs104_bs_chunk and apply_group take a compile-time VERIFY flag that
 //    turns their stores into a compare with the stored rows.
+//  * The locate kernel (rs104_locate_kernel) is the scrub's second pass: it
+//    reads only the stripes the verify flagged and names the wrong shard of
+//    each byte column from its syndrome.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -788,16 +791,17 @@ static hipError_t launch_rs104(ApplyArgs a, Rs104Kind kind, hipStream_t stream) 
     }
 }
 
-// A grid-stride kernel (rs_apply_kernel / rs_verify_kernel) over the batch's
-// (stripe, 4 KiB chunk) items.
+// A grid-stride kernel (rs_apply_kernel / rs_verify_kernel / rs104_locate_kernel)
+// over the batch's (stripe, 4 KiB chunk) items, on at most max_grid workgroups.
 template <typename Args>
-static hipError_t launch_stride(void (*kern)(Args), Args v, hipStream_t stream) {
+static hipError_t launch_stride(void (*kern)(Args), Args v, hipStream_t stream,
+                                uint64_t max_grid = kMaxLaunchBlocks) {
     ApplyArgs& a = apply_args(v);
     const uint64_t chunk = uint64_t(kThreads) * kVecBytes;
     a.chunks_per_stripe = uint32_t((a.len + chunk - 1) / chunk);
     a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
     if (a.n_items == 0) return hipSuccess;
-    const uint64_t grid = std::min<uint64_t>(a.n_items, kMaxLaunchBlocks);  // grid-stride covers the rest
+    const uint64_t grid = std::min<uint64_t>(a.n_items, max_grid);  // grid-stride covers the rest
     hipLaunchKernelGGL(kern, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, v);
     return hipGetLastError();
 }
@@ -927,6 +931,155 @@ hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t
     }
     if (nin == 10) return launch_stride(aligned ? rs_verify_kernel<10, true> : rs_verify_kernel<10, false>, v, stream);
     return launch_stride(aligned ? rs_verify_kernel<0, true> : rs_verify_kernel<0, false>, v, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Locate (RS(10,4)): which shard of a flagged stripe is wrong. Pass 2 of the
+// scrub; pass 1 (launch_verify, above) has filled mismatch[]. With H = [P | I4]
+// (P the 4 x 10 parity rows), the syndrome of a byte column -- stored parity
+// XOR parity of the stored data, s[0..3] -- is v * H[:,c] when shard c alone
+// is wrong by v. Any four columns of H are independent (the code is MDS), so
+// one wrong shard is named uniquely and two or three wrong shards in a column
+// look like no single shard (DESIGN.md §4 "Locate"). Bytewise in SWAR:
+//  * exactly one s[j] non-zero -> parity shard 10 + j (column 10 + j of H is
+//    the unit vector e_j);
+//  * all four non-zero -> data shard c when s[j] = s[0] * P[j][c] / P[0][c]
+//    for j = 1..3: gf_mac<3> of s[0] over the three ratio constants of c (every
+//    entry of P is non-zero; the ratios are a plan like any other);
+//  * any other non-zero pattern, and an all-four byte no c matches, is
+//    unexplained (bit 31).
+// A clean item of a flagged stripe ends at one ballot; an item of a clean
+// stripe at one scalar load, without touching a shard.
+// ---------------------------------------------------------------------------
+// 0x80 in every non-zero byte of x.
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) {
+    return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
+    constexpr int K = 10, R = 4;
+    const ApplyArgs& a = v.a;
+    cu32p tab = as_const(a.tabs);        // encode plan: [K][R][5] words
+    cu32p rat = as_const(v.ratio_tabs);  // [K][R - 1][5] words
+    cu32p flagged = as_const(v.mismatch);
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        if (flagged[stripe] == 0) continue;  // pass 1 found the stripe clean
+        const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        const uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+        const uint64_t o = uint64_t(chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;
+        // the syndrome of this lane's 16 columns; lanes past the shard's end
+        // keep zeros and still take part in the ballots
+        u32x4 s[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) s[j] = u32x4{0, 0, 0, 0};
+        if (o < a.len) {
+            const uint64_t avail = a.len - o;
+            if (avail >= kVecBytes) {
+                u32x4 d[K];
+#pragma unroll
+                for (int i = 0; i < K; ++i) d[i] = load_full(in_b + uint64_t(i) * a.in_shard + o, ALIGNED);
+#pragma unroll
+                for (int i = 0; i < K; ++i) gf_mac<R>(s, d[i], tab + i * (R * 5));
+#pragma unroll
+                for (int j = 0; j < R; ++j) s[j] ^= load_full(par_b + uint64_t(j) * a.out_shard + o, ALIGNED);
+            } else {
+                // the last vector of a shard: zero-filled from a.len on, data
+                // and stored parity alike, so those columns have syndrome 0
+                for (int i = 0; i < K; ++i)
+                    gf_mac<R>(s, load_tail(in_b + uint64_t(i) * a.in_shard + o, avail), tab + i * (R * 5));
+                for (int j = 0; j < R; ++j) s[j] ^= load_tail(par_b + uint64_t(j) * a.out_shard + o, avail);
+            }
+        }
+        uint32_t any = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) any |= s[j][0] | s[j][1] | s[j][2] | s[j][3];
+        if (__ballot(any != 0) == 0) continue;  // wave-uniform: this wave's 1 KiB is clean
+
+        uint32_t one[R] = {0, 0, 0, 0};  // bytes where only s[j] is non-zero
+        uint32_t all4[4];                // per dword: bytes where all four are
+        uint32_t unexplained = 0, all_any = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t n0 = nz_bytes(s[0][w]), n1 = nz_bytes(s[1][w]), n2 = nz_bytes(s[2][w]),
+                           n3 = nz_bytes(s[3][w]);
+            const uint32_t o0 = n0 & ~(n1 | n2 | n3), o1 = n1 & ~(n0 | n2 | n3), o2 = n2 & ~(n0 | n1 | n3),
+                           o3 = n3 & ~(n0 | n1 | n2);
+            one[0] |= o0;
+            one[1] |= o1;
+            one[2] |= o2;
+            one[3] |= o3;
+            all4[w] = n0 & n1 & n2 & n3;
+            all_any |= all4[w];
+            unexplained |= (n0 | n1 | n2 | n3) & ~all4[w] & ~(o0 | o1 | o2 | o3);  // two or three non-zero
+        }
+        uint32_t bits = 0;
+        if (__ballot(all_any != 0) != 0) {  // wave-uniform: some column may name a data shard
+            uint32_t matched[4] = {0, 0, 0, 0};
+#pragma unroll 1
+            for (int c = 0; c < K; ++c) {
+                u32x4 e[R - 1];
+#pragma unroll
+                for (int j = 0; j < R - 1; ++j) e[j] = u32x4{0, 0, 0, 0};
+                gf_mac<R - 1>(e, s[0], rat + c * ((R - 1) * 5));
+                uint32_t hit = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const uint32_t diff = (e[0][w] ^ s[1][w]) | (e[1][w] ^ s[2][w]) | (e[2][w] ^ s[3][w]);
+                    const uint32_t m = all4[w] & ~nz_bytes(diff);
+                    matched[w] |= m;
+                    hit |= m;
+                }
+                bits |= (__ballot(hit != 0) != 0 ? 1u : 0u) << c;
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) unexplained |= all4[w] & ~matched[w];
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) bits |= (__ballot(one[j] != 0) != 0 ? 1u : 0u) << (K + j);
+        if (__ballot(unexplained != 0) != 0) bits |= kSuspectUnexplained;
+        if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+    }
+}
+
+hipError_t launch_locate(const VerifyArgs& v, bool aligned, hipStream_t stream) {
+    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
+    return launch_stride(aligned ? rs104_locate_kernel<true> : rs104_locate_kernel<false>, v, stream,
+                         kLocateMaxBlocks);
+}
+
+// Present masks of a repair, one lane per stripe; a wave counts the stripes it
+// leaves alone with one atomic.
+__global__ __launch_bounds__(kThreads) void repair_masks_kernel(const uint32_t* suspects, uint32_t* masks,
+                                                                uint32_t* unrepaired, uint32_t n_stripes) {
+    constexpr uint32_t kAll = (1u << 14) - 1;
+    // whole waves run every round, so the ballot below sees all 64 lanes
+    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
+    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
+        bool left = false;
+        if (s < n_stripes) {
+            const uint32_t w = suspects[s];
+            const uint32_t named = uint32_t(__builtin_popcount(w & kAll));
+            const bool repair = (w & kSuspectUnexplained) == 0 && named >= 1 && named <= 4;
+            masks[s] = repair ? (kAll & ~w) : kAll;
+            left = w != 0 && !repair;
+        }
+        const unsigned long long b = __ballot(left);
+        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
+    }
+}
+
+hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32_t* unrepaired, uint32_t n_stripes,
+                               hipStream_t stream) {
+    if (n_stripes == 0) return hipSuccess;
+    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
+    hipLaunchKernelGGL(repair_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, suspects, masks, unrepaired,
+                       n_stripes);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

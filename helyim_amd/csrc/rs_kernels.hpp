@@ -127,10 +127,34 @@ const char* decode_kernel_name(uint64_t len);
 struct VerifyArgs {
     ApplyArgs a;
     uint32_t* mismatch;
+    // launch_locate only (the verify kernels never read these):
+    uint32_t* suspects = nullptr;          // one word per stripe, zero at launch
+    const uint32_t* ratio_tabs = nullptr;  // [10 data shards][3][kTabWords]: P[j][c] / P[0][c], j = 1..3
 };
 // a.len is the TRUE shard length: bytes at or past it take no part (a length
 // rounded up for a pitch would compare pad bytes).
 hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t stream);
+
+// Locate (pass 2 of the RS(10,4) scrub, after launch_verify on the same
+// stream filled v.mismatch): for every stripe with a non-zero mismatch word,
+// the syndrome (stored parity XOR parity of the stored data) of each byte
+// column is classified and the result ORed into v.suspects[stripe] (hec.h,
+// hec_gpu_locate_corrupt_batch: bit c = shard c alone explains a column, bit
+// 31 = a column no single shard explains). v.a: the RS(10,4) encode plan's
+// arguments as for launch_verify; stripes whose mismatch word is 0 are not
+// read. A grid-stride kernel over (stripe, 4 KiB chunk) items on at most
+// kLocateMaxBlocks workgroups (a memory-bound grid-stride loop wants a few
+// workgroups per CU, not one per item; speed only, unmeasured).
+constexpr uint32_t kLocateMaxBlocks = 2048;
+constexpr uint32_t kSuspectUnexplained = 0x80000000u;  // hec.h HEC_SUSPECT_UNEXPLAINED
+hipError_t launch_locate(const VerifyArgs& v, bool aligned, hipStream_t stream);
+
+// Present masks of a repair from the suspects words (hec_gpu_repair_batch):
+// masks[s] = 0x3FFF & ~suspects[s] when the word names 1 to 4 shards and bit
+// 31 is clear, else 0x3FFF (the reconstruct's no-op); *unrepaired (optional)
+// += stripes with a non-zero word that are left alone.
+hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32_t* unrepaired, uint32_t n_stripes,
+                               hipStream_t stream);
 // Name of the kernel an aligned RS(10,4) device verify of this shard length runs.
 const char* verify_kernel_name(uint64_t len);
 

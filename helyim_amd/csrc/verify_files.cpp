@@ -1,4 +1,6 @@
-// Scrub of a volume's shard files base.ec00 .. base.ec13 (hec_verify_ec_files).
+// Scrub of a volume's shard files base.ec00 .. base.ec13 (hec_verify_ec_files,
+// and hec_locate_corrupt_ec_files: the same walk with the locate pass, which
+// also names the wrong shard file of each bad block).
 //
 // RS parity is bytewise: byte o of every parity file is a function of byte o
 // of the ten data files, whatever large / small block geometry laid the .dat
@@ -65,8 +67,11 @@ void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, u
         err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off + uint64_t(got)));
 }
 
-int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
-                         uint64_t* n_blocks) {
+// locate: every launch is run_locate instead of run_verify, a chunk's suspects
+// words follow its mismatch words at +per_chunk in the same result buffers,
+// and the bad blocks go to sus[] with their suspects word instead of to bad[].
+int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, hec_scrub_bad* bad,
+                         hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks) {
     // files and sizes first: these failures need no device
     Fd fd[N];
     std::string names[N];
@@ -102,7 +107,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad*
     const uint64_t per_chunk = std::max<uint64_t>(1, kChunkCols / block);  // blocks per chunk
     const uint64_t cols = per_chunk * block;                               // columns per chunk
     const uint64_t pitch = round_up(std::min(cols, round_up(size, block)), 256);
-    HEC_TRY(sc->reserve(size_t(N) * pitch, size_t(per_chunk)));
+    HEC_TRY(sc->reserve(size_t(N) * pitch, size_t(per_chunk) * (locate ? 2 : 1)));
     uint8_t* zs[2] = {pinned_device_ptr(sc->slot[0]), pinned_device_ptr(sc->slot[1])};
     if (!zs[0] || !zs[1]) return fail(HEC_ERR_HIP, "pinned scrub slots are not addressable by the device");
 
@@ -118,11 +123,12 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad*
         for (uint64_t b = 0; b < nb; ++b) {
             const uint32_t w = sc->words_host[q][b];
             if (!w) continue;
-            if (found < cap) {
-                bad[found].offset = c * cols + b * block;
-                bad[found].length = uint32_t(std::min(block, len - b * block));
-                bad[found].parity_mask = w;
-            }
+            const uint64_t offset = c * cols + b * block;
+            const uint32_t length = uint32_t(std::min(block, len - b * block));
+            if (found < cap && locate)
+                sus[found] = hec_scrub_suspect{offset, length, w, sc->words_host[q][per_chunk + b], 0};
+            else if (found < cap)
+                bad[found] = hec_scrub_bad{offset, length, w};
             ++found;
         }
         return HEC_OK;
@@ -145,15 +151,23 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad*
         // launch compares exactly the bytes read, never the slot's stale rest
         const uint64_t full = len / block, tail = len - full * block;
         uint32_t* wd = sc->words_dev[q];
-        if (full)
-            HEC_TRY(run_verify(gd->encode, K, zs[q], block, pitch, zs[q] + uint64_t(K) * pitch, block, pitch, block,
-                               uint32_t(full), wd, nullptr, sc->stream));
-        if (tail)
-            HEC_TRY(run_verify(gd->encode, K, zs[q] + full * block, block, pitch,
-                               zs[q] + uint64_t(K) * pitch + full * block, block, pitch, tail, 1, wd + full, nullptr,
-                               sc->stream));
-        HEC_HIP(hipMemcpyAsync(sc->words_host[q], wd, size_t(full + (tail ? 1 : 0)) * 4, hipMemcpyDeviceToHost,
-                               sc->stream));
+        // n blocks of blen bytes from column `first` of the slot on
+        auto launch = [&](uint64_t first, uint64_t blen, uint64_t n) -> int {
+            const uint8_t* d = zs[q] + first * block;
+            const uint8_t* p = d + uint64_t(K) * pitch;
+            if (locate)
+                return run_locate(*gd, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first,
+                                  wd + per_chunk + first, nullptr, sc->stream);
+            return run_verify(gd->encode, K, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first, nullptr,
+                              sc->stream);
+        };
+        if (full) HEC_TRY(launch(0, block, full));
+        if (tail) HEC_TRY(launch(full, tail, 1));
+        const size_t n_words = size_t(full + (tail ? 1 : 0));
+        HEC_HIP(hipMemcpyAsync(sc->words_host[q], wd, n_words * 4, hipMemcpyDeviceToHost, sc->stream));
+        if (locate)
+            HEC_HIP(hipMemcpyAsync(sc->words_host[q] + per_chunk, wd + per_chunk, n_words * 4, hipMemcpyDeviceToHost,
+                                   sc->stream));
         HEC_HIP(hipEventRecord(sc->done[q], sc->stream));
     }
     if (n_chunks >= 2) HEC_TRY(collect(n_chunks - 2));
@@ -168,15 +182,30 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, hec_scrub_bad*
 
 extern "C" {
 
-int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
-                        uint64_t* n_blocks) {
+// The two entry points' shared prologue; has_out: the result array is there.
+static int scrub_args(const char* base_filename, uint64_t block_size, bool has_out, size_t cap, size_t* n_bad,
+                      uint64_t* n_blocks, uint64_t* block) {
     if (n_bad) *n_bad = 0;
     if (n_blocks) *n_blocks = 0;
-    if (!base_filename || (cap && !bad)) return hec::fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    const uint64_t block = block_size ? block_size : HEC_SMALL_BLOCK_SIZE;
-    if (block % 4096 != 0 || block > 0xFFFFF000ull)
+    if (!base_filename || (cap && !has_out)) return hec::fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    *block = block_size ? block_size : HEC_SMALL_BLOCK_SIZE;
+    if (*block % 4096 != 0 || *block > 0xFFFFF000ull)
         return hec::fail(HEC_ERR_INVALID_ARGUMENT, "block_size must be a multiple of 4096 below 4 GiB");
-    return hec::verify_ec_files_impl(base_filename, block, bad, cap, n_bad, n_blocks);
+    return HEC_OK;
+}
+
+int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
+                        uint64_t* n_blocks) {
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, false, bad, nullptr, cap, n_bad, n_blocks);
+}
+
+int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                                size_t* n_bad, uint64_t* n_blocks) {
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, true, nullptr, bad, cap, n_bad, n_blocks);
 }
 
 }  // extern "C"

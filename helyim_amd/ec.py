@@ -81,6 +81,31 @@ def verify_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024):
             [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask)) for i in range(got)])
 
 
+class _ScrubSuspect(ctypes.Structure):
+    """include/hec.h ``hec_scrub_suspect``."""
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint32), ("parity_mask", ctypes.c_uint32),
+                ("suspects", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def locate_corrupt_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024):
+    """verify_ec_files that also names the corrupt file of each bad block
+    (hec_locate_corrupt_ec_files). Returns ``(n_blocks, n_bad, bad)`` with
+    entries ``(offset, length, parity_mask, suspects)``: bit c of suspects =
+    ``.ec(c)`` alone explains a byte column of the block, bit 31 = a column no
+    single file explains. Reads only: to repair, delete the named ``.ecNN``
+    and call ``rebuild_ec_files``."""
+    if cap < 0:
+        raise ValueError("negative cap")
+    bad = (_ScrubSuspect * cap)() if cap else None
+    n_bad, n_blocks = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    check_ec(lib.hec_locate_corrupt_ec_files(base_filename.encode(), block_size, bad, cap, ctypes.byref(n_bad),
+                                             ctypes.byref(n_blocks)))
+    got = min(cap, n_bad.value)
+    return (int(n_blocks.value), int(n_bad.value),
+            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
+             for i in range(got)])
+
+
 # --- EC volume files around the shards (helyim-ec host-side byte formats) ---
 
 def write_sorted_file_from_index(base_filename: str, ext: str = ".ecx") -> None:

@@ -242,6 +242,64 @@ int hec_gpu_verify_batch(const hec_rs_t* rs,
                          uint64_t shard_len, uint32_t n_stripes,
                          uint32_t* d_mismatch, uint32_t* d_bad_stripes, void* stream);
 
+/* Locate: hec_gpu_verify_batch that also names the corrupt shard. RS(10,4)
+ * only (any other codec: HEC_ERR_INVALID_ARGUMENT before any device work, the
+ * detail says so). d_mismatch and d_bad_stripes are exactly
+ * hec_gpu_verify_batch's. Result contract of d_suspects[s] (device, 32-bit
+ * words), over the byte columns o < shard_len of stripe s: let syn(o) = stored
+ * parity XOR parity of the stored data at column o (4 bytes), and H = [P | I4]
+ * the 4 x 14 check matrix (P = the 4 x 10 parity rows of hec_rs_matrix).
+ *   - syn(o) == 0: the column contributes nothing;
+ *   - there is a shard c in 0..13 and a byte v != 0 with syn(o) == v * H[:,c]
+ *     (such a c is unique): bit c is set. Data shards are bits 0..9, parity
+ *     shard j is bit 10 + j;
+ *   - otherwise HEC_SUSPECT_UNEXPLAINED (bit 31) is set.
+ * A clean stripe gives 0. Different columns of one stripe may name different
+ * shards; then all their bits are set. Guarantee (RS(10,4) is MDS: any four
+ * columns of H are independent): a column with at most 3 wrong shards never
+ * sets the bit of an intact shard; one wrong shard sets its own bit; two or
+ * three wrong shards set bit 31. 4 or more wrong shards in ONE byte column
+ * are outside any guarantee (no decoder can do better). Bytes at or past
+ * shard_len take no part, as in verify.
+ * Two passes on `stream`, no host synchronisation: hec_gpu_verify_batch's
+ * kernels, then a second kernel that reads only the stripes the first flagged.
+ * Measured on one MI355X, 4096 x 1 MiB stripes, medians of 9 alternating
+ * rounds (tools/bench_locate.py, profiles/locate/bench_locate.json): verify
+ * alone 8.70 ms, locate on the clean batch 8.91 ms (1.025 x, 1.018..1.026 over
+ * the rounds), with 1 stripe holding a flipped byte 8.94 ms, with 64 such
+ * stripes 9.11 ms.
+ * The call overwrites words [0, n_stripes) of d_mismatch and d_suspects and
+ * writes no other byte anywhere. d_mismatch and d_suspects must be two
+ * distinct arrays that overlap neither each other nor any shard (not checked:
+ * the second pass clears d_suspects while it still reads d_mismatch). Argument errors are hec_gpu_verify_batch's
+ * plus a null d_suspects and the codec, all before any device work; n_stripes
+ * == 0 returns HEC_OK and writes nothing. Any strides, bases and lengths (odd
+ * ones take the unaligned kernel). */
+#define HEC_SUSPECT_UNEXPLAINED 0x80000000u
+int hec_gpu_locate_corrupt_batch(const hec_rs_t* rs,
+                                 const uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                                 const uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                                 uint64_t shard_len, uint32_t n_stripes,
+                                 uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes, void* stream);
+
+/* Repair in place what locate can name: hec_gpu_reconstruct_batch's layout
+ * (RS(10,4); parity at d_shards + 10 * shard_stride). In stream order: (1)
+ * locate into d_mismatch / d_suspects as above; (2) d_present_masks[s] =
+ * 0x3FFF & ~d_suspects[s] when the word names 1 to 4 shards and bit 31 is
+ * clear, else 0x3FFF, and *d_unrepaired (device word, optional, accumulated)
+ * gets plus one per stripe with a non-zero word that is left alone; (3)
+ * hec_gpu_reconstruct_batch with those masks. Only the suspect shards of
+ * repaired stripes are written; everything else, the unrepaired stripes
+ * included, stays byte for byte. All three arrays hold n_stripes words, are
+ * overwritten, and must be distinct arrays that overlap neither one another
+ * nor any shard (not checked). The repair trusts the guarantee above: a caller who wants proof
+ * runs hec_gpu_verify_batch afterwards. Argument errors as locate's (all
+ * three arrays required), before any device work. */
+int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                         uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                         uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_present_masks,
+                         uint32_t* d_unrepaired, void* stream);
+
 /* ---- host-memory batches (the path helyim runs: bytes start and end in host
  * memory, encoder.rs:169-195 / 263-304) -------------------------------------
  * Same strided layout as above but on HOST pointers; synchronous on return.
@@ -361,6 +419,23 @@ typedef struct hec_scrub_bad {
 } hec_scrub_bad;
 int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap,
                         size_t* n_bad, uint64_t* n_blocks);
+/* hec_verify_ec_files that also names the corrupt file of each bad block:
+ * arguments, block rules, errors and the read-only promise are identical;
+ * each entry carries the block's suspects word (hec_gpu_locate_corrupt_batch's
+ * contract: bit c = .ec(c) alone explains a byte column of the block, bit 31 =
+ * a column no single file explains). How the result is used: when a volume's
+ * blocks name one file (up to four) and bit 31 is clear everywhere, delete
+ * the named .ecNN and call hec_rebuild_ec_files, which recreates them from the
+ * other files; then scrub again. No file is written here. */
+typedef struct hec_scrub_suspect {
+    uint64_t offset;
+    uint32_t length;
+    uint32_t parity_mask;
+    uint32_t suspects;
+    uint32_t reserved;  /* 0 */
+} hec_scrub_suspect;
+int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                                size_t* n_bad, uint64_t* n_blocks);
 
 /* ---- EC volume files around the shards (host-side byte formats) ----------- */
 /* write_sorted_file_from_index(base, ext) (encoder.rs:21-37): replay base.idx

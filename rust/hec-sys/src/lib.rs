@@ -62,6 +62,22 @@ pub struct hec_scrub_bad {
     pub parity_mask: u32,
 }
 
+/// A bad column block with the shard files its byte columns name
+/// (`hec_locate_corrupt_ec_files`): bit c of `suspects` = `.ec(c)` alone
+/// explains a column, `HEC_SUSPECT_UNEXPLAINED` = a column no single file does.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct hec_scrub_suspect {
+    pub offset: u64,
+    pub length: u32,
+    pub parity_mask: u32,
+    pub suspects: u32,
+    pub reserved: u32,
+}
+
+/// Bit 31 of a suspects word (`hec_gpu_locate_corrupt_batch`).
+pub const HEC_SUSPECT_UNEXPLAINED: u32 = 0x8000_0000;
+
 pub const HEC_OK: c_int = 0;
 pub const HEC_ERR_TOO_FEW_SHARDS_PRESENT: c_int = 10;
 pub const HEC_ERR_IO: c_int = 32;
@@ -132,6 +148,14 @@ extern "C" {
                                 data_shard_stride: u64, d_parity: *const u8, parity_stripe_stride: u64,
                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
                                 d_mismatch: *mut u32, d_bad_stripes: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_locate_corrupt_batch(rs: *const hec_rs_t, d_data: *const u8, data_stripe_stride: u64,
+                                        data_shard_stride: u64, d_parity: *const u8, parity_stripe_stride: u64,
+                                        parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                        d_mismatch: *mut u32, d_suspects: *mut u32, d_bad_stripes: *mut u32,
+                                        stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_repair_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64, shard_stride: u64,
+                                shard_len: u64, n_stripes: u32, d_mismatch: *mut u32, d_suspects: *mut u32,
+                                d_present_masks: *mut u32, d_unrepaired: *mut u32, stream: *mut c_void) -> c_int;
     pub fn hec_host_verify_batch(rs: *const hec_rs_t, h_data: *const u8, data_stripe_stride: u64,
                                  data_shard_stride: u64, h_parity: *const u8, parity_stripe_stride: u64,
                                  parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
@@ -165,6 +189,8 @@ extern "C" {
                                 -> c_int;
     pub fn hec_verify_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_bad, cap: usize,
                                n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
+    pub fn hec_locate_corrupt_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_suspect,
+                                       cap: usize, n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
     pub fn hec_write_sorted_file_from_index(base_filename: *const c_char, ext: *const c_char) -> c_int;
     pub fn hec_rebuild_ecx_file(base_filename: *const c_char) -> c_int;
     pub fn hec_save_volume_info(filename: *const c_char, version: u32) -> c_int;
