@@ -15,6 +15,7 @@ from .errors import check
 from .rs import ReedSolomon
 
 lib = _lib.lib
+check_status = check  # for the calls that have a result tensor named `check`
 
 
 def _stream_ptr(stream=None):
@@ -202,6 +203,91 @@ def repair_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor 
                                    mismatch.data_ptr(), suspects.data_ptr(), present_masks.data_ptr(), left,
                                    _stream_ptr(stream)))
     return mismatch, suspects, present_masks
+
+
+def _masks_arg(S: int, present_masks: torch.Tensor) -> torch.Tensor:
+    if not (present_masks.is_cuda and present_masks.dtype in (torch.int32, torch.uint32)
+            and present_masks.numel() == S and present_masks.is_contiguous()):
+        raise ValueError("present_masks must be a contiguous 32-bit CUDA tensor with one word per stripe")
+    _check_device(present_masks)
+    return present_masks
+
+
+def verify_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
+                         check: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                         unchecked: torch.Tensor = None, stream=None) -> torch.Tensor:
+    """Scrub degraded ``stripes[S, 14, L]`` (hec_gpu_verify_present_batch, RS(10,4)
+    only): present_masks as reconstruct_batch's. Of a stripe's p >= 11 present
+    shards the ten lowest are decoded from and the other p - 10 compared: bit e
+    (shard index) of the returned int32 ``[S]`` word is set when present shard
+    e differs from what those ten imply; with the full mask that is
+    verify_batch's word shifted left by 10. Stripes with p <= 10 give 0, are
+    not read and are counted into unchecked; bad_stripes counts the non-zero
+    words (32-bit CUDA words, accumulated). Absent shards are never read and
+    nothing but the words is written. Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    check = _words_arg(S, check, "check")
+    check_status(lib.hec_gpu_verify_present_batch(
+        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
+        check.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"),
+        _stream_ptr(stream)))
+    return check
+
+
+def locate_corrupt_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
+                                 check: torch.Tensor = None, suspects: torch.Tensor = None,
+                                 bad_stripes: torch.Tensor = None, unchecked: torch.Tensor = None, stream=None):
+    """verify_present_batch that also names the corrupt survivor
+    (hec_gpu_locate_corrupt_present_batch). Returns ``(check, suspects)``: bit c
+    of suspects[s] = present shard c alone explains a byte column of stripe s,
+    ``helyim_amd.SUSPECT_UNEXPLAINED`` = a column no single shard explains. With
+    1 or 2 shards lost one corrupt survivor is named; with 3 lost it is only
+    detected (bit 31); with 2 lost, two wrong shards in one column may name an
+    intact shard (include/hec.h has the table). With the full mask the words
+    are locate_corrupt_batch's (check = mismatch << 10)."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    check = _words_arg(S, check, "check")
+    suspects = _words_arg(S, suspects, "suspects")
+    check_status(lib.hec_gpu_locate_corrupt_present_batch(
+        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
+        check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
+    return check, suspects
+
+
+def reconstruct_checked_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
+                              check: torch.Tensor = None, suspects: torch.Tensor = None,
+                              use_masks: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                              unrepaired: torch.Tensor = None, stream=None):
+    """reconstruct_batch that checks its survivors first
+    (hec_gpu_reconstruct_checked_batch). Returns ``(check, suspects, use_masks)``:
+    a clean or uncheckable stripe is rebuilt from present_masks as
+    reconstruct_batch would; a stripe whose suspects word names shards (bit 31
+    clear, at least 10 others present) has them rebuilt too (use mask =
+    present & ~suspects); any other dirty stripe is left byte for byte, holes
+    included (use mask 0x3FFF), and counted into unrepaired. bad_stripes is
+    reconstruct_batch's count. Only shards outside a stripe's use mask are
+    written. Run verify_batch afterwards for proof."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    check = _words_arg(S, check, "check")
+    suspects = _words_arg(S, suspects, "suspects")
+    use_masks = _words_arg(S, use_masks, "use_masks")
+    check_status(lib.hec_gpu_reconstruct_checked_batch(
+        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
+        check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        _counter_arg(unrepaired, "unrepaired"), _stream_ptr(stream)))
+    return check, suspects, use_masks
+
+
+def check_kernel_name(L: int) -> str:
+    """The kernel an aligned verify_present_batch of this shard length runs (hec_check_kernel_name)."""
+    return lib.hec_check_kernel_name(L).decode()
 
 
 def verify_kernel_name(L: int) -> str:

@@ -149,6 +149,64 @@ int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_
                      shard_stride, shard_len, n_stripes, d_present_masks, nullptr, s);
 }
 
+int hec_gpu_verify_present_batch(const hec_rs_t* rs, const uint8_t* d_shards, uint64_t stripe_stride,
+                                 uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                 const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_bad_stripes,
+                                 uint32_t* d_unchecked, void* stream) {
+    HEC_TRY(check_present_args(rs, d_shards, d_present_masks, d_check, stripe_stride, shard_stride, shard_len,
+                               n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HEC_TRY(ensure_check_plans(rs, gd, s));
+    return run_check(*gd, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks, d_check,
+                     d_bad_stripes, d_unchecked, s);
+}
+
+int hec_gpu_locate_corrupt_present_batch(const hec_rs_t* rs, const uint8_t* d_shards, uint64_t stripe_stride,
+                                         uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                         const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_suspects,
+                                         uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream) {
+    if (rs && d_shards && d_present_masks && d_check && !d_suspects)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    HEC_TRY(check_present_args(rs, d_shards, d_present_masks, d_check, stripe_stride, shard_stride, shard_len,
+                               n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HEC_TRY(ensure_check_plans(rs, gd, s));
+    return run_locate_present(*gd, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks,
+                              d_check, d_suspects, d_bad_stripes, d_unchecked, s);
+}
+
+int hec_gpu_reconstruct_checked_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                      uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                      const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_suspects,
+                                      uint32_t* d_use_masks, uint32_t* d_bad_stripes, uint32_t* d_unrepaired,
+                                      void* stream) {
+    if (rs && d_shards && d_present_masks && d_check && (!d_suspects || !d_use_masks))
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    HEC_TRY(check_present_args(rs, d_shards, d_present_masks, d_check, stripe_stride, shard_stride, shard_len,
+                               n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // both plan sets before any launch: their first call uploads and waits
+    HEC_TRY(ensure_check_plans(rs, gd, s));
+    HEC_TRY(ensure_dense_decode(rs, gd, s));
+    HEC_TRY(run_locate_present(*gd, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks,
+                               d_check, d_suspects, nullptr, nullptr, s));
+    HEC_HIP(launch_use_masks(d_present_masks, d_check, d_suspects, d_use_masks, d_unrepaired, n_stripes, s));
+    // a stripe left alone has every shard "present": the reconstruct's no-op
+    return run_apply(gd->decode_dense, uint32_t(rs->k), d_shards, stripe_stride, shard_stride, d_shards, stripe_stride,
+                     shard_stride, shard_len, n_stripes, d_use_masks, d_bad_stripes, s);
+}
+
+const char* hec_check_kernel_name(uint64_t shard_len) { return check_kernel_name(shard_len); }
+
 int hec_gpu_fill_splitmix(uint8_t* d_base, uint64_t stripe_stride, uint64_t bytes_per_stripe, uint32_t n_stripes,
                           uint64_t seed_base, void* stream) {
     if (!d_base) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");

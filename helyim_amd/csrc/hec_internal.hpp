@@ -222,9 +222,21 @@ struct GeomDevice {
     // RS(10,4) only: the locate kernel's ratio constants as one 3 x 10 plan,
     // row j - 1, input c = P[j][c] / P[0][c] (P = the parity rows; run_locate)
     DevicePlanSet locate;
+    // RS(10,4) only, built on first use (ensure_check_plans): the degraded
+    // scrub's plans. check: a dense LUT over the 2^14 present masks to one
+    // plan per mask with 11 or more shards present (inputs B, outputs E,
+    // coefficients A_m, 4-row tables); check_ratio: the same plan ids with the
+    // masked locate's ratios A_m[j][c] / A_m[0][c] as 3-row tables.
+    DevicePlanSet check, check_ratio;
+    bool check_ready = false;
 };
 int geom_device(const hec_rs* rs, GeomDevice** out);
 int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s);
+// Check plan of one present mask: in_ids = the first k present shards (B, the
+// reconstruct's inputs), out_ids = the other present shards (E), coefs = A_m.
+int check_plan(const hec_rs* rs, const uint8_t* present, Mat& coefs, std::vector<uint32_t>& in_ids,
+               std::vector<uint32_t>& out_ids);
+int ensure_check_plans(const hec_rs* rs, GeomDevice* gd, hipStream_t s);
 
 int current_device(int* dev);
 
@@ -453,6 +465,28 @@ inline int check_locate_args(const hec_rs* rs, const void* suspects) {
     if (rs->k != 10 || rs->m != 4)
         return fail(HEC_ERR_INVALID_ARGUMENT, "locate and repair are RS(10,4) only");
     return HEC_OK;
+}
+
+// Masked verify (degraded scrub; hec.h hec_gpu_verify_present_batch is the
+// contract), asynchronously on s: check[0, n_stripes) are cleared on s, then
+// the check kernels run over gd's check plans (ensure_check_plans first).
+int run_check(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* bad,
+              uint32_t* unchecked, hipStream_t s);
+// run_check, then suspects[0, n_stripes) are cleared on s and the masked
+// locate kernel reads the flagged stripes again.
+int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+                       uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* suspects,
+                       uint32_t* bad, uint32_t* unchecked, hipStream_t s);
+// Prologue of the masked entry points: nulls, the empty shard, the codec, the
+// layout. All before device work.
+inline int check_present_args(const hec_rs* rs, const void* shards, const void* masks, const void* check,
+                              uint64_t stripe_stride, uint64_t shard_stride, uint64_t len, uint32_t n_stripes) {
+    if (!rs || !shards || !masks || !check) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    if (rs->k != 10 || rs->m != 4)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "masked verify, locate and checked reconstruct are RS(10,4) only");
+    return check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, len, n_stripes);
 }
 
 }  // namespace hec

@@ -195,6 +195,67 @@ int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
     return HEC_OK;
 }
 
+// decode_plan's sibling for the degraded scrub: the inputs are the same first
+// k present shards (B), but the outputs are the OTHER present shards (E), so
+// coefs = A_m, what the reconstruct would apply to B had E been erased.
+int check_plan(const hec_rs* rs, const uint8_t* present, Mat& coefs, std::vector<uint32_t>& in_ids,
+               std::vector<uint32_t>& out_ids) {
+    const int k = rs->k, n = rs->n;
+    in_ids.clear();
+    out_ids.clear();
+    for (int i = 0; i < n; ++i) {
+        if (!present[i]) continue;
+        if (int(in_ids.size()) < k) in_ids.push_back(uint32_t(i));
+        else out_ids.push_back(uint32_t(i));
+    }
+    if (int(in_ids.size()) < k) return fail(HEC_ERR_TOO_FEW_SHARDS_PRESENT, "");
+    Mat sub(k, k), rows(int(out_ids.size()), k);
+    for (int r = 0; r < k; ++r)
+        for (int c = 0; c < k; ++c) sub.at(r, c) = rs->matrix.at(int(in_ids[r]), c);
+    Mat inv;
+    if (!mat_invert(sub, inv)) return fail(HEC_ERR_INVALID_ARGUMENT, "singular decode matrix");
+    for (size_t r = 0; r < out_ids.size(); ++r)
+        for (int c = 0; c < k; ++c) rows.at(int(r), c) = rs->matrix.at(int(out_ids[r]), c);
+    coefs = mat_mul(rows, inv);
+    return HEC_OK;
+}
+
+int ensure_check_plans(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_geom_mu);
+    if (gd->check_ready) return HEC_OK;
+    const int n = rs->n, k = rs->k;
+    if (k != 10 || rs->m != 4) return fail(HEC_ERR_INVALID_ARGUMENT, "check plans are RS(10,4) only");
+    // plan ids count the masks with a spare shard in ascending order, in both
+    // sets: the tables of plan p start at p * 200 (check) and p * 150 (ratio) words
+    HostPlans hp, rp;
+    hp.fixed_rows = 4;
+    rp.fixed_rows = 3;
+    std::vector<uint32_t> lut(size_t(1) << n, kNoPlan);
+    uint8_t present[16];
+    Mat coefs;
+    std::vector<uint32_t> in_ids, out_ids;
+    const Gf& g = gf();
+    for (uint32_t mask = 0; mask < (1u << n); ++mask) {
+        if (__builtin_popcount(mask) <= k) continue;
+        for (int i = 0; i < n; ++i) present[i] = (mask >> i) & 1;
+        HEC_TRY(check_plan(rs, present, coefs, in_ids, out_ids));
+        lut[mask] = hp.add(coefs, in_ids, out_ids);
+        // the masked locate's constants: A_m[j][c] / A_m[0][c], j = 1..r-1 (zero past r)
+        Mat ratio(3, k);
+        for (int c = 0; c < k; ++c) {
+            if (coefs.at(0, c) == 0) return fail(HEC_ERR_INVALID_ARGUMENT, "zero entry in a check matrix");
+            for (int j = 1; j < coefs.rows; ++j) ratio.at(j - 1, c) = g.mul[coefs.at(j, c)][g.inv(coefs.at(0, c))];
+        }
+        rp.add(ratio, in_ids, {1, 2, 3});
+    }
+    HEC_TRY(gd->check.upload(hp, &lut, s));
+    HEC_TRY(gd->check_ratio.upload(rp, nullptr, s));
+    gd->check.fast104 = true;
+    gd->check.lut_bits = uint32_t(n);
+    gd->check_ready = true;
+    return HEC_OK;
+}
+
 // The coding arguments every strided launch shares, from a plan set and the
 // batch's layout. Returns whether every base and stride is 16-byte aligned.
 static bool fill_args(ApplyArgs& a, const DevicePlanSet& ps, const uint8_t* in_base, uint64_t in_stripe,
@@ -273,6 +334,48 @@ int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, 
     v.ratio_tabs = gd.locate.tabs;
     HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
     HEC_HIP(launch_locate(v, aligned, s));
+    return HEC_OK;
+}
+
+// The arguments of a masked verify or locate launch over gd's check plans;
+// returns fill_args' alignment.
+static bool fill_check_args(CheckArgs& v, const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride,
+                            uint64_t shard_stride, uint64_t len, uint32_t n_stripes, const uint32_t* masks,
+                            uint32_t* check, uint32_t* bad, uint32_t* unchecked) {
+    v.check = check;
+    v.unchecked = unchecked;
+    v.a.masks = masks;
+    v.a.lut = gd.check.lut;
+    v.a.mask_limit = (1u << gd.check.lut_bits) - 1u;
+    return fill_args(v.a, gd.check, shards, stripe_stride, shard_stride, const_cast<uint8_t*>(shards) /* only read */,
+                     stripe_stride, shard_stride, len, n_stripes, bad);
+}
+
+int run_check(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* bad,
+              uint32_t* unchecked, hipStream_t s) {
+    if (n_stripes == 0) return HEC_OK;
+    CheckArgs v{};
+    const bool aligned =
+        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked);
+    HEC_HIP(hipMemsetAsync(check, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_check(v, aligned, s));
+    return HEC_OK;
+}
+
+int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+                       uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* suspects,
+                       uint32_t* bad, uint32_t* unchecked, hipStream_t s) {
+    if (n_stripes == 0) return HEC_OK;
+    HEC_TRY(run_check(gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked, s));
+    // pass 2: only the stripes pass 1 flagged are read again (the counts are pass 1's)
+    CheckArgs v{};
+    const bool aligned =
+        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, nullptr, nullptr);
+    v.suspects = suspects;
+    v.ratio_tabs = gd.check_ratio.tabs;
+    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_locate_present(v, aligned, s));
     return HEC_OK;
 }
 

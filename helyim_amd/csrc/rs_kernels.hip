@@ -27,6 +27,9 @@
 //  * The locate kernel (rs104_locate_kernel) is the scrub's second pass: it
 //    reads only the stripes the verify flagged and names the wrong shard of
 //    each byte column from its syndrome.
+//  * The masked verify and locate (rs104_check_kernel and siblings) are the
+//    degraded scrub: the mask-driven decode with its stores replaced by a
+//    compare against the spare present shards.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -765,6 +768,7 @@ static void set_fast_map(ApplyArgs& a, uint32_t chunk_bytes, bool round_up) {
 // The coding arguments of either kernel argument struct.
 static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
 static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
+static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
 
 // A fast-mapped batch (set_fast_map), one workgroup per item: k32 where every
 // byte offset inside a shard fits 32 bits, k64 for shards of 4 GiB and more.
@@ -1079,6 +1083,299 @@ hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32
     const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
     hipLaunchKernelGGL(repair_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, suspects, masks, unrepaired,
                        n_stripes);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Masked verify and locate (degraded scrub, RS(10,4)): a stripe with shards
+// missing still has r = p - 10 spare shards among its p >= 11 present ones.
+// The ten lowest present shards (B) are what the reconstruct would decode
+// from; A_m applied to them is what the other present shards (E) must hold.
+// The check kernels are the mask-driven decode with its stores replaced by a
+// compare against the stored E rows; the result bits are by shard index.
+// ---------------------------------------------------------------------------
+// Fast form, rs104_narrow_chunk<true> with a compare: 8 bytes per lane, one
+// 2 KiB column range per workgroup, the ten B loads and the r stored E loads
+// in flight before the math, the plan looked up from the mask while they fly.
+// Aligned bases and strides, shard_len a multiple of 2 KiB below 4 GiB.
+__global__ __launch_bounds__(kThreads) void rs104_check_kernel(CheckArgs v) {
+    typedef u32x2 V;
+    constexpr int K = 10, N = 14, R = 4, VB = int(sizeof(V));
+    const ApplyArgs& a = v.a;
+    uint32_t stripe, chunk;
+    fast_item(a, a.chunks_per_stripe, stripe, chunk);
+    const uint32_t mask = as_const(a.masks)[stripe] & ((1u << N) - 1);
+    const uint32_t present = __builtin_popcount(mask);
+    if (present <= K) {  // wave-uniform: no spare shard, nothing to check and nothing read
+        if (chunk == 0 && threadIdx.x == 0 && v.unchecked) atomicAdd(v.unchecked, 1u);
+        return;
+    }
+    const uint32_t r = present - K;
+    uint32_t in_id[K], out_id[R];
+    uint32_t m = mask;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {  // B: the ten lowest present shards
+        in_id[i] = __builtin_ctz(m);
+        m &= m - 1;
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {  // E: the other present shards, ascending
+        out_id[j] = m ? __builtin_ctz(m) : 0;
+        m &= m - 1;
+    }
+    uint32_t plan = as_const(a.lut)[mask];  // first used after the data loads
+    const uint8_t* b = a.in_base + uint64_t(stripe) * a.in_stripe;
+    const uint32_t o = chunk * (kThreads * VB) + threadIdx.x * VB;
+    V d[K], st[R];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        d[i] = __builtin_nontemporal_load(
+            (const __attribute__((address_space(1))) V*)((gcu8p)(b + uint64_t(in_id[i]) * a.in_shard) + o));
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        st[j] = V(0u);
+        if (uint32_t(j) < r)
+            st[j] = __builtin_nontemporal_load(
+                (const __attribute__((address_space(1))) V*)((gcu8p)(b + uint64_t(out_id[j]) * a.in_shard) + o));
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the math
+    asm volatile("" : "+s"(plan));
+    cu32p tab = as_const(a.tabs) + plan * (K * R * 5);
+    V acc[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j] = V(0u);
+#pragma unroll
+    for (int i = 0; i < K; i += 2)
+        gf_mac2<R, V>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), r);
+    // rows at or past r: acc and st are both zero, the ballot is empty
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const uint32_t x = (acc[j][0] ^ st[j][0]) | (acc[j][1] ^ st[j][1]);
+        bits |= (__ballot(x != 0) != 0 ? 1u : 0u) << out_id[j];
+    }
+    report_mismatch(v.check + stripe, a.bad_count, bits);
+}
+
+// Every other layout and length: rs_verify_kernel's grid-stride loop and row
+// groups (apply_rows<10, ALIGNED, VERIFY>) with the stripe's check plan; the
+// last vector of a shard is zero-filled from a.len on, inputs and stored rows
+// alike, so bytes at or past a.len compare equal.
+template <bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void rs104_check_stride_kernel(CheckArgs v) {
+    const ApplyArgs& a = v.a;
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        const uint32_t pid = as_const(a.lut)[as_const(a.masks)[stripe] & a.mask_limit];
+        if (pid == kNoPlan) {  // at most ten shards present
+            if (chunk == 0 && threadIdx.x == 0 && v.unchecked) atomicAdd(v.unchecked, 1u);
+            continue;
+        }
+        const __attribute__((address_space(4))) DevPlan* pp = as_const(a.plans) + pid;
+        const DevPlan p{pp->nin, pp->nout, pp->tab_off, pp->idx_off, pp->tab_rows, {0, 0, 0}};
+        uint8_t* b = a.out_base + uint64_t(stripe) * a.out_stripe;  // only read
+        cu32p in_ids = as_const(a.idx) + p.idx_off;
+        cu32p out_ids = in_ids + p.nin;
+        cu32p tab = as_const(a.tabs) + p.tab_off;
+        const uint64_t chunk_off = uint64_t(chunk) * (kThreads * kVecBytes);
+        const uint32_t differs =
+            apply_rows<10, ALIGNED, true>(a, b, b, in_ids, out_ids, tab, p, p.tab_rows * 5, chunk_off);
+        uint32_t bits = 0;
+        for (uint32_t j = 0; j < p.nout; ++j) bits |= (__ballot((differs >> j) & 1u) != 0 ? 1u : 0u) << out_ids[j];
+        report_mismatch(v.check + stripe, a.bad_count, bits);
+    }
+}
+
+constexpr const char* kFastCheckName = "rs104_check_kernel<8 B per lane> (table lookup)";
+constexpr const char* kStrideCheckName = "rs104_check_stride_kernel (table lookup)";
+
+static bool check_fast(uint64_t len) { return len % kNarrowChunk == 0 && len <= 0xFFFFFFFFull; }
+
+const char* check_kernel_name(uint64_t len) {
+    if (len == 0) return kNoLaunch;
+    return check_fast(len) ? kFastCheckName : kStrideCheckName;
+}
+
+hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream) {
+    const ApplyArgs& a = v.a;
+    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
+    if (aligned && check_fast(a.len)) {
+        // one chunk per workgroup and no grid-stride loop: batches past one
+        // launch's workgroup limit go in stripe ranges, as launch_verify's
+        // (the masks advance in stripe_range, the words here)
+        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, a.len / kNarrowChunk);
+        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
+            const Range r = range_at(a.n_stripes, step, i);
+            CheckArgs b = v;
+            b.a = stripe_range(a, r);
+            b.check = v.check + r.first;
+            set_fast_map(b.a, kNarrowChunk, false);
+            hipError_t e = launch_items(rs104_check_kernel, rs104_check_kernel, b, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    return launch_stride(aligned ? rs104_check_stride_kernel<true> : rs104_check_stride_kernel<false>, v, stream);
+}
+
+// rs104_locate_kernel made mask-driven: the syndrome has r = p - 10 rows (rows
+// past r stay zero: zero tables, no stored row), H_m = [A_m | I_r].
+//  * r = 1: every non-zero column is unexplained (one row cannot tell shards
+//    apart);
+//  * exactly one of r >= 2 rows non-zero -> shard E[j];
+//  * all r non-zero -> shard B[c] when s[j] = s[0] * A_m[j][c] / A_m[0][c] for
+//    j = 1..r-1 (no entry of A_m is zero and no two columns of H_m are
+//    proportional, for every mask: tests/test_check_model.py);
+//  * anything else is unexplained.
+template <bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(CheckArgs v) {
+    constexpr int K = 10, N = 14, R = 4;
+    const ApplyArgs& a = v.a;
+    cu32p flagged = as_const(v.check);
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        if (flagged[stripe] == 0) continue;  // pass 1 found the stripe clean, or had nothing to check
+        const uint32_t mask = as_const(a.masks)[stripe] & ((1u << N) - 1);
+        const uint32_t pid = as_const(a.lut)[mask];
+        if (pid == kNoPlan) continue;  // never flagged by pass 1
+        const uint32_t r = uint32_t(__builtin_popcount(mask)) - K;
+        uint32_t in_id[K], out_id[R];
+        uint32_t m = mask;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            in_id[i] = __builtin_ctz(m);
+            m &= m - 1;
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            out_id[j] = m ? __builtin_ctz(m) : 0;
+            m &= m - 1;
+        }
+        cu32p tab = as_const(a.tabs) + pid * (K * R * 5);              // A_m: [K][R][5] words
+        cu32p rat = as_const(v.ratio_tabs) + pid * (K * (R - 1) * 5);  // [K][R - 1][5] words
+        const uint8_t* b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        const uint64_t o = uint64_t(chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;
+        u32x4 s[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) s[j] = u32x4{0, 0, 0, 0};
+        if (o < a.len) {
+            const uint64_t avail = a.len - o;
+            if (avail >= kVecBytes) {
+                u32x4 d[K];
+#pragma unroll
+                for (int i = 0; i < K; ++i) d[i] = load_full(b + uint64_t(in_id[i]) * a.in_shard + o, ALIGNED);
+#pragma unroll
+                for (int i = 0; i < K; ++i) gf_mac<R>(s, d[i], tab + i * (R * 5));
+#pragma unroll
+                for (int j = 0; j < R; ++j)
+                    if (uint32_t(j) < r) s[j] ^= load_full(b + uint64_t(out_id[j]) * a.in_shard + o, ALIGNED);
+            } else {
+                for (int i = 0; i < K; ++i)
+                    gf_mac<R>(s, load_tail(b + uint64_t(in_id[i]) * a.in_shard + o, avail), tab + i * (R * 5));
+                for (int j = 0; j < R; ++j)
+                    if (uint32_t(j) < r) s[j] ^= load_tail(b + uint64_t(out_id[j]) * a.in_shard + o, avail);
+            }
+        }
+        uint32_t any = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) any |= s[j][0] | s[j][1] | s[j][2] | s[j][3];
+        if (__ballot(any != 0) == 0) continue;  // wave-uniform: this wave's 1 KiB is clean
+
+        // rows at or past r count as non-zero in "all rows"; with one row
+        // nothing is ever named
+        const uint32_t kEach = 0x80808080u;
+        const uint32_t f1 = r > 1 ? 0u : kEach, f2 = r > 2 ? 0u : kEach, f3 = r > 3 ? 0u : kEach;
+        const uint32_t naming = r > 1 ? ~0u : 0u;
+        uint32_t one[R] = {0, 0, 0, 0};  // bytes where only s[j] is non-zero
+        uint32_t allr[4];                // per dword: bytes where all r rows are
+        uint32_t unexplained = 0, all_any = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t n0 = nz_bytes(s[0][w]), n1 = nz_bytes(s[1][w]), n2 = nz_bytes(s[2][w]),
+                           n3 = nz_bytes(s[3][w]);
+            const uint32_t o0 = n0 & ~(n1 | n2 | n3) & naming, o1 = n1 & ~(n0 | n2 | n3) & naming,
+                           o2 = n2 & ~(n0 | n1 | n3) & naming, o3 = n3 & ~(n0 | n1 | n2) & naming;
+            one[0] |= o0;
+            one[1] |= o1;
+            one[2] |= o2;
+            one[3] |= o3;
+            allr[w] = n0 & (n1 | f1) & (n2 | f2) & (n3 | f3) & naming;
+            all_any |= allr[w];
+            unexplained |= (n0 | n1 | n2 | n3) & ~allr[w] & ~(o0 | o1 | o2 | o3);
+        }
+        uint32_t bits = 0;
+        if (__ballot(all_any != 0) != 0) {  // wave-uniform: some column may name a shard of B
+            uint32_t matched[4] = {0, 0, 0, 0};
+            uint32_t bm = mask;  // its lowest set bit is B[c]
+#pragma unroll 1
+            for (int c = 0; c < K; ++c) {
+                u32x4 e[R - 1];
+#pragma unroll
+                for (int j = 0; j < R - 1; ++j) e[j] = u32x4{0, 0, 0, 0};
+                gf_mac<R - 1>(e, s[0], rat + c * ((R - 1) * 5));
+                uint32_t hit = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const uint32_t diff = (e[0][w] ^ s[1][w]) | (e[1][w] ^ s[2][w]) | (e[2][w] ^ s[3][w]);
+                    const uint32_t mt = allr[w] & ~nz_bytes(diff);
+                    matched[w] |= mt;
+                    hit |= mt;
+                }
+                bits |= (__ballot(hit != 0) != 0 ? 1u : 0u) << __builtin_ctz(bm);
+                bm &= bm - 1;
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) unexplained |= allr[w] & ~matched[w];
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) bits |= (__ballot(one[j] != 0) != 0 ? 1u : 0u) << out_id[j];
+        if (__ballot(unexplained != 0) != 0) bits |= kSuspectUnexplained;
+        if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+    }
+}
+
+hipError_t launch_locate_present(const CheckArgs& v, bool aligned, hipStream_t stream) {
+    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
+    return launch_stride(aligned ? rs104_locate_present_kernel<true> : rs104_locate_present_kernel<false>, v, stream,
+                         kLocateMaxBlocks);
+}
+
+// repair_masks_kernel with the present mask and the check word taken into
+// account; a wave counts the stripes it leaves alone with one atomic.
+__global__ __launch_bounds__(kThreads) void use_masks_kernel(const uint32_t* present, const uint32_t* check,
+                                                             const uint32_t* suspects, uint32_t* use,
+                                                             uint32_t* unrepaired, uint32_t n_stripes) {
+    constexpr uint32_t kAll = (1u << 14) - 1;
+    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
+    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
+        bool left = false;
+        if (s < n_stripes) {
+            const uint32_t m = present[s] & kAll;
+            if (check[s] == 0) {
+                use[s] = m;  // clean, or nothing to check: the plain reconstruct
+            } else {
+                const uint32_t w = suspects[s], kept = m & ~w;
+                const bool repair =
+                    (w & kSuspectUnexplained) == 0 && (w & kAll) != 0 && __builtin_popcount(kept) >= 10;
+                use[s] = repair ? kept : kAll;
+                left = !repair;
+            }
+        }
+        const unsigned long long b = __ballot(left);
+        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
+    }
+}
+
+hipError_t launch_use_masks(const uint32_t* present, const uint32_t* check, const uint32_t* suspects, uint32_t* use,
+                            uint32_t* unrepaired, uint32_t n_stripes, hipStream_t stream) {
+    if (n_stripes == 0) return hipSuccess;
+    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
+    hipLaunchKernelGGL(use_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects, use,
+                       unrepaired, n_stripes);
     return hipGetLastError();
 }
 

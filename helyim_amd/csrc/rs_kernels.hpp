@@ -158,6 +158,39 @@ hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32
 // Name of the kernel an aligned RS(10,4) device verify of this shard length runs.
 const char* verify_kernel_name(uint64_t len);
 
+// Masked verify and locate (degraded scrub, RS(10,4); hec.h
+// hec_gpu_verify_present_batch): the mask-driven decode with its stores
+// replaced by a compare. Of a stripe's p >= 11 present shards the ten lowest
+// (B) are the inputs, the other r = p - 10 (E) the stored rows; the "check"
+// plan of a mask holds A_m (rows E of the encoding matrix times the inverse
+// of rows B) as r rows of a 4-row table set, plan id = lut[mask], tables at
+// plan id * 200 words. a: the in-place batch (in_* == out_*, only read), the
+// check plan set, masks, lut, and bad_count = the optional count of stripes
+// with a non-zero word. check[s] bit e (e in E) = syn row e is non-zero
+// somewhere in the stripe; the words must be zero at launch. Stripes with
+// p <= 10 are not read and add one to *unchecked (optional).
+struct CheckArgs {
+    ApplyArgs a;
+    uint32_t* check;
+    uint32_t* unchecked = nullptr;
+    // launch_locate_present only (the check kernels never read these):
+    uint32_t* suspects = nullptr;          // one word per stripe, zero at launch
+    const uint32_t* ratio_tabs = nullptr;  // per plan [10][3][kTabWords]: A_m[j][c] / A_m[0][c], j = 1..r-1
+};
+hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream);
+// Pass 2 after launch_check on the same stream: rs104_locate_kernel's method
+// with the stripe's own A_m, ratio tables and row count; stripes whose check
+// word is 0 are not read. Same grid rule as launch_locate.
+hipError_t launch_locate_present(const CheckArgs& v, bool aligned, hipStream_t stream);
+// Use masks of a checked reconstruct (hec_gpu_reconstruct_checked_batch):
+// use[s] = m = present[s] & 0x3FFF when check[s] == 0; m & ~suspects[s] when
+// bit 31 is clear, a shard is named and at least 10 bits remain; else 0x3FFF
+// (the reconstruct's no-op) and *unrepaired (optional) += 1.
+hipError_t launch_use_masks(const uint32_t* present, const uint32_t* check, const uint32_t* suspects, uint32_t* use,
+                            uint32_t* unrepaired, uint32_t n_stripes, hipStream_t stream);
+// Name of the kernel an aligned masked verify of this shard length runs.
+const char* check_kernel_name(uint64_t len);
+
 // splitmix64 byte stream per stripe (bench/test data generator):
 // stripe s: bytes_per_stripe bytes at base + s*stripe_stride, word n (n>=1) =
 // mix(seed_base + s + n*gamma), little endian.

@@ -1,6 +1,8 @@
 // Scrub of a volume's shard files base.ec00 .. base.ec13 (hec_verify_ec_files,
 // and hec_locate_corrupt_ec_files: the same walk with the locate pass, which
-// also names the wrong shard file of each bad block).
+// also names the wrong shard file of each bad block; and
+// hec_locate_corrupt_ec_files_present: that walk over a degraded volume, its
+// missing files treated as erased shards).
 //
 // RS parity is bytewise: byte o of every parity file is a function of byte o
 // of the ten data files, whatever large / small block geometry laid the .dat
@@ -33,6 +35,7 @@ struct Scrub {
     hipStream_t stream = nullptr;
     PinnedBuf<> slot[2];
     DeviceBuf<uint32_t> words_dev[2];
+    DeviceBuf<uint32_t> masks_dev;  // degraded scrub: the volume's present mask, one word per block of a chunk
     PinnedBuf<uint32_t> words_host[2];
     hipEvent_t done[2] = {};
     int init() {
@@ -70,24 +73,41 @@ void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, u
 // locate: every launch is run_locate instead of run_verify, a chunk's suspects
 // words follow its mismatch words at +per_chunk in the same result buffers,
 // and the bad blocks go to sus[] with their suspects word instead of to bad[].
+// degraded (with locate): a missing file is an erased shard, not an error; its
+// row of a slot is neither read into nor read by the kernels, every launch is
+// run_locate_present with the volume's present mask, and the words are the
+// masked calls' (shard-index bits). *present_out (optional) = the files found.
 int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, hec_scrub_bad* bad,
-                         hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks) {
+                         hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks,
+                         bool degraded = false, uint32_t* present_out = nullptr) {
     // files and sizes first: these failures need no device
     Fd fd[N];
     std::string names[N];
     uint64_t size = 0;
+    uint32_t present = 0;
     for (int i = 0; i < N; ++i) {
         names[i] = shard_name(base, i);
         fd[i].fd = ::open(names[i].c_str(), O_RDONLY);
         if (fd[i].fd < 0) {
+            if (errno == ENOENT && degraded) continue;
             if (errno == ENOENT) return fail(HEC_ERR_SHARD_NOT_FOUND, "no shard file " + names[i]);
             return fail_errno(HEC_ERR_IO, "open " + names[i], errno);
         }
+        present |= 1u << i;
     }
+    if (present_out) *present_out = present;
+    const int n_present = __builtin_popcount(present);
+    if (n_present == 0) return fail(HEC_ERR_SHARD_NOT_FOUND, "no shard file " + names[0] + " .. " + names[N - 1]);
+    if (n_present <= K)
+        return fail(HEC_ERR_TOO_FEW_SHARDS_PRESENT, std::to_string(n_present) + " of " + std::to_string(N) +
+                                                        " shard files present, the check needs at least " +
+                                                        std::to_string(K + 1));
+    const int first_present = __builtin_ctz(present);
     for (int i = 0; i < N; ++i) {
+        if (fd[i].fd < 0) continue;
         struct stat st;
         if (::fstat(fd[i].fd, &st) != 0) return fail_errno(HEC_ERR_IO, "stat " + names[i], errno);
-        if (i == 0) size = uint64_t(st.st_size);
+        if (i == first_present) size = uint64_t(st.st_size);
         if (uint64_t(st.st_size) != size)
             return fail_values(HEC_ERR_UNEXPECTED_EC_SHARD_SIZE,
                                "ec shard size expected " + std::to_string(size) + " but actually is " +
@@ -108,6 +128,13 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, h
     const uint64_t cols = per_chunk * block;                               // columns per chunk
     const uint64_t pitch = round_up(std::min(cols, round_up(size, block)), 256);
     HEC_TRY(sc->reserve(size_t(N) * pitch, size_t(per_chunk) * (locate ? 2 : 1)));
+    if (degraded) {
+        HEC_TRY(ensure_check_plans(codec.rs, gd, sc->stream));
+        // one mask word per block, uploaded once per call
+        HEC_TRY(sc->masks_dev.reserve(size_t(per_chunk) * 4));
+        HEC_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc->masks_dev.p), int(present), size_t(per_chunk),
+                                  sc->stream));
+    }
     uint8_t* zs[2] = {pinned_device_ptr(sc->slot[0]), pinned_device_ptr(sc->slot[1])};
     if (!zs[0] || !zs[1]) return fail(HEC_ERR_HIP, "pinned scrub slots are not addressable by the device");
 
@@ -142,6 +169,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, h
         uint8_t* h = sc->slot[q];
         parallel_io_for(size_t(N * pieces), uint64_t(N) * len, [&](size_t t) {
             const int i = int(t / pieces);
+            if (fd[i].fd < 0) return;  // an erased shard: its row stays unread
             const uint64_t p0 = (t % pieces) * kReadPiece;
             read_exact(err, fd[i].fd, names[i], h + uint64_t(i) * pitch + p0, std::min(kReadPiece, len - p0),
                        off + p0);
@@ -155,6 +183,9 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, h
         auto launch = [&](uint64_t first, uint64_t blen, uint64_t n) -> int {
             const uint8_t* d = zs[q] + first * block;
             const uint8_t* p = d + uint64_t(K) * pitch;
+            if (degraded)
+                return run_locate_present(*gd, d, block, pitch, blen, uint32_t(n), sc->masks_dev, wd + first,
+                                          wd + per_chunk + first, nullptr, nullptr, sc->stream);
             if (locate)
                 return run_locate(*gd, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first,
                                   wd + per_chunk + first, nullptr, sc->stream);
@@ -206,6 +237,15 @@ int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, 
     uint64_t block;
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
     return hec::verify_ec_files_impl(base_filename, block, true, nullptr, bad, cap, n_bad, n_blocks);
+}
+
+int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
+                                        size_t cap, size_t* n_bad, uint64_t* n_blocks, uint32_t* present_mask) {
+    if (present_mask) *present_mask = 0;
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, true, nullptr, bad, cap, n_bad, n_blocks, true,
+                                     present_mask);
 }
 
 }  // extern "C"

@@ -106,6 +106,29 @@ def locate_corrupt_ec_files(base_filename: str, block_size: int = 0, cap: int = 
              for i in range(got)])
 
 
+def locate_corrupt_ec_files_present(base_filename: str, block_size: int = 0, cap: int = 1024):
+    """locate_corrupt_ec_files for a degraded volume
+    (hec_locate_corrupt_ec_files_present): missing ``.ecNN`` files are erased
+    shards. Returns ``(n_blocks, n_bad, bad, present_mask)``; entries are
+    ``(offset, length, check, suspects)`` with bits by file index 0..13 (the
+    masked verify's and locate's words). Needs 11 or more files
+    (``ErasureCoding(TooFewShardsPresent)`` below that, ``ShardNotFound`` with none). Reads
+    only. To repair: when blocks name files and bit 31 is clear everywhere,
+    delete the named files too (at most four missing in all), call
+    ``rebuild_ec_files``, scrub again."""
+    if cap < 0:
+        raise ValueError("negative cap")
+    bad = (_ScrubSuspect * cap)() if cap else None
+    n_bad, n_blocks, present = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    check_ec(lib.hec_locate_corrupt_ec_files_present(base_filename.encode(), block_size, bad, cap,
+                                                     ctypes.byref(n_bad), ctypes.byref(n_blocks),
+                                                     ctypes.byref(present)))
+    got = min(cap, n_bad.value)
+    return (int(n_blocks.value), int(n_bad.value),
+            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
+             for i in range(got)], int(present.value))
+
+
 # --- EC volume files around the shards (helyim-ec host-side byte formats) ---
 
 def write_sorted_file_from_index(base_filename: str, ext: str = ".ecx") -> None:

@@ -300,6 +300,118 @@ int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_
                          uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_present_masks,
                          uint32_t* d_unrepaired, void* stream);
 
+/* ---- degraded scrub: check and locate with shards missing (RS(10,4)) -------
+ * The calls above need all 14 shards. These take hec_gpu_reconstruct_batch's
+ * in-place layout and d_present_masks (bit i set = shard i present) and use
+ * the redundancy a degraded stripe still has. Definitions, for stripe s:
+ *   m = d_present_masks[s] & 0x3FFF, p = popcount(m), r = p - 10; for p >= 11
+ *   B    = the ten lowest set bits of m (upstream's "first data_shards present"
+ *          rule: the shards hec_gpu_reconstruct_batch decodes from);
+ *   E    = the remaining r set bits, ascending (the spare shards);
+ *   A_m  = (r x 10) rows E of the encoding matrix (hec_rs_matrix) times the
+ *          inverse of its rows B: what the reconstruct would apply to B had E
+ *          been erased;
+ *   H_m  = [A_m | I_r], columns labelled by shard ids B then E;
+ *   syn(o) = for byte column o < shard_len, the stored bytes of E XOR A_m
+ *          times the stored bytes of B (r bytes).
+ * The present shards form an MDS [p,10] code of distance r + 1. For each of
+ * the 469 masks with 11..13 shards present no entry of A_m is zero and, for
+ * r >= 2, no two columns of H_m are proportional (tests/test_check_model.py),
+ * so one wrong shard is named uniquely:
+ *   shards lost  r   one corrupt survivor is
+ *   0            4   detected and named (hec_gpu_locate_corrupt_batch's case)
+ *   1            3   detected and named
+ *   2            2   detected and named
+ *   3            1   detected
+ * Any other codec: HEC_ERR_INVALID_ARGUMENT before any device work, the
+ * detail says "RS(10,4) only". All are asynchronous on `stream` with no host
+ * synchronisation (the first call on a device uploads the plan tables and
+ * waits for that copy once).
+ *
+ * Masked verify. d_check[s] gets bit e set, for e in E, when row e of syn is
+ * non-zero in at least one column: bits are by SHARD INDEX 0..13, so with the
+ * full mask 0x3FFF the word is hec_gpu_verify_batch's shifted left by 10. A
+ * stripe with p <= 10 has no spare shard and nothing to check: its word is 0,
+ * it is not read, and it adds one to *d_unchecked (device word, optional,
+ * accumulated). *d_bad_stripes (optional, accumulated): plus one per stripe
+ * with a non-zero word, exactly once. Words [0, n_stripes) are cleared on
+ * `stream` first; no other byte anywhere is written, absent shards are never
+ * read, and bytes at or past shard_len take no part. Argument errors are
+ * hec_gpu_reconstruct_batch's plus a null d_present_masks / d_check, all
+ * before device work; n_stripes == 0 returns HEC_OK and writes nothing.
+ * 16-byte-aligned bases and strides with shard_len a multiple of 2 KiB below
+ * 4 GiB run the 8-byte-per-lane kernel, everything else a grid-stride kernel
+ * (hec_check_kernel_name).
+ * Measured on one MI355X, 4096 x 1 MiB stripes, medians of 9 alternating
+ * rounds (tools/bench_check.py, profiles/degraded/bench_check.json), bytes
+ * read per second: with 1 shard of every stripe erased 7.79 ms (13 shards
+ * read, 7.17 TB/s, 0.90 of 8 TB/s), with 2 erased 6.92 ms (7.45 TB/s, 0.93),
+ * with 3 erased 6.39 ms (7.39 TB/s, 0.92), with full masks 9.23 ms (6.52 TB/s,
+ * 0.81) against hec_gpu_verify_batch's bit-sliced 8.18 ms (7.35 TB/s, 0.92):
+ * with every shard present call that one. The route a degraded batch had
+ * before, hec_gpu_reconstruct_batch then hec_gpu_verify_batch, takes 15.91 /
+ * 16.69 / 17.45 ms with 1 / 2 / 3 erased; the masked verify was faster in
+ * every round (0.48..0.50 of it with 1 erased). */
+int hec_gpu_verify_present_batch(const hec_rs_t* rs, const uint8_t* d_shards, uint64_t stripe_stride,
+                                 uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                 const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_bad_stripes,
+                                 uint32_t* d_unchecked, void* stream);
+
+/* Masked locate: the masked verify (d_check, d_bad_stripes, d_unchecked are
+ * exactly its), then a second kernel that reads only the flagged stripes.
+ * Contract of d_suspects[s], per byte column o < shard_len:
+ *   - syn(o) == 0: the column contributes nothing;
+ *   - r >= 2 and there is a present shard c and a byte v != 0 with
+ *     syn(o) == v * H_m[:,c] (such a c is unique): bit c is set;
+ *   - any other non-zero column, and every non-zero column when r == 1:
+ *     HEC_SUSPECT_UNEXPLAINED (bit 31).
+ * With the full mask both words equal hec_gpu_locate_corrupt_batch's (d_check
+ * = its d_mismatch shifted left by 10). Guarantees, per byte column:
+ *   r = 4: as hec_gpu_locate_corrupt_batch;
+ *   r = 3: one wrong shard is named; two wrong shards give bit 31; an intact
+ *          shard is never named while at most two are wrong;
+ *   r = 2: one wrong shard is named; two or more wrong shards in ONE column
+ *          are outside any guarantee and may name an intact shard;
+ *   r = 1: detection only (bit 31 on every dirty stripe).
+ * d_check and d_suspects must be distinct arrays that overlap neither each
+ * other nor the masks nor any shard (not checked). Both are overwritten in
+ * [0, n_stripes); no other byte is written. Argument errors as the masked
+ * verify plus a null d_suspects. */
+int hec_gpu_locate_corrupt_present_batch(const hec_rs_t* rs, const uint8_t* d_shards, uint64_t stripe_stride,
+                                         uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                         const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_suspects,
+                                         uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream);
+
+/* Checked reconstruct: the rebuild that does not launder corruption.
+ * hec_gpu_reconstruct_batch decodes from the ten lowest present shards on
+ * faith; one silently corrupt survivor among them is multiplied into every
+ * rebuilt shard, and a later scrub that finds the stripe inconsistent has
+ * more wrong shards to explain than it can name. This call looks at the spare
+ * shards first. In stream order:
+ *  (1) masked locate into d_check / d_suspects, as above;
+ *  (2) d_use_masks[s] = m when d_check[s] == 0 (clean stripes, and unchecked
+ *      stripes with p <= 10: exactly hec_gpu_reconstruct_batch's behaviour);
+ *      = m & ~d_suspects[s] when bit 31 is clear, at least one shard is named
+ *      and at least 10 bits remain (the named shards are treated as erased);
+ *      otherwise 0x3FFF: the stripe is left byte for byte as it was, its
+ *      holes included, and *d_unrepaired (device word, optional, accumulated)
+ *      gets plus one;
+ *  (3) hec_gpu_reconstruct_batch with d_use_masks; *d_bad_stripes is its count
+ *      (stripes whose use mask has fewer than 10 bits).
+ * Only shards in ~d_use_masks[s] & 0x3FFF of a stripe are written; the caller
+ * reads d_use_masks to learn what was rebuilt. d_present_masks is only read.
+ * The call trusts the guarantees above, r = 2's limit included (two wrong
+ * shards in one column of a stripe with two spares may name, and so rebuild,
+ * an intact shard from corrupt ones); hec_gpu_verify_batch afterwards is the
+ * proof. d_check, d_suspects and d_use_masks hold n_stripes words each, are
+ * overwritten, and must be distinct arrays that overlap nothing else.
+ * Argument errors as the masked locate plus a null d_use_masks. */
+int hec_gpu_reconstruct_checked_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                      uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                      const uint32_t* d_present_masks, uint32_t* d_check, uint32_t* d_suspects,
+                                      uint32_t* d_use_masks, uint32_t* d_bad_stripes, uint32_t* d_unrepaired,
+                                      void* stream);
+
 /* ---- host-memory batches (the path helyim runs: bytes start and end in host
  * memory, encoder.rs:169-195 / 263-304) -------------------------------------
  * Same strided layout as above but on HOST pointers; synchronous on return.
@@ -436,6 +548,26 @@ typedef struct hec_scrub_suspect {
 } hec_scrub_suspect;
 int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                                 size_t* n_bad, uint64_t* n_blocks);
+/* hec_locate_corrupt_ec_files for a degraded volume: a missing .ecNN (ENOENT)
+ * is an erased shard, not an error. *present_mask (optional) reports which
+ * files were found (bit i = base.ec(i)). Each entry's parity_mask field
+ * carries the block's check word and its suspects field the masked-locate
+ * word (hec_gpu_locate_corrupt_present_batch's contracts, bits by file index
+ * 0..13); with all 14 files present the entries equal
+ * hec_locate_corrupt_ec_files's with parity_mask << 10. Only present files are
+ * opened and read, and none is written. Errors, all before device work: no
+ * file present -> HEC_ERR_SHARD_NOT_FOUND; 1 to 10 present ->
+ * HEC_ERR_TOO_FEW_SHARDS_PRESENT (the detail gives the count); present sizes
+ * not all equal -> HEC_ERR_UNEXPECTED_EC_SHARD_SIZE with hec_last_error_values
+ * = (size of the first present file, size of the first that differs). Block,
+ * cap and bad rules are unchanged.
+ * Recipe for a degraded volume: scrub it with this call; if blocks name files
+ * and bit 31 is clear everywhere, delete the named files too (at most four
+ * missing in total); then hec_rebuild_ec_files; then scrub again. With bit 31
+ * set somewhere (always so with three files missing) the volume has damage
+ * this library cannot attribute: rebuild nothing from it. */
+int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
+                                        size_t cap, size_t* n_bad, uint64_t* n_blocks, uint32_t* present_mask);
 
 /* ---- EC volume files around the shards (host-side byte formats) ----------- */
 /* write_sorted_file_from_index(base, ext) (encoder.rs:21-37): replay base.idx
@@ -594,6 +726,8 @@ const char* hec_encode_kernel_name(uint64_t shard_len);
 const char* hec_decode_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned RS(10,4) device batch verify. */
 const char* hec_verify_kernel_name(uint64_t shard_len);
+/* Same for a 16-byte-aligned hec_gpu_verify_present_batch (masked verify). */
+const char* hec_check_kernel_name(uint64_t shard_len);
 /* Kernel hec_gpu_encode_ragged (decode = 0) or hec_gpu_reconstruct_ragged
  * (decode != 0) runs on these descriptors: the same choice the launch makes
  * (static string). */

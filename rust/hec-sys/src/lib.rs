@@ -156,6 +156,20 @@ extern "C" {
     pub fn hec_gpu_repair_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64, shard_stride: u64,
                                 shard_len: u64, n_stripes: u32, d_mismatch: *mut u32, d_suspects: *mut u32,
                                 d_present_masks: *mut u32, d_unrepaired: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_verify_present_batch(rs: *const hec_rs_t, d_shards: *const u8, stripe_stride: u64,
+                                        shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                        d_present_masks: *const u32, d_check: *mut u32, d_bad_stripes: *mut u32,
+                                        d_unchecked: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_locate_corrupt_present_batch(rs: *const hec_rs_t, d_shards: *const u8, stripe_stride: u64,
+                                                shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                                d_present_masks: *const u32, d_check: *mut u32,
+                                                d_suspects: *mut u32, d_bad_stripes: *mut u32,
+                                                d_unchecked: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_reconstruct_checked_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64,
+                                             shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                             d_present_masks: *const u32, d_check: *mut u32, d_suspects: *mut u32,
+                                             d_use_masks: *mut u32, d_bad_stripes: *mut u32,
+                                             d_unrepaired: *mut u32, stream: *mut c_void) -> c_int;
     pub fn hec_host_verify_batch(rs: *const hec_rs_t, h_data: *const u8, data_stripe_stride: u64,
                                  data_shard_stride: u64, h_parity: *const u8, parity_stripe_stride: u64,
                                  parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
@@ -191,6 +205,9 @@ extern "C" {
                                n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
     pub fn hec_locate_corrupt_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_suspect,
                                        cap: usize, n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
+    pub fn hec_locate_corrupt_ec_files_present(base_filename: *const c_char, block_size: u64,
+                                               bad: *mut hec_scrub_suspect, cap: usize, n_bad: *mut usize,
+                                               n_blocks: *mut u64, present_mask: *mut u32) -> c_int;
     pub fn hec_write_sorted_file_from_index(base_filename: *const c_char, ext: *const c_char) -> c_int;
     pub fn hec_rebuild_ecx_file(base_filename: *const c_char) -> c_int;
     pub fn hec_save_volume_info(filename: *const c_char, version: u32) -> c_int;
@@ -242,5 +259,6 @@ extern "C" {
     pub fn hec_encode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_decode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_check_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_ragged_kernel_name(descs: *const hec_stripe_desc, n_stripes: u32, decode: c_int) -> *const c_char;
 }
