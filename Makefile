@@ -7,7 +7,7 @@ SRC := $(wildcard helyim_amd/csrc/*.cpp) $(wildcard helyim_amd/csrc/*.hip)
 HDR := $(wildcard helyim_amd/csrc/*.hpp) $(wildcard helyim_amd/csrc/*.inc) include/hec.h
 OBJ := $(patsubst helyim_amd/csrc/%,build/obj/%.o,$(SRC))
 
-all: helyim_amd/libhec.so oracle build/cabi_bench build/membench_calib
+all: helyim_amd/libhec.so oracle build/cabi_bench build/membench_calib build/variants/libhec_smallgrid.so
 
 helyim_amd/libhec.so: $(OBJ)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $(OBJ) -lpthread
@@ -35,17 +35,24 @@ build/membench_calib: tools/membench.hip include/hec.h helyim_amd/libhec.so
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -DMEMBENCH_WITH_HEC -o $@ $< -Lhelyim_amd -lhec \
 	    -Wl,-rpath,'$$ORIGIN/../helyim_amd'
 
-# A/B method check: a byte-identical rebuild of the kernel file as a separate
-# library (HEC_LIB_PATH=build/variants/libhec_null.so), to measure the spread
-# of alternating-process A/Bs between two library builds (tools/tune.py).
-VARIANTS := null
+# Kernel variants: rs_kernels.hip rebuilt with other flags and linked with the
+# product's other objects into a library of its own (HEC_LIB_PATH loads one).
+#  * null: a byte-identical rebuild, to measure the spread of
+#    alternating-process A/Bs between two library builds (tools/tune.py).
+#  * smallgrid: tiny launch limits, so the GPU suites' small batches go in
+#    several stripe ranges, grid-stride iterations and mask rounds
+#    (tests/test_gpu_small_grid.py). 100 is no multiple of 8, 3 or 5; 4
+#    workgroups make the mask kernels go round after 1024 stripes. Part of
+#    `all`: the tests need it.
+VARIANTS := null smallgrid
+VFLAGS_null := -DHEC_NULL_VARIANT=1
+VFLAGS_smallgrid := -DHEC_MAX_LAUNCH_BLOCKS=100 -DHEC_LOCATE_MAX_BLOCKS=4
+VOBJ := $(filter-out build/obj/rs_kernels.hip.o,$(OBJ))
 variants: $(foreach v,$(VARIANTS),build/variants/libhec_$(v).so)
-build/variants/libhec_%.so: $(SRC) $(HDR)
+build/variants/libhec_%.so: $(SRC) $(HDR) $(VOBJ)
 	@mkdir -p build/variants/$*
 	$(HIPCC) $(HIPFLAGS) $(VFLAGS_$*) -c helyim_amd/csrc/rs_kernels.hip -o build/variants/$*/rs_kernels.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ build/variants/$*/rs_kernels.o \
-	    $(filter-out build/obj/rs_kernels.hip.o,$(OBJ)) -lpthread
-VFLAGS_null := -DHEC_NULL_VARIANT=1  # identical code: measures the A/B method itself
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ build/variants/$*/rs_kernels.o $(VOBJ) -lpthread
 
 clean:
 	rm -rf build helyim_amd/libhec.so

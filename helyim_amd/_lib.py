@@ -10,7 +10,8 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# HEC_LIB_PATH: measurement builds only (tools/tune.py loads kernel variants).
+# HEC_LIB_PATH: measurement and test builds only (tools/tune.py and
+# tests/test_gpu_small_grid.py load the Makefile's kernel variants).
 LIB_PATH = os.environ.get("HEC_LIB_PATH") or os.path.join(_HERE, "libhec.so")
 
 if not os.path.exists(LIB_PATH):

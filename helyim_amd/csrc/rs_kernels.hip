@@ -1190,7 +1190,11 @@ __global__ __launch_bounds__(kThreads) void rs104_check_stride_kernel(CheckArgs 
 constexpr const char* kFastCheckName = "rs104_check_kernel<8 B per lane> (table lookup)";
 constexpr const char* kStrideCheckName = "rs104_check_stride_kernel (table lookup)";
 
-static bool check_fast(uint64_t len) { return len % kNarrowChunk == 0 && len <= 0xFFFFFFFFull; }
+// The fast check takes shard lengths that are a multiple of 2 KiB below 4 GiB
+// whose chunks fit one launch (launch_check's stripe ranges hold whole stripes).
+static bool check_fast(uint64_t len) {
+    return len % kNarrowChunk == 0 && len <= 0xFFFFFFFFull && len / kNarrowChunk <= kMaxLaunchBlocks;
+}
 
 const char* check_kernel_name(uint64_t len) {
     if (len == 0) return kNoLaunch;
@@ -1417,3 +1421,13 @@ hipError_t launch_fill_splitmix(uint8_t* base, uint64_t stripe_stride, uint64_t 
 }
 
 }  // namespace hec
+
+#ifdef HEC_MAX_LAUNCH_BLOCKS
+// Test builds only (rs_kernels.hpp): the limits this library was compiled
+// with, so a test can prove that the variant it loaded is the one it meant.
+// The shipped library does not export this.
+extern "C" void hec_test_launch_limits(uint64_t* max_launch_blocks, uint32_t* locate_max_blocks) {
+    *max_launch_blocks = hec::kMaxLaunchBlocks;
+    *locate_max_blocks = hec::kLocateMaxBlocks;
+}
+#endif

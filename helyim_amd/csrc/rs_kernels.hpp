@@ -25,7 +25,17 @@ constexpr uint32_t kNoPlan = 0xFFFFFFFFu;   // mask LUT entry: too few shards pr
 constexpr int kThreads = 256;               // 4 waves of 64 lanes
 // Workgroups per launch: the dispatch packet's grid is 32-bit in work-items,
 // so 2^23 workgroups (2^31 work-items at 256 threads) keeps every launch legal.
+// HEC_MAX_LAUNCH_BLOCKS / HEC_LOCATE_MAX_BLOCKS: test builds only (the
+// Makefile's smallgrid variant), so that batches of a few hundred stripes go
+// in several launches, grid-stride iterations and mask rounds. The shipped
+// library defines neither. Only rs_kernels.hip reads the two limits, the one
+// file a variant recompiles.
+#ifdef HEC_MAX_LAUNCH_BLOCKS
+constexpr uint64_t kMaxLaunchBlocks = HEC_MAX_LAUNCH_BLOCKS;
+#else
 constexpr uint64_t kMaxLaunchBlocks = 1ull << 23;
+#endif
+static_assert(kMaxLaunchBlocks >= 1 && kMaxLaunchBlocks <= (1ull << 23), "one launch: 1 to 2^23 workgroups");
 constexpr int kVecBytes = 16;               // one dwordx4 per lane per access
 
 struct ApplyArgs {
@@ -145,7 +155,12 @@ hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t
 // read. A grid-stride kernel over (stripe, 4 KiB chunk) items on at most
 // kLocateMaxBlocks workgroups (a memory-bound grid-stride loop wants a few
 // workgroups per CU, not one per item; speed only, unmeasured).
+#ifdef HEC_LOCATE_MAX_BLOCKS
+constexpr uint32_t kLocateMaxBlocks = HEC_LOCATE_MAX_BLOCKS;
+#else
 constexpr uint32_t kLocateMaxBlocks = 2048;
+#endif
+static_assert(kLocateMaxBlocks >= 1 && kLocateMaxBlocks <= (1u << 23), "locate grid: 1 to 2^23 workgroups");
 constexpr uint32_t kSuspectUnexplained = 0x80000000u;  // hec.h HEC_SUSPECT_UNEXPLAINED
 hipError_t launch_locate(const VerifyArgs& v, bool aligned, hipStream_t stream);
 

@@ -1,7 +1,8 @@
 // Check of helyim_amd/csrc/launch_split.hpp, the arithmetic that cuts a launch
 // of more than `limit` workgroups into pieces: block launches of a ragged
 // batch and stripe ranges of a strided one. Small limits are walked piece by
-// piece; at the production limit (2^23) the pieces are counted arithmetically
+// piece; at the production limit (2^23) and at the smallgrid variant's (100)
+// the pieces of long splits are counted arithmetically
 // and the first, the last and sampled middle ones are checked against 64-bit
 // expectations, so a 32-bit intermediate that wraps shows as a wrong field.
 // For every split: the pieces are in order and cover [0, n) exactly once, each
@@ -85,17 +86,21 @@ int main() {
             for (uint64_t per = 1; per <= 9 && per <= limit; ++per)  // the callers split only when per <= limit
                 if (walk(n, hec::stripes_per_launch(limit, per), per, limit)) return 1;
         }
-    const uint64_t limit = uint64_t(1) << 23;  // kMaxLaunchBlocks
-    const uint64_t counts[] = {1, 2, limit, limit + 1, 0xFFFFFFFFull};
-    for (uint64_t n : counts) {
-        if (sample(n, limit, 1, limit)) return 1;  // block launches
-        for (uint64_t per : {uint64_t(1), limit - 1, limit}) {
-            const uint64_t step = hec::stripes_per_launch(limit, per);
-            if (step != limit / per || step < 1) {
-                std::printf("FAIL stripes_per_launch(%llu, %llu)\n", (unsigned long long)limit, (unsigned long long)per);
-                return 1;
+    // kMaxLaunchBlocks: the product's 2^23, and the 100 of the Makefile's
+    // smallgrid variant (no multiple of 8, 3 or 5: uneven eighths and ranges)
+    for (uint64_t limit : {uint64_t(1) << 23, uint64_t(100)}) {
+        const uint64_t counts[] = {1, 2, limit - 1, limit, limit + 1, 3 * limit + 7, 0xFFFFFFFFull};
+        for (uint64_t n : counts) {
+            if (sample(n, limit, 1, limit)) return 1;  // block launches
+            for (uint64_t per : {uint64_t(1), uint64_t(3), uint64_t(5), limit / 2 + 1, limit - 1, limit}) {
+                const uint64_t step = hec::stripes_per_launch(limit, per);
+                if (step != limit / per || step < 1) {
+                    std::printf("FAIL stripes_per_launch(%llu, %llu)\n", (unsigned long long)limit,
+                                (unsigned long long)per);
+                    return 1;
+                }
+                if (sample(n, step, per, limit)) return 1;
             }
-            if (sample(n, step, per, limit)) return 1;
         }
     }
     std::printf("ok %ld pieces\n", checked);

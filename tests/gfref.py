@@ -6,7 +6,8 @@ rs_oracle.build_matrix through rs_oracle.mul_rows (one 256-entry table lookup
 per coefficient) over the flattened batch. torch_encode is the same lookup in
 torch, for batches that live on the device and are too large to copy back: the
 oracle's 256 x 256 product table indexed with the data bytes, XORed over the
-inputs, a chunk of stripes at a time.
+inputs, a chunk of stripes at a time. device_codewords is a batch of seeded
+random stripes with torch_encode's parity, built on the device.
 
 all_masks_case builds the image the every-mask sweeps share: 2^(k+m) stripes,
 stripe s with present mask s. It needs no reconstruct oracle: upstream (and
@@ -71,6 +72,17 @@ def torch_encode(k: int, m: int, data, out=None, max_index_bytes: int = 1 << 29)
         out[s0:s1] = acc.permute(1, 0, 2)
         del acc
     return out
+
+
+def device_codewords(k: int, m: int, S: int, L: int, seed: int):
+    """[S, k + m, L] uint8 on the current device: seeded random data shards
+    and torch_encode's parity (batches too large to encode on the host)."""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    t = torch.empty((S, k + m, L), dtype=torch.uint8, device="cuda")
+    t[:, :k] = torch.randint(0, 256, (S, k, L), dtype=torch.uint8, device="cuda", generator=g)
+    torch_encode(k, m, t[:, :k], out=t[:, k:])
+    return t
 
 
 class MaskTables(NamedTuple):

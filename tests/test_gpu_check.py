@@ -277,26 +277,59 @@ def test_shard_end(gpu):
     assert results[0] == results[1]
 
 
+LAYOUT_MASKS = [R3, R2, R1, ALL, lost(13), lost(0, 1), 0x3FF, R3]
+
+
+def layouts_batch(L, kind, masks=LAYOUT_MASKS):
+    """Every r, flips at the ends of chunks in all stripes but the last; bits
+    of `masks` above bit 13 take no part in where the shards are."""
+    b = Batch(clean_stripes(len(masks), L), masks, kind)
+    positions = sorted({p for p in (0, 2047, 2048, 4095, 4096, L - 1) if p < L})
+    for s, m in enumerate(masks[:-1]):
+        B, E = C.split(m)
+        shard = (B + E)[(4 * s + 1) % len(B + E)]
+        for n, p in enumerate(positions):
+            b.shard(s, shard)[p] ^= 0x11 * (n + 1)
+    return b
+
+
 @pytest.mark.parametrize("L", LENGTHS)
 def test_layouts_give_the_same_words(gpu, L):
     """Odd base and odd strides, and the shard-major layout, against the
     aligned run, over a batch with every r and flips at the ends of chunks."""
     import helyim_amd as H
     rs = H.ReedSolomon(10, 4)
-    masks = [R3, R2, R1, ALL, lost(13), lost(0, 1), 0x3FF, R3]
-    S = len(masks)
-    positions = sorted({p for p in (0, 2047, 2048, 4095, 4096, L - 1) if p < L})
     runs = []
     for kind in ("aligned", "odd", "shard-major"):
-        b = Batch(clean_stripes(S, L), masks, kind)
-        for s, m in enumerate(masks[:-1]):
-            B, E = C.split(m)
-            shard = (B + E)[(4 * s + 1) % len(B + E)]
-            for n, p in enumerate(positions):
-                b.shard(s, shard)[p] ^= 0x11 * (n + 1)
-        runs.append(check_batch(rs, b, note=(kind, L)))
+        runs.append(check_batch(rs, layouts_batch(L, kind), note=(kind, L)))
         assert runs[-1][0][-1] == 0 and runs[-1][0][6] == 0 and all(runs[-1][0][:6])
     assert runs[0] == runs[1] == runs[2]
+
+
+def with_stray_bits(masks, seed):
+    """Random bits 14..30 and bit 31 ORed into every mask: hec.h defines the
+    present mask of a stripe as d_present_masks[s] & 0x3FFF."""
+    rng = np.random.default_rng(seed)
+    out = [m | int(rng.integers(1, 1 << 17)) << 14 | 1 << 31 for m in masks]
+    assert all(o & ALL == m and o >> 14 for o, m in zip(out, masks))
+    return out
+
+
+@pytest.mark.parametrize("L", LENGTHS)
+def test_stray_mask_bits_change_nothing(gpu, L):
+    """The batches of test_layouts_give_the_same_words (the fast and the
+    grid-stride kernels, aligned and odd) with bits 14..31 set in every mask:
+    the model's words for the masks & 0x3FFF, and words, counts and footprint
+    equal to the run with clean masks. A kernel that indexes its plan table
+    or counts present shards with the raw word gives other words or faults."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    stray = with_stray_bits(LAYOUT_MASKS, L)
+    for kind in ("aligned", "odd"):
+        # check_batch: both calls' words and counts against the model, the footprint
+        runs = [check_batch(rs, layouts_batch(L, kind, masks), note=(kind, L, masks is stray))
+                for masks in (LAYOUT_MASKS, stray)]
+        assert runs[0] == runs[1] and any(runs[0][0]), (kind, L)
 
 
 @pytest.mark.parametrize("L", [8192 + 2048, 4096 + 16])
@@ -443,8 +476,9 @@ def test_shard_len_near_4gib(gpu, L):
 
 
 # ---- checked reconstruct ---------------------------------------------------------
-@pytest.mark.parametrize("L,kind", [(8192 + 2048, "aligned"), (1000, "aligned"), (1000, "odd")])
-def test_checked_reconstruct(gpu, L, kind):
+def checked_reconstruct(L, kind, stray=False):
+    """stray: the call is given the masks with bits 14..31 set; everything
+    expected is built from the masks & 0x3FFF."""
     import torch
     import helyim_amd as H
     rs = H.ReedSolomon(10, 4)
@@ -462,6 +496,7 @@ def test_checked_reconstruct(gpu, L, kind):
     ]
     S = len(cases)
     masks = [m for m, _ in cases]
+    given = with_stray_bits(masks, L) if stray else masks
     clean = clean_stripes(S, L, seed=3)
     b = Batch(clean, masks, kind)
     for s, (_, flips) in enumerate(cases):
@@ -484,7 +519,7 @@ def test_checked_reconstruct(gpu, L, kind):
     la = b.layout
     dev = torch.from_numpy(b.arena).cuda()
     chk, sus, use = words(3, S)
-    mt = torch.tensor(np.array(masks + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
+    mt = torch.tensor(np.array(given + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
     bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
     left = torch.full((1,), 5, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -500,7 +535,7 @@ def test_checked_reconstruct(gpu, L, kind):
     F.assert_unchanged([expected.arena], [after], b.stripes)
     assert read_words(chk, S) == want_chk and read_words(sus, S) == want_sus
     assert read_words(use, S) == want_use, hexes(read_words(use, S))
-    assert mt.cpu().numpy().view(np.uint32).tolist() == masks + [0x3FFF]
+    assert mt.cpu().numpy().view(np.uint32).tolist() == given + [0x3FFF]
     assert int(left.item()) == 5 + want_left and int(bad.item()) == 7 + 1
     for s in range(S):
         for i in range(14):
@@ -514,6 +549,19 @@ def test_checked_reconstruct(gpu, L, kind):
     assert rc == 0
     torch.cuda.synchronize()
     assert [w == 0 for w in read_words(ver, S)] == [s in repaired or s == 9 for s in range(S)]
+
+
+@pytest.mark.parametrize("L,kind", [(8192 + 2048, "aligned"), (1000, "aligned"), (1000, "odd")])
+def test_checked_reconstruct(gpu, L, kind):
+    checked_reconstruct(L, kind)
+
+
+@pytest.mark.parametrize("L,kind", [(8192 + 2048, "aligned"), (1000, "odd")])
+def test_checked_reconstruct_with_stray_mask_bits(gpu, L, kind):
+    """Bits 14..31 set in every present mask: the check, the locate, the use
+    masks (built from m & 0x3FFF, so none of the stray bits may come through)
+    and the reconstruct give what the clean masks give."""
+    checked_reconstruct(L, kind, stray=True)
 
 
 def test_checked_reconstruct_python_mirror(gpu):
@@ -539,6 +587,167 @@ def test_checked_reconstruct_python_mirror(gpu):
     assert sus.cpu().tolist() == [0, 1 << 3] and use.cpu().tolist() == [lost(12), lost(12, 3)]
     assert chk.cpu().tolist() == [0, 1 << 10 | 1 << 11 | 1 << 13] and int(left.item()) == 0
     assert torch.equal(good_copy.cpu(), clean)
+
+
+# ---- big batches: built, corrupted and compared on the device ----------------------
+MASK_ROUND = 2048 * 256  # stripes one round of the mask kernels takes: 2048 workgroups of 256 lanes
+LAUNCH_LIMIT = 1 << 23   # workgroups of one launch, and of one pass of a grid-stride loop
+CYCLE = [ALL, R3, R2, R1, 0x3FF]  # r = 4, 3, 2, 1 and p = 10, over the whole batch
+
+
+def edge_hits(edge):
+    """stripe -> (present mask, flips [(shard, pos, value)], suspects word by
+    construction) of a batch of edge + 5 stripes of 16 bytes: one-shard flips
+    (named and rebuilt) in the first and last stripe, on both sides of a wave
+    and of `edge`; same-column pairs and one-spare stripes (left alone) on both
+    sides of `edge` and in the last, partial wave; clean stripes with nine
+    shards (skipped and counted by the reconstruct)."""
+    S = edge + 5
+    assert edge % 64 == 0 and edge // 2 > 1000
+    return {
+        0: (lost(13), [(2, 7, 0x21)], 1 << 2),
+        77: (lost(0, 1, 2, 3, 4), [], 0),
+        255: (R2, [(13, 0, 0x01)], 1 << 13),
+        256: (ALL, [(11, 15, 0x80)], 1 << 11),
+        1000: (R1, [(5, 4, 0x01)], UNEXPLAINED),
+        edge // 2 + 1: (lost(1, 10), [(12, 9, 0x5A)], 1 << 12),
+        edge - 3: (lost(9, 10, 11, 12, 13), [], 0),
+        edge - 2: (R3, [(4, 5, 0x33), (8, 5, 0x44)], UNEXPLAINED),
+        edge - 1: (R3, [(9, 3, 0xFF)], 1 << 9),
+        edge: (R2, [(1, 8, 0x10)], 1 << 1),
+        edge + 1: (R3, [(0, 11, 0x07), (13, 11, 0x70)], UNEXPLAINED),
+        S - 3: (ALL, [(6, 9, 0x11), (12, 9, 0x22)], UNEXPLAINED),
+        S - 2: (R1, [(0, 0, 0x01)], UNEXPLAINED),
+        S - 1: (lost(5), [(0, 15, 0x42)], 1 << 0),
+    }
+
+
+def i32(values):
+    import torch
+    return torch.tensor(np.array(values, dtype=np.uint32).view(np.int32), device="cuda")
+
+
+def expect_words(S, idx, values, rest=0):
+    """[S + 1] words on the device: `rest` (a value or an [S] tensor), `values`
+    at the stripes idx, the sentinel at S -- what words(n, S) must become."""
+    import torch
+    t = torch.empty(S + 1, dtype=torch.int32, device="cuda")
+    t[:S] = rest
+    t[idx] = i32(values)
+    t[S] = SENTINEL_WORD
+    return t
+
+
+def assert_words(got, want, what):
+    import torch
+    if not torch.equal(got, want):
+        at = torch.nonzero(got != want).flatten()[:8].cpu().tolist()
+        pytest.fail(f"{what}: wrong at {at}: got {hexes(got[at].cpu().numpy().view(np.uint32))}, "
+                    f"expected {hexes(want[at].cpu().numpy().view(np.uint32))}")
+
+
+def checksum(t):
+    """One device reduction over every byte of a contiguous tensor."""
+    import torch
+    return int(t.view(torch.int64).sum().item())
+
+
+def masked_scrub_big(edge):
+    """The masked verify, the masked locate and the checked reconstruct over
+    edge + 5 stripes of 16 bytes with CYCLE's masks and edge_hits' corruption.
+    Expected words of the dirty stripes from check_model on those stripes, and
+    by construction; every other stripe is a codeword of gfref's torch twin
+    with its absent shards holding FILL, so its words are zero, its use mask
+    its present mask and its image the codeword: whole arrays and the whole
+    image are compared on the device."""
+    import torch
+    import gfref
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    S, L = edge + 5, 16
+    hits = edge_hits(edge)
+    order = sorted(hits)
+    idx = torch.tensor(order, device="cuda")
+    hit_masks = [hits[s][0] for s in order]
+    expected = gfref.device_codewords(10, 4, S, L, seed=edge)
+    masks = i32(CYCLE)[torch.arange(S, device="cuda") % len(CYCLE)]
+    masks[idx] = i32(hit_masks)
+    t = expected.clone()
+    for i in range(14):
+        t[:, i][(masks >> i & 1) == 0] = FILL  # absent shards
+    for s in order:
+        for shard, pos, value in hits[s][1]:
+            t[s, shard, pos] ^= value
+    dirty = t[idx].cpu().numpy()
+    want_chk, want_sus = C.check_words(dirty, hit_masks), C.suspect_words(dirty, hit_masks)
+    assert want_sus == [hits[s][2] for s in order], hexes(want_sus)
+    want_use, want_left = C.use_masks(hit_masks, want_chk, want_sus)
+    n_dirty = sum(1 for w in want_chk if w)
+    assert n_dirty == sum(1 for s in order if hits[s][1]) and want_left == 5
+    present = sum(masks >> i & 1 for i in range(14))
+    n_unchecked, n_few = int((present <= 10).sum()), int((present < 10).sum())
+    assert n_few == 2 and n_unchecked > S // len(CYCLE)
+    chk_want, sus_want = expect_words(S, idx, want_chk), expect_words(S, idx, want_sus)
+    use_want = expect_words(S, idx, want_use, rest=masks)
+    given, before = masks.clone(), checksum(t)
+
+    # pass 1 alone, then both passes: words and counts, nothing else written
+    for locate in (False, True):
+        chk, sus = words(2, S)
+        bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+        unchecked = torch.full((1,), 5, dtype=torch.int32, device="cuda")
+        if locate:
+            H.locate_corrupt_present_batch(rs, t, masks, check=chk, suspects=sus, bad_stripes=bad, unchecked=unchecked)
+        else:
+            H.verify_present_batch(rs, t, masks, check=chk, bad_stripes=bad, unchecked=unchecked)
+        torch.cuda.synchronize()
+        assert_words(chk, chk_want, ("check", locate))
+        if locate:
+            assert_words(sus, sus_want, "suspects")
+        assert (int(bad.item()), int(unchecked.item())) == (7 + n_dirty, 5 + n_unchecked), locate
+        assert checksum(t) == before and torch.equal(masks, given)
+
+    # the checked reconstruct: stripes it must leave byte for byte keep what they hold now
+    kept = [n for n, u in enumerate(want_use) if u == ALL or bin(u).count("1") < 10]
+    assert len(kept) == want_left + n_few
+    kept_idx = idx[torch.tensor(kept, device="cuda")]
+    expected[kept_idx] = t[kept_idx]
+    chk, sus, use = words(3, S)
+    bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+    left = torch.full((1,), 5, dtype=torch.int32, device="cuda")
+    H.reconstruct_checked_batch(rs, t, masks, check=chk, suspects=sus, use_masks=use, bad_stripes=bad,
+                                unrepaired=left)
+    torch.cuda.synchronize()
+    assert_words(chk, chk_want, "check of the reconstruct")
+    assert_words(sus, sus_want, "suspects of the reconstruct")
+    assert_words(use, use_want, "use masks")
+    assert (int(left.item()), int(bad.item())) == (5 + want_left, 7 + n_few)
+    assert torch.equal(masks, given)
+    if not torch.equal(t, expected):
+        wrong = torch.nonzero((t != expected).flatten(1).any(dim=1)).flatten()
+        pytest.fail(f"image: {wrong.numel()} wrong stripes, the first {wrong[:8].cpu().tolist()}")
+    # the proof: every stripe but the ones left alone verifies clean
+    ver, = words(1, S)
+    H.verify_batch(rs, t, mismatch=ver)
+    torch.cuda.synchronize()
+    assert torch.nonzero(ver[:S]).flatten().cpu().tolist() == [order[n] for n in kept]
+    del t, expected
+    torch.cuda.empty_cache()
+
+
+def test_checked_reconstruct_second_mask_round(gpu):
+    """2^19 + 5 stripes (117 MB): use_masks_kernel runs 2048 workgroups of 256
+    lanes, so the stripes from 2^19 on are its second round, the last five in
+    a partial wave whose ballot counts the stripes left alone."""
+    masked_scrub_big(MASK_ROUND)
+
+
+def test_masked_scrub_past_one_launch(gpu):
+    """2^23 + 5 stripes (1.9 GB and one clone): the last five items are the
+    second pass of rs104_check_stride_kernel's and rs104_locate_present_kernel's
+    grid-stride loops, the mask kernel's 17th round, and the second stripe
+    range of the reconstruct, driven by the use masks written just before."""
+    masked_scrub_big(LAUNCH_LIMIT)
 
 
 # ---- shard files -----------------------------------------------------------------
@@ -654,3 +863,47 @@ def test_files_all_present_equal_the_full_locate(gpu, volume, tmp_path):
         assert n_bad == 4 and [e[3] for e in full] == [UNEXPLAINED, 1 << 2, 1 << 11, 1 << 5]
         assert H.locate_corrupt_ec_files_present(base, block) == \
             (n_blocks, n_bad, [(o, ln, pm << 10, sus) for o, ln, pm, sus in full], 0x3FFF)
+
+
+def test_files_longer_than_the_two_slots(gpu, tmp_path):
+    """Shards of 8 MiB and a ragged rest with two files missing: three chunks
+    of the scrub's 4 MiB column range, both pinned slots reused. A missing
+    file's row of a slot is never read into, so it holds what an earlier call
+    left there: a full locate of another volume, 14 files of random bytes, runs
+    first in this process, and only "the kernel never reads an absent shard"
+    keeps the words right. Flips in the first, a middle and the last, short
+    block and on both sides of the chunk edges; the words of every listed block
+    from check_model, at 64 KiB blocks and at the default block size."""
+    import helyim_amd as H
+    size = (8 << 20) + 300_007
+    absent, mask = (3, 12), lost(3, 12)
+    rng = np.random.default_rng(2026)
+    stale = str(tmp_path / "stale")
+    for i in range(14):
+        rng.integers(0, 256, size, dtype=np.uint8).tofile(stale + ".ec%02d" % i)
+    bufs = [rng.integers(0, 256, size, dtype=np.uint8) for _ in range(10)] + [np.zeros(size, np.uint8) for _ in range(4)]
+    corc.CReedSolomon(10, 4).encode(bufs)
+    hits = [(11, 5), (2, (4 << 20) - 1), (13, 4 << 20), (6, (6 << 20) + 99), (9, (6 << 20) + 99),
+            (0, (8 << 20) - 1), (10, 8 << 20), (4, size - 1)]
+    for shard, off in hits:
+        assert shard not in absent
+        bufs[shard][off] ^= 0x33
+    base = str(tmp_path / "big")
+    for i in range(14):
+        if i not in absent:
+            bufs[i].tofile(base + ".ec%02d" % i)
+    for block in (65536, 0):
+        width = block or 1 << 20  # HEC_SMALL_BLOCK_SIZE
+        n_blocks = -(-size // width)
+        # every block of the random volume is bad, so both slots and all 14 rows were filled
+        assert H.locate_corrupt_ec_files(stale, block, cap=0)[:2] == (n_blocks, n_blocks)
+        want = []
+        for lo in sorted({off // width * width for _, off in hits}):
+            hi = min(lo + width, size)
+            want.append((lo, hi - lo) + block_words(bufs, mask, lo, hi))
+        assert all(w[2] and w[3] for w in want)
+        assert want[-1][:2] == (size // width * width, size % width)
+        if block:
+            assert [w[3] for w in want] == [1 << 11, 1 << 2, 1 << 13, want[3][3], 1 << 0, 1 << 10, 1 << 4]
+        assert H.locate_corrupt_ec_files_present(base, block) == (n_blocks, len(want), want, mask), hex(block)
+    assert not any(os.path.exists(base + ".ec%02d" % i) for i in absent)

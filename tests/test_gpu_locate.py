@@ -384,6 +384,135 @@ def test_repair_leaves_five_suspects_alone(gpu):
     assert after == mis == oracle_words(work, stripes, 10, 4) and after[1] != 0
 
 
+# ---- big batches: built, corrupted and compared on the device ----------------------
+MASK_ROUND = 2048 * 256  # stripes one round of repair_masks_kernel takes: 2048 workgroups of 256 lanes
+LAUNCH_LIMIT = 1 << 23   # workgroups of one launch, and of one pass of a grid-stride loop
+
+
+def edge_hits(edge):
+    """stripe -> (flips [(shard, pos, value)], suspects word by construction)
+    of a batch of edge + 5 stripes of 16 bytes: one-shard flips (repaired) in
+    the first and last stripe, on both sides of a wave and of `edge`; two
+    shards in two columns (both repaired); same-column pairs and five wrong
+    shards (left alone) on both sides of `edge` and in the last, partial wave."""
+    S = edge + 5
+    assert edge % 64 == 0 and edge // 2 > 1000
+    return {
+        0: ([(2, 7, 0x21)], 1 << 2),
+        255: ([(13, 0, 0x01)], 1 << 13),
+        256: ([(11, 15, 0x80)], 1 << 11),
+        1000: ([(1, 0, 0x80), (4, 3, 0x40), (8, 6, 0x20), (10, 9, 0x10), (13, 12, 0x08)],
+               1 << 1 | 1 << 4 | 1 << 8 | 1 << 10 | 1 << 13),
+        edge // 2 + 1: ([(0, 2, 0x5A), (12, 9, 0x5A)], 1 << 0 | 1 << 12),
+        edge - 2: ([(4, 5, 0x33), (8, 5, 0x44)], UNEXPLAINED),
+        edge - 1: ([(9, 3, 0xFF)], 1 << 9),
+        edge: ([(1, 8, 0x10)], 1 << 1),
+        edge + 1: ([(0, 11, 0x07), (13, 11, 0x70)], UNEXPLAINED),
+        S - 3: ([(6, 9, 0x11), (12, 9, 0x22)], UNEXPLAINED),
+        S - 2: ([(3, 1, 0x01), (3, 14, 0xFE)], 1 << 3),
+        S - 1: ([(10, 15, 0x42)], 1 << 10),
+    }
+
+
+def i32(values):
+    import torch
+    return torch.tensor(np.array(values, dtype=np.uint32).view(np.int32), device="cuda")
+
+
+def expect_words(S, idx, values, rest=0):
+    """[S + 1] words on the device: `rest` everywhere, `values` at the stripes
+    idx, the sentinel at S -- what result_words(n, S) must become."""
+    import torch
+    t = torch.full((S + 1,), rest, dtype=torch.int32, device="cuda")
+    t[idx] = i32(values)
+    t[S] = SENTINEL
+    return t
+
+
+def assert_words(got, want, what):
+    import torch
+    if not torch.equal(got, want):
+        at = torch.nonzero(got != want).flatten()[:8].cpu().tolist()
+        pytest.fail(f"{what}: wrong at {at}: got {hex_list(got[at].cpu().numpy().view(np.uint32))}, "
+                    f"expected {hex_list(want[at].cpu().numpy().view(np.uint32))}")
+
+
+def locate_and_repair_big(edge):
+    """hec_gpu_locate_corrupt_batch, then hec_gpu_repair_batch, over edge + 5
+    stripes of 16 bytes with edge_hits' corruption. Expected words of the dirty
+    stripes from locate_model on those stripes, and by construction; every
+    other stripe is a codeword of gfref's torch twin, so its words are zero
+    and its mask 0x3FFF: whole arrays and the whole image are compared on the
+    device."""
+    import torch
+    import gfref
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    S, L = edge + 5, 16
+    hits = edge_hits(edge)
+    order = sorted(hits)
+    idx = torch.tensor(order, device="cuda")
+    expected = gfref.device_codewords(10, 4, S, L, seed=edge + 1)
+    t = expected.clone()
+    for s in order:
+        for shard, pos, value in hits[s][0]:
+            t[s, shard, pos] ^= value
+    dirty = t[idx].cpu().numpy()
+    want_sus, want_mis = M.suspect_words(dirty), M.mismatch_words(dirty)
+    assert want_sus == [hits[s][1] for s in order], hex_list(want_sus)
+    assert all(want_mis)
+    want_masks = expected_masks(want_sus)
+    kept = [n for n, m in enumerate(want_masks) if m == ALL]  # dirty and left alone
+    assert [order[n] for n in kept] == [1000, edge - 2, edge + 1, S - 3]
+    sus_want, mis_want = expect_words(S, idx, want_sus), expect_words(S, idx, want_mis)
+    masks_want = expect_words(S, idx, want_masks, rest=ALL)
+    before = int(t.view(torch.int64).sum().item())
+
+    mis, sus = result_words(2, S)
+    bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+    H.locate_corrupt_batch(rs, t, mismatch=mis, suspects=sus, bad_stripes=bad)
+    torch.cuda.synchronize()
+    assert_words(mis, mis_want, "mismatch")
+    assert_words(sus, sus_want, "suspects")
+    assert int(bad.item()) == 7 + len(order)
+    assert int(t.view(torch.int64).sum().item()) == before  # nothing written: one reduction over every byte
+
+    kept_idx = idx[torch.tensor(kept, device="cuda")]
+    expected[kept_idx] = t[kept_idx]
+    mis, sus, masks = result_words(3, S)
+    left = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+    H.repair_batch(rs, t, mismatch=mis, suspects=sus, present_masks=masks, unrepaired=left)
+    torch.cuda.synchronize()
+    assert_words(mis, mis_want, "mismatch of the repair")
+    assert_words(sus, sus_want, "suspects of the repair")
+    assert_words(masks, masks_want, "present masks")
+    assert int(left.item()) == 7 + len(kept)
+    if not torch.equal(t, expected):
+        wrong = torch.nonzero((t != expected).flatten(1).any(dim=1)).flatten()
+        pytest.fail(f"image: {wrong.numel()} wrong stripes, the first {wrong[:8].cpu().tolist()}")
+    # the proof: every stripe but the ones left alone verifies clean
+    ver, = result_words(1, S)
+    H.verify_batch(rs, t, mismatch=ver)
+    torch.cuda.synchronize()
+    assert_words(ver, expect_words(S, kept_idx, [want_mis[n] for n in kept]), "verify after the repair")
+    del t, expected
+    torch.cuda.empty_cache()
+
+
+def test_repair_second_mask_round(gpu):
+    """2^19 + 5 stripes (117 MB): repair_masks_kernel runs 2048 workgroups of
+    256 lanes, so the stripes from 2^19 on are its second round, the last five
+    in a partial wave whose ballot counts the stripes left alone."""
+    locate_and_repair_big(MASK_ROUND)
+
+
+def test_locate_and_repair_past_one_launch(gpu):
+    """2^23 + 5 stripes (1.9 GB and one clone): rs104_locate_kernel's loop far
+    past 2^23 items, the mask kernel's 17th round, and the second stripe range
+    of the reconstruct, driven by the masks written just before."""
+    locate_and_repair_big(LAUNCH_LIMIT)
+
+
 # ---- shard files -----------------------------------------------------------------
 BLOCK = 4096
 

@@ -1,0 +1,142 @@
+"""The model-based GPU suites again, against build/variants/libhec_smallgrid.so:
+the product's sources with kMaxLaunchBlocks = 100 and kLocateMaxBlocks = 4
+(Makefile, VFLAGS_smallgrid). Every test of the files below compares the
+library with check_model, locate_model, gfref or the C oracle, never with
+itself, so under the variant their batches of a few hundred stripes become
+split tests: stripe ranges in launch_apply, launch_verify, launch_check and
+launch_ragged, second and later iterations of every grid-stride loop, and
+several rounds of the two mask kernels -- paths that need 2^23 workgroups (up
+to 960 GB of shards) at the product's limits.
+
+One child process per file (`python -m pytest <file> -m gpu` with HEC_LIB_PATH
+set); tests/small_grid_probe.py runs first in the child and ends it unless the
+limits are live. A child that dies of a signal or runs out of time fails every
+remaining file without starting another process on the device."""
+import os
+import re
+import subprocess
+import sys
+import time
+
+import pytest
+
+import small_grid_probe as probe
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TESTS = os.path.join(ROOT, "tests")
+VARIANT = os.path.join(ROOT, "build", "variants", "libhec_smallgrid.so")
+CHILD_TIMEOUT = 300  # seconds; a child takes about what its file takes with the product library
+
+FILES = ["test_gpu_check.py", "test_gpu_locate.py", "test_gpu_verify.py", "test_gpu_generic_codecs.py",
+         "test_gpu_footprint.py", "test_gpu_intervals.py", "test_gpu_parity.py"]
+
+# Deselected under the variant, by node id. Only two kinds: shapes of more than
+# 2 GiB of device memory or more than 2^20 stripes ("size"), and expectations
+# that are a kernel name or a path choice the limit legitimately changes
+# ("name"). No verify, locate, repair, check or checked-reconstruct test at
+# shards of 16 KiB or less is here.
+DESELECT = {
+    "test_gpu_check.py": [
+        ("test_shard_len_near_4gib[4294965248]", "size: 112 GiB in HBM"),
+        ("test_shard_len_near_4gib[4294971408]", "size: 112 GiB in HBM"),
+        ("test_masked_scrub_past_one_launch", "size: 2^23 + 5 stripes, 1.9 GB and a clone"),
+    ],
+    "test_gpu_locate.py": [
+        ("test_locate_and_repair_past_one_launch", "size: 2^23 + 5 stripes, 1.9 GB and a clone"),
+    ],
+    "test_gpu_verify.py": [
+        ("test_verify_shard_len_near_4gib[4294959104]", "size: 56 GiB in HBM"),
+        ("test_verify_shard_len_near_4gib[4294975488]", "size: 56 GiB in HBM"),
+        ("test_verify_shard_len_near_4gib[4294971408]", "size: 56 GiB in HBM"),
+        ("test_kernel_names", "name: 1 MiB shards are 128 chunks of 8 KiB, more than 100: the generic verify"),
+    ],
+    "test_gpu_generic_codecs.py": [
+        ("test_generic_batch_past_one_grid[16]", "size: 2^23 + 5 stripes"),
+        ("test_generic_batch_past_one_grid[1]", "size: 2^23 + 5 stripes"),
+        ("test_rs104_odd_base_batch_past_one_grid", "size: 2^23 + 5 stripes"),
+        ("test_k10_odd_base_batch_past_one_grid", "size: 2^23 + 5 stripes"),
+        ("test_verify_past_one_grid[10-4-16]", "size: 2^23 + 5 stripes"),
+        ("test_verify_past_one_grid[3-2-1]", "size: 2^23 + 5 stripes"),
+    ],
+    "test_gpu_footprint.py": [],
+    "test_gpu_intervals.py": [],
+    "test_gpu_parity.py": [
+        ("test_bitslice_encode_matches_oracle", "name: asserts the bit-sliced encode at 1 MiB shards (256 chunks > 100)"),
+        ("test_full_config_roundtrip[0]", "size: 4096 stripes of 14 x 1 MiB, 56 GiB"),
+        ("test_full_config_roundtrip[65536]", "size: 4096 stripes of 14 x 1 MiB, 56 GiB"),
+        ("test_full_config_every_4_erasure_pattern_and_linearity", "size: 4004 stripes of 14 x 1 MiB, 55 GiB"),
+        ("test_batch_over_launch_limit_is_split", "size: 2^24 + 5 stripes"),
+        ("test_ragged_over_launch_limit_is_split", "size: 2^24 + 5 stripes"),
+        ("test_ragged_shard_len_near_4gib", "size: 56 GiB in HBM"),
+        ("test_strided_batch_shard_len_near_4gib[4294959104]", "size: 56 GiB in HBM"),
+        ("test_strided_batch_shard_len_near_4gib[4294963200]", "size: 56 GiB in HBM"),
+        ("test_strided_batch_shard_len_near_4gib[4294975488]", "size: 56 GiB in HBM"),
+        ("test_config5_whole_batch_vs_oracle", "size: 32 GiB in HBM, and 17 of this child's 26 s"),
+    ],
+}
+
+_stopped = []  # why no further child may start (a child died of a signal or ran out of time)
+
+
+def child_env():
+    env = dict(os.environ)
+    env["HEC_LIB_PATH"] = VARIANT
+    env["PYTHONPATH"] = os.pathsep.join([TESTS] + [p for p in env.get("PYTHONPATH", "").split(os.pathsep) if p])
+    return env
+
+
+def tail(text, n=60):
+    return "\n".join(text.splitlines()[-n:])
+
+
+def count(word, text):
+    m = re.search(r"(\d+) " + word, text.splitlines()[-1] if text.strip() else "")
+    return int(m.group(1)) if m else 0
+
+
+def test_variant_is_built_and_its_limits_are_live():
+    """build() leaves the variant beside the product; a process that loads it
+    reports the limits and the kernel names that flip with them, and the
+    product library exports no such query."""
+    import helyim_amd as H
+    assert os.path.exists(VARIANT), VARIANT + " is missing: `make all` builds it"
+    assert probe.limits(H.lib) is None or os.environ.get("HEC_LIB_PATH")
+    r = subprocess.run([sys.executable, os.path.join(TESTS, "small_grid_probe.py")], env=child_env(), cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("small-grid probe ok"), tail(r.stdout + r.stderr)
+    # the same shard lengths name the one-chunk-per-workgroup kernels in the product
+    product = {(fn, length): getattr(H.lib, fn)(length).decode() for fn, length, _ in probe.NAMES}
+    if not os.environ.get("HEC_LIB_PATH"):
+        assert product["hec_encode_kernel_name", 102 * 4096].startswith("rs104_bs_encode_kernel")
+        assert product["hec_verify_kernel_name", 101 * 8192].startswith("rs104_bs_verify_kernel")
+        assert product["hec_check_kernel_name", 101 * 2048].startswith("rs104_check_kernel")
+        assert product["hec_decode_kernel_name", 101 * 2048].startswith("rs104_narrow_kernel<DEC=true")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FILES)
+def test_suite_against_small_grid(gpu, name):
+    assert not _stopped, "not started: " + _stopped[0]
+    assert os.path.exists(VARIANT), VARIANT + " is missing: `make all` builds it"
+    cmd = [sys.executable, "-m", "pytest", "-p", "small_grid_probe", os.path.join("tests", name), "-m", "gpu", "-q",
+           "--maxfail=5", "-p", "no:cacheprovider"]
+    for node, _reason in DESELECT[name]:
+        cmd += ["--deselect", f"tests/{name}::{node}"]
+    t0 = time.monotonic()
+    try:
+        r = subprocess.run(cmd, env=child_env(), cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+    except subprocess.TimeoutExpired as e:
+        _stopped.append(f"the child of {name} was killed after {CHILD_TIMEOUT} s")
+        out = e.stdout if isinstance(e.stdout, str) else (e.stdout or b"").decode(errors="replace")
+        pytest.fail(_stopped[0] + "\n" + tail(out))
+    wall = time.monotonic() - t0
+    out = r.stdout + r.stderr
+    if r.returncode < 0:
+        _stopped.append(f"the child of {name} died of signal {-r.returncode}")
+        pytest.fail(_stopped[0] + "\n" + tail(out))
+    passed, deselected = count("passed", r.stdout), count("deselected", r.stdout)
+    print(f"small grid {name}: {passed + deselected + count('failed', r.stdout)} collected, {deselected} deselected, "
+          f"{passed} passed, {wall:.1f} s")
+    assert r.returncode == 0, f"{name} under the small-grid variant (return code {r.returncode}):\n{tail(out)}"
+    assert passed > 0, tail(out)
+    assert deselected == len(DESELECT[name]), f"a deselected node id of {name} matches no test:\n{tail(out)}"

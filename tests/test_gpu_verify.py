@@ -179,6 +179,33 @@ def test_bad_stripes_counts_a_stripe_exactly_once(gpu, which):
     assert words == want and bad == 9, (name, words, bad)
 
 
+def test_bitsliced_batch_of_three_chunk_stripes(gpu):
+    """70 stripes of 3 x 8 KiB: 210 bit-sliced workgroups, a chunk count per
+    stripe that is no power of two and a grid that is no multiple of 8. Flips
+    in chunks 0, 1 and 2 of the first and last stripe and of stripes 32, 33, 65
+    and 66: with the launch limit of the small-grid build
+    (tests/test_gpu_small_grid.py) a launch takes 33 such stripes, so those are
+    the two sides of its stripe ranges and the words of a range land at its
+    first stripe."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    S, L = 70, 3 * 8192
+    assert H.lib.hec_verify_kernel_name(L).decode().startswith("rs104_bs_verify_kernel")
+    name, data, par, stripes, arenas = clean_case(10, 4, L, S, 0)
+    work = copies(arenas)
+    want = [0] * S
+    for n, s in enumerate((0, 32, 33, 65, 66, S - 1)):
+        j = n % 4
+        shard_of(work, stripes, s, 10 + j)[(n % 3) * 8192 + 4095 + n] ^= 0x01 << n
+        want[s] = 1 << j
+    shard_of(work, stripes, 34, 3)[L - 1] ^= 0x80  # a data shard: every parity shard differs
+    want[34] = 0b1111
+    assert oracle_words(work, stripes, 10, 4) == want
+    words, bad = device_verify(rs, work, stripes, data, par)
+    assert words == want, ([hex(w) for w in words], [hex(w) for w in want])
+    assert bad == 7 + 7
+
+
 @pytest.mark.parametrize("k,m", [(5, 5), (3, 2), (17, 3), (4, 32), (10, 2), (10, 6)])
 @pytest.mark.parametrize("L", [4096, 100])
 def test_other_codecs_take_the_generic_kernel(gpu, k, m, L):
