@@ -143,6 +143,44 @@ def verify_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, 
     return mismatch
 
 
+def _locate(call, rs, stripes, mismatch, suspects, bad_stripes, stream):
+    _check_stripes(stripes, rs)
+    k = rs.data_shard_count()
+    S, n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    check(call(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
+               _stream_ptr(stream)))
+    return mismatch, suspects
+
+
+def _locate_sep(call, rs, data, parity, mismatch, suspects, bad_stripes, stream):
+    _check_stripes(data, rs, rs.data_shard_count())
+    _check_stripes(parity, rs, rs.parity_shard_count())
+    S, k, L = data.shape
+    if parity.shape[0] != S or parity.shape[2] != L:
+        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    check(call(rs.handle, data.data_ptr(), data.stride(0), data.stride(1), parity.data_ptr(), parity.stride(0),
+               parity.stride(1), L, S, mismatch.data_ptr(), suspects.data_ptr(), bad, _stream_ptr(stream)))
+    return mismatch, suspects
+
+
+def _repair(call, rs, stripes, mismatch, suspects, present_masks, unrepaired, stream):
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    mismatch = _words_arg(S, mismatch, "mismatch")
+    left = _counter_arg(unrepaired, "unrepaired")
+    suspects = _words_arg(S, suspects, "suspects")
+    present_masks = _words_arg(S, present_masks, "present_masks")
+    check(call(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, mismatch.data_ptr(),
+               suspects.data_ptr(), present_masks.data_ptr(), left, _stream_ptr(stream)))
+    return mismatch, suspects, present_masks
+
+
 def locate_corrupt_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
                          suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, stream=None):
     """verify_batch that also names the corrupt shard (hec_gpu_locate_corrupt_batch,
@@ -153,33 +191,35 @@ def locate_corrupt_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch
     31) = a column no single shard explains; 0 = clean. With at most 3 wrong
     shards in a column no intact shard is ever named. Nothing else is written.
     Asynchronous on the stream."""
-    _check_stripes(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    suspects = _words_arg(S, suspects, "suspects")
-    check(lib.hec_gpu_locate_corrupt_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(),
-                                           suspects.data_ptr(), bad, _stream_ptr(stream)))
-    return mismatch, suspects
+    return _locate(lib.hec_gpu_locate_corrupt_batch, rs, stripes, mismatch, suspects, bad_stripes, stream)
 
 
 def locate_corrupt_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
                              mismatch: torch.Tensor = None, suspects: torch.Tensor = None,
                              bad_stripes: torch.Tensor = None, stream=None):
     """locate_corrupt_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
-    _check_stripes(data, rs, rs.data_shard_count())
-    _check_stripes(parity, rs, rs.parity_shard_count())
-    S, k, L = data.shape
-    if parity.shape[0] != S or parity.shape[2] != L:
-        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    suspects = _words_arg(S, suspects, "suspects")
-    check(lib.hec_gpu_locate_corrupt_batch(rs.handle, data.data_ptr(), data.stride(0), data.stride(1),
-                                           parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
-                                           mismatch.data_ptr(), suspects.data_ptr(), bad, _stream_ptr(stream)))
-    return mismatch, suspects
+    return _locate_sep(lib.hec_gpu_locate_corrupt_batch, rs, data, parity, mismatch, suspects, bad_stripes, stream)
+
+
+def locate_corrupt_pairs_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                               suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, stream=None):
+    """locate_corrupt_batch that also names two wrong shards of a byte column
+    (hec_gpu_locate_corrupt_pairs_batch, RS(10,4) only): the same arguments
+    and result shape. A column one shard explains sets its bit as before; a
+    column that shards a and b together explain sets bits a and b; bit 31 = a
+    column no one or two shards explain. At most 2 wrong shards in a column
+    are named exactly; 3 wrong shards never name a single intact shard but
+    may name an intact pair (include/hec.h) -- locate_corrupt_batch keeps the
+    stricter promise. Asynchronous on the stream."""
+    return _locate(lib.hec_gpu_locate_corrupt_pairs_batch, rs, stripes, mismatch, suspects, bad_stripes, stream)
+
+
+def locate_corrupt_pairs_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
+                                   mismatch: torch.Tensor = None, suspects: torch.Tensor = None,
+                                   bad_stripes: torch.Tensor = None, stream=None):
+    """locate_corrupt_pairs_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
+    return _locate_sep(lib.hec_gpu_locate_corrupt_pairs_batch, rs, data, parity, mismatch, suspects, bad_stripes,
+                       stream)
 
 
 def repair_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
@@ -193,16 +233,18 @@ def repair_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor 
     byte (mask ``0x3FFF``) and, when its word is non-zero, counted into
     unrepaired (32-bit CUDA word, accumulated). Run verify_batch afterwards
     for proof. Asynchronous on the stream."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    mismatch = _words_arg(S, mismatch, "mismatch")
-    left = _counter_arg(unrepaired, "unrepaired")
-    suspects = _words_arg(S, suspects, "suspects")
-    present_masks = _words_arg(S, present_masks, "present_masks")
-    check(lib.hec_gpu_repair_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S,
-                                   mismatch.data_ptr(), suspects.data_ptr(), present_masks.data_ptr(), left,
-                                   _stream_ptr(stream)))
-    return mismatch, suspects, present_masks
+    return _repair(lib.hec_gpu_repair_batch, rs, stripes, mismatch, suspects, present_masks, unrepaired, stream)
+
+
+def repair_pairs_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                       suspects: torch.Tensor = None, present_masks: torch.Tensor = None,
+                       unrepaired: torch.Tensor = None, stream=None):
+    """repair_batch over locate_corrupt_pairs_batch's words
+    (hec_gpu_repair_pairs_batch): the same arguments and results; a stripe with
+    two shards wrong in one column is repaired too, as long as its columns
+    name at most four shards in all and bit 31 is clear. Whole shards per
+    stripe. Asynchronous on the stream."""
+    return _repair(lib.hec_gpu_repair_pairs_batch, rs, stripes, mismatch, suspects, present_masks, unrepaired, stream)
 
 
 def _masks_arg(S: int, present_masks: torch.Tensor) -> torch.Tensor:

@@ -110,10 +110,11 @@ int hec_gpu_verify_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t dat
                       static_cast<hipStream_t>(stream));
 }
 
-int hec_gpu_locate_corrupt_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
-                                 uint64_t data_shard_stride, const uint8_t* d_parity, uint64_t parity_stripe_stride,
-                                 uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
-                                 uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes, void* stream) {
+// hec_gpu_locate_corrupt_batch and its pairs form: one body.
+static int locate_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
+                        uint64_t data_shard_stride, const uint8_t* d_parity, uint64_t parity_stripe_stride,
+                        uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch,
+                        uint32_t* d_suspects, uint32_t* d_bad_stripes, void* stream, bool pairs) {
     HEC_TRY(check_batch_args(rs, d_data, d_parity, shard_len));
     HEC_TRY(check_verify_args(rs, d_mismatch));
     HEC_TRY(check_locate_args(rs, d_suspects));
@@ -124,12 +125,32 @@ int hec_gpu_locate_corrupt_batch(const hec_rs_t* rs, const uint8_t* d_data, uint
     HEC_TRY(geom_device(rs, &gd));
     return run_locate(*gd, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
                       parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes,
-                      static_cast<hipStream_t>(stream));
+                      static_cast<hipStream_t>(stream), pairs);
 }
 
-int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride, uint64_t shard_stride,
-                         uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,
-                         uint32_t* d_present_masks, uint32_t* d_unrepaired, void* stream) {
+int hec_gpu_locate_corrupt_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
+                                 uint64_t data_shard_stride, const uint8_t* d_parity, uint64_t parity_stripe_stride,
+                                 uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                 uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes, void* stream) {
+    return locate_batch(rs, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
+                        parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes, stream,
+                        false);
+}
+
+int hec_gpu_locate_corrupt_pairs_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
+                                       uint64_t data_shard_stride, const uint8_t* d_parity,
+                                       uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                                       uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch,
+                                       uint32_t* d_suspects, uint32_t* d_bad_stripes, void* stream) {
+    return locate_batch(rs, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
+                        parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes, stream,
+                        true);
+}
+
+// hec_gpu_repair_batch and its pairs form: one body.
+static int repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride, uint64_t shard_stride,
+                        uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,
+                        uint32_t* d_present_masks, uint32_t* d_unrepaired, void* stream, bool pairs) {
     if (!rs || !d_shards || !d_mismatch || !d_suspects || !d_present_masks)
         return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     if (shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
@@ -142,11 +163,25 @@ int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_
     HEC_TRY(ensure_dense_decode(rs, gd, s));  // before any launch: its first call uploads and waits
     const uint8_t* parity = d_shards + uint64_t(rs->k) * shard_stride;
     HEC_TRY(run_locate(*gd, d_shards, stripe_stride, shard_stride, parity, stripe_stride, shard_stride, shard_len,
-                       n_stripes, d_mismatch, d_suspects, nullptr, s));
+                       n_stripes, d_mismatch, d_suspects, nullptr, s, pairs));
     HEC_HIP(launch_repair_masks(d_suspects, d_present_masks, d_unrepaired, n_stripes, s));
     // a stripe left alone has every shard present: the reconstruct's no-op
     return run_apply(gd->decode_dense, uint32_t(rs->k), d_shards, stripe_stride, shard_stride, d_shards, stripe_stride,
                      shard_stride, shard_len, n_stripes, d_present_masks, nullptr, s);
+}
+
+int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride, uint64_t shard_stride,
+                         uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,
+                         uint32_t* d_present_masks, uint32_t* d_unrepaired, void* stream) {
+    return repair_batch(rs, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_mismatch, d_suspects,
+                        d_present_masks, d_unrepaired, stream, false);
+}
+
+int hec_gpu_repair_pairs_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride, uint64_t shard_stride,
+                               uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,
+                               uint32_t* d_present_masks, uint32_t* d_unrepaired, void* stream) {
+    return repair_batch(rs, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_mismatch, d_suspects,
+                        d_present_masks, d_unrepaired, stream, true);
 }
 
 int hec_gpu_verify_present_batch(const hec_rs_t* rs, const uint8_t* d_shards, uint64_t stripe_stride,

@@ -222,6 +222,10 @@ struct GeomDevice {
     // RS(10,4) only: the locate kernel's ratio constants as one 3 x 10 plan,
     // row j - 1, input c = P[j][c] / P[0][c] (P = the parity rows; run_locate)
     DevicePlanSet locate;
+    // RS(10,4) only: the pair search's constants (rs_kernels.hpp
+    // VerifyArgs::pair_tabs): plan 0 = T, 4 x 4, classical syndromes S = T *
+    // syn; plan 1 = 14 rows (alpha_c^2, alpha_c) over the inputs (D, N1)
+    DevicePlanSet locate_pairs;
     // RS(10,4) only, built on first use (ensure_check_plans): the degraded
     // scrub's plans. check: a dense LUT over the 2^14 present masks to one
     // plan per mask with 11 or more shards present (inputs B, outputs E,
@@ -455,10 +459,11 @@ inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
 // run_verify over gd's encode plan (mismatch[], bad: exactly its contract),
 // then suspects[0, n_stripes) are cleared on s and the locate kernel reads the
 // flagged stripes again (rs_kernels.hpp launch_locate; the result contract is
-// hec.h's). gd: the RS(10,4) geometry (the caller checks the codec).
+// hec.h's). gd: the RS(10,4) geometry (the caller checks the codec). pairs:
+// pass 2 also names two shards per column (hec_gpu_locate_corrupt_pairs_batch).
 int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
                const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
-               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s);
+               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s, bool pairs = false);
 // The locate entry points' extra argument checks, after check_verify_args.
 inline int check_locate_args(const hec_rs* rs, const void* suspects) {
     if (!suspects) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");

@@ -155,6 +155,38 @@ int geom_device(const hec_rs* rs, GeomDevice** out) {
         HostPlans rp;
         rp.add(ratio, in_ids, {1, 2, 3});
         if ((rc = gd->locate.upload(rp, nullptr, nullptr))) return rc;
+        // the pair search's constants. Shard i of a codeword is p(alpha_i),
+        // alpha_i = the byte i, deg p < k, so H'[j][i] = u_i * alpha_i^j with
+        // u_i = 1 / prod_{l != i} (alpha_i ^ alpha_l) annihilates the code
+        // and H' = T * [P | I], T = H'[:, k..n): checked here, not assumed.
+        const int n = rs->n, m = rs->m;
+        Mat dual(m, n);
+        for (int i = 0; i < n; ++i) {
+            uint8_t prod = 1;
+            for (int l = 0; l < n; ++l)
+                if (l != i) prod = g.mul[prod][uint8_t(i ^ l)];
+            for (int j = 0; j < m; ++j) dual.at(j, i) = g.mul[g.inv(prod)][g.pow(uint8_t(i), unsigned(j))];
+        }
+        Mat t(m, m);
+        for (int j = 0; j < m; ++j)
+            for (int i = 0; i < m; ++i) t.at(j, i) = dual.at(j, rs->k + i);
+        const Mat tp = mat_mul(t, par);
+        for (int j = 0; j < m; ++j)
+            for (int c = 0; c < rs->k; ++c)
+                if (tp.at(j, c) != dual.at(j, c))
+                    return fail(HEC_ERR_INVALID_ARGUMENT, "the encoding matrix is not the evaluation code");
+        // plan 0: S = T * syn; plan 1: D * alpha_c^2 ^ N1 * alpha_c, one row per shard c
+        Mat roots(n, 2);
+        for (int c = 0; c < n; ++c) {
+            roots.at(c, 0) = g.mul[uint8_t(c)][uint8_t(c)];
+            roots.at(c, 1) = uint8_t(c);
+        }
+        std::vector<uint32_t> all_ids;
+        for (int c = 0; c < n; ++c) all_ids.push_back(uint32_t(c));
+        HostPlans pp;
+        pp.add(t, {0, 1, 2, 3}, {0, 1, 2, 3});
+        pp.add(roots, {0, 1}, all_ids);
+        if ((rc = gd->locate_pairs.upload(pp, nullptr, nullptr))) return rc;
     }
     *out = gd.get();
     g_geom[key] = std::move(gd);
@@ -321,7 +353,7 @@ int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint6
 
 int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
                const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
-               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s) {
+               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s, bool pairs) {
     if (n_stripes == 0) return HEC_OK;
     // pass 1: the scrub itself (bit-sliced where it applies), at its own rate
     HEC_TRY(run_verify(gd.encode, 10, data, data_stripe, data_shard, parity, parity_stripe, parity_shard, len,
@@ -332,8 +364,9 @@ int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, 
                                           parity_shard, len, n_stripes, mismatch, nullptr);
     v.suspects = suspects;
     v.ratio_tabs = gd.locate.tabs;
+    v.pair_tabs = gd.locate_pairs.tabs;
     HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_locate(v, aligned, s));
+    HEC_HIP(launch_locate(v, aligned, pairs, s));
     return HEC_OK;
 }
 

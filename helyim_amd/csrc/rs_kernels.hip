@@ -26,7 +26,8 @@
 //    turns their stores into a compare with the stored rows.
 //  * The locate kernel (rs104_locate_kernel) is the scrub's second pass: it
 //    reads only the stripes the verify flagged and names the wrong shard of
-//    each byte column from its syndrome.
+//    each byte column from its syndrome; its PAIRS form also names two wrong
+//    shards of a column (an error-locator step on the bytes left unexplained).
 //  * The masked verify and locate (rs104_check_kernel and siblings) are the
 //    degraded scrub: the mask-driven decode with its stores replaced by a
 //    compare against the spare present shards.
@@ -960,8 +961,113 @@ __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) {
     return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
 }
 
-template <bool ALIGNED>
-__global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
+// ---------------------------------------------------------------------------
+// Locate, two per column (hec.h hec_gpu_locate_corrupt_pairs_batch): the bytes
+// the ratio method leaves unexplained are tried as two wrong shards. Shard i of
+// a codeword is p(alpha_i), alpha_i = the byte i, deg p < 10, so the dual is
+// generalised Reed-Solomon: H'[j][i] = u_i * alpha_i^j annihilates the code,
+// H' = T * H, and S = T * syn are classical syndromes, S_j = sum e_i u_i
+// alpha_i^j (DESIGN.md §4 "Locate, two per column"). Two errors make S obey
+// S_{j+2} = sigma1 * S_{j+1} + sigma2 * S_j; with
+//   D = S0 S2 ^ S1^2,  N1 = S0 S3 ^ S1 S2,  N2 = S1 S3 ^ S2^2
+// (sigma1 = N1 / D, sigma2 = N2 / D) the wrong shards are the roots alpha_i of
+// D x^2 ^ N1 x ^ N2. A pair is named only when exactly two of the 14 alpha_i
+// are roots; then D != 0 (with D == 0 the polynomial is linear or zero: one
+// root, none or all 14; one error always has D == 0) and S_j = A a^j ^ B b^j
+// with A, B != 0, which is the contract's statement. No division is needed.
+// ---------------------------------------------------------------------------
+// a * b bytewise in GF(2^8) (0x11D), both operands variable: shift-and-add over
+// the bits of b with a packed xtime of a. No product leaves its byte: 0x01
+// bytes times 0xFF or 0x1D stay below 0x100.
+__device__ __forceinline__ uint32_t gf_mul_var(uint32_t a, const uint32_t b) {
+    uint32_t r = 0;
+#pragma unroll 1  // rolled: six unrolled products interleave and cost the kernel a fifth of its waves
+    for (int bit = 0; bit < 8; ++bit) {
+        r ^= a & (((b >> bit) & 0x01010101u) * 0xFFu);
+        a = ((a & 0x7F7F7F7Fu) << 1) ^ (((a >> 7) & 0x01010101u) * 0x1Du);
+    }
+    return r;
+}
+
+// coef * x bytewise, one dword: gf_mac's three lookups; tab -> the 5 words of coef.
+__device__ __forceinline__ uint32_t gf_mul_const(const uint32_t x, cu32p tab) {
+    const uint32_t a = __builtin_amdgcn_perm(tab[1], tab[0], x & 0x07070707u);
+    const uint32_t b = __builtin_amdgcn_perm(tab[3], tab[2], (x >> 3) & 0x07070707u);
+    const uint32_t c = __builtin_amdgcn_perm(tab[4], tab[4], (x >> 6) & 0x03030303u);
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+}
+
+// Set bits per byte (each count <= 8).
+__device__ __forceinline__ uint32_t popcount_bytes(uint32_t x) {
+    x = x - ((x >> 1) & 0x55555555u);
+    x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+    return (x + (x >> 4)) & 0x0F0F0F0Fu;
+}
+
+// Dword w (wave-uniform) of v, without indexing a register vector by a variable.
+__device__ __forceinline__ uint32_t dword_of(const u32x4 v, int w) {
+    return w == 0 ? v[0] : w == 1 ? v[1] : w == 2 ? v[2] : v[3];
+}
+
+constexpr int kPairSynWords = 4 * 4 * 5;  // T's tables; the root tables follow
+
+// s: the syndrome of this lane's 16 columns; unx[w]: 0x80 in the bytes of dword
+// w that no single shard explains. Returns bit c for every shard c that is one
+// of the two of some such byte, and clears those bytes from unx. pt: T as a
+// 4-input 4-row plan, then [2][14] tables: input 0 = D with alpha_c^2, input 1
+// = N1 with alpha_c, row c. One dword per round and a rolled loop over the
+// shards: the registers of one round, not of four at once (the kernel keeps
+// the single-shard kernel's occupancy).
+__device__ __forceinline__ uint32_t rs104_pair_search(const u32x4 (&s)[4], u32x4& unx, cu32p pt) {
+    constexpr int N = 14;
+    cu32p rt = pt + kPairSynWords;
+    uint32_t named = 0;
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t u = dword_of(unx, w);
+        if (__ballot(u != 0) == 0) continue;  // wave-uniform
+        uint32_t S[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t x = dword_of(s[i], w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) S[j] ^= gf_mul_const(x, pt + (i * 4 + j) * 5);
+        }
+        const uint32_t D = gf_mul_var(S[0], S[2]) ^ gf_mul_var(S[1], S[1]);
+        const uint32_t N1 = gf_mul_var(S[0], S[3]) ^ gf_mul_var(S[1], S[2]);
+        const uint32_t N2 = gf_mul_var(S[1], S[3]) ^ gf_mul_var(S[2], S[2]);
+        uint32_t lo = 0, hi = 0;  // bit c (lo) / c - 8 (hi) of a byte: alpha_c is a root
+#pragma unroll 1
+        for (int c = 0; c < N; ++c) {
+            const uint32_t q = gf_mul_const(D, rt + c * 5) ^ gf_mul_const(N1, rt + (N + c) * 5) ^ N2;
+            const uint32_t root = (u & ~nz_bytes(q)) >> 7;  // 0x01 per byte
+            if (c < 8)
+                lo |= root << c;
+            else
+                hi |= root << (c - 8);
+        }
+        const uint32_t count = popcount_bytes(lo) + popcount_bytes(hi);
+        const uint32_t two = u & ~nz_bytes(count ^ 0x02020202u);  // exactly two roots
+        const uint32_t keep = (two >> 7) * 0xFFu;
+        lo &= keep;
+        hi &= keep;
+        lo |= lo >> 16;
+        hi |= hi >> 16;
+        named |= ((lo | (lo >> 8)) & 0xFFu) | (((hi | (hi >> 8)) & 0x3Fu) << 8);
+        const uint32_t rest = u & ~two;
+        unx = u32x4{w == 0 ? rest : unx[0], w == 1 ? rest : unx[1], w == 2 ? rest : unx[2],
+                    w == 3 ? rest : unx[3]};
+    }
+    return named;
+}
+
+// PAIRS: bytes the single-shard method leaves unexplained go on to
+// rs104_pair_search; everything up to there is the same code. The pairs
+// instantiation asks for the five waves per SIMD the other one gets unasked
+// (95 VGPRs): without the bound it takes 103 VGPRs and four waves, and a clean
+// batch would pay for code it never reaches (profiles/locate_pairs/isa.md).
+template <bool ALIGNED, bool PAIRS = false>
+__global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(VerifyArgs v) {
     constexpr int K = 10, R = 4;
     const ApplyArgs& a = v.a;
     cu32p tab = as_const(a.tabs);        // encode plan: [K][R][5] words
@@ -1005,6 +1111,7 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
         uint32_t one[R] = {0, 0, 0, 0};  // bytes where only s[j] is non-zero
         uint32_t all4[4];                // per dword: bytes where all four are
         uint32_t unexplained = 0, all_any = 0;
+        [[maybe_unused]] u32x4 unx;  // PAIRS: `unexplained` per dword
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const uint32_t n0 = nz_bytes(s[0][w]), n1 = nz_bytes(s[1][w]), n2 = nz_bytes(s[2][w]),
@@ -1017,7 +1124,9 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
             one[3] |= o3;
             all4[w] = n0 & n1 & n2 & n3;
             all_any |= all4[w];
-            unexplained |= (n0 | n1 | n2 | n3) & ~all4[w] & ~(o0 | o1 | o2 | o3);  // two or three non-zero
+            const uint32_t some = (n0 | n1 | n2 | n3) & ~all4[w] & ~(o0 | o1 | o2 | o3);  // two or three non-zero
+            unexplained |= some;
+            if constexpr (PAIRS) unx[w] = some;
         }
         uint32_t bits = 0;
         if (__ballot(all_any != 0) != 0) {  // wave-uniform: some column may name a data shard
@@ -1039,7 +1148,18 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
                 bits |= (__ballot(hit != 0) != 0 ? 1u : 0u) << c;
             }
 #pragma unroll
-            for (int w = 0; w < 4; ++w) unexplained |= all4[w] & ~matched[w];
+            for (int w = 0; w < 4; ++w) {
+                unexplained |= all4[w] & ~matched[w];
+                if constexpr (PAIRS) unx[w] |= all4[w] & ~matched[w];
+            }
+        }
+        if constexpr (PAIRS) {
+            if (__ballot(unexplained != 0) != 0) {  // wave-uniform: some column may name two shards
+                const uint32_t two = rs104_pair_search(s, unx, as_const(v.pair_tabs));
+#pragma unroll
+                for (int c = 0; c < K + R; ++c) bits |= (__ballot(((two >> c) & 1u) != 0) != 0 ? 1u : 0u) << c;
+                unexplained = unx[0] | unx[1] | unx[2] | unx[3];
+            }
         }
 #pragma unroll
         for (int j = 0; j < R; ++j) bits |= (__ballot(one[j] != 0) != 0 ? 1u : 0u) << (K + j);
@@ -1048,8 +1168,11 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_kernel(VerifyArgs v) {
     }
 }
 
-hipError_t launch_locate(const VerifyArgs& v, bool aligned, hipStream_t stream) {
+hipError_t launch_locate(const VerifyArgs& v, bool aligned, bool pairs, hipStream_t stream) {
     if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
+    if (pairs)
+        return launch_stride(aligned ? rs104_locate_kernel<true, true> : rs104_locate_kernel<false, true>, v, stream,
+                             kLocateMaxBlocks);
     return launch_stride(aligned ? rs104_locate_kernel<true> : rs104_locate_kernel<false>, v, stream,
                          kLocateMaxBlocks);
 }

@@ -140,6 +140,9 @@ struct VerifyArgs {
     // launch_locate only (the verify kernels never read these):
     uint32_t* suspects = nullptr;          // one word per stripe, zero at launch
     const uint32_t* ratio_tabs = nullptr;  // [10 data shards][3][kTabWords]: P[j][c] / P[0][c], j = 1..3
+    // launch_locate with pairs only: [4 syndrome rows][4][kTabWords] = T (classical
+    // syndromes S = T * syn), then [2][14][kTabWords]: alpha_c^2 and alpha_c, c = 0..13
+    const uint32_t* pair_tabs = nullptr;
 };
 // a.len is the TRUE shard length: bytes at or past it take no part (a length
 // rounded up for a pitch would compare pad bytes).
@@ -162,7 +165,11 @@ constexpr uint32_t kLocateMaxBlocks = 2048;
 #endif
 static_assert(kLocateMaxBlocks >= 1 && kLocateMaxBlocks <= (1u << 23), "locate grid: 1 to 2^23 workgroups");
 constexpr uint32_t kSuspectUnexplained = 0x80000000u;  // hec.h HEC_SUSPECT_UNEXPLAINED
-hipError_t launch_locate(const VerifyArgs& v, bool aligned, hipStream_t stream);
+// pairs (hec.h hec_gpu_locate_corrupt_pairs_batch; needs v.pair_tabs): a column
+// no single shard explains sets the bits of the two shards that do, bit 31
+// only when no two do either. The same walk; the pair search runs behind a
+// ballot of its own, only in waves that hold such a column.
+hipError_t launch_locate(const VerifyArgs& v, bool aligned, bool pairs, hipStream_t stream);
 
 // Present masks of a repair from the suspects words (hec_gpu_repair_batch):
 // masks[s] = 0x3FFF & ~suspects[s] when the word names 1 to 4 shards and bit

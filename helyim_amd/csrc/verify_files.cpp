@@ -1,6 +1,7 @@
 // Scrub of a volume's shard files base.ec00 .. base.ec13 (hec_verify_ec_files,
 // and hec_locate_corrupt_ec_files: the same walk with the locate pass, which
-// also names the wrong shard file of each bad block; and
+// also names the wrong shard file of each bad block;
+// hec_locate_corrupt_pairs_ec_files: that walk naming two files per column; and
 // hec_locate_corrupt_ec_files_present: that walk over a degraded volume, its
 // missing files treated as erased shards).
 //
@@ -70,16 +71,20 @@ void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, u
         err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off + uint64_t(got)));
 }
 
-// locate: every launch is run_locate instead of run_verify, a chunk's suspects
-// words follow its mismatch words at +per_chunk in the same result buffers,
-// and the bad blocks go to sus[] with their suspects word instead of to bad[].
+enum class ScrubMode { Verify, Locate, LocatePairs };
+
+// mode Locate / LocatePairs: every launch is run_locate instead of run_verify
+// (LocatePairs: with the pair search), a chunk's suspects words follow its
+// mismatch words at +per_chunk in the same result buffers, and the bad blocks
+// go to sus[] with their suspects word instead of to bad[].
 // degraded (with locate): a missing file is an erased shard, not an error; its
 // row of a slot is neither read into nor read by the kernels, every launch is
 // run_locate_present with the volume's present mask, and the words are the
 // masked calls' (shard-index bits). *present_out (optional) = the files found.
-int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, hec_scrub_bad* bad,
+int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode, hec_scrub_bad* bad,
                          hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks,
                          bool degraded = false, uint32_t* present_out = nullptr) {
+    const bool locate = mode != ScrubMode::Verify;
     // files and sizes first: these failures need no device
     Fd fd[N];
     std::string names[N];
@@ -188,7 +193,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, bool locate, h
                                           wd + per_chunk + first, nullptr, nullptr, sc->stream);
             if (locate)
                 return run_locate(*gd, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first,
-                                  wd + per_chunk + first, nullptr, sc->stream);
+                                  wd + per_chunk + first, nullptr, sc->stream, mode == ScrubMode::LocatePairs);
             return run_verify(gd->encode, K, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first, nullptr,
                               sc->stream);
         };
@@ -229,14 +234,22 @@ int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scru
                         uint64_t* n_blocks) {
     uint64_t block;
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, false, bad, nullptr, cap, n_bad, n_blocks);
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Verify, bad, nullptr, cap, n_bad, n_blocks);
 }
 
 int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                                 size_t* n_bad, uint64_t* n_blocks) {
     uint64_t block;
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, true, nullptr, bad, cap, n_bad, n_blocks);
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks);
+}
+
+int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
+                                      size_t cap, size_t* n_bad, uint64_t* n_blocks) {
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::LocatePairs, nullptr, bad, cap, n_bad,
+                                     n_blocks);
 }
 
 int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
@@ -244,8 +257,8 @@ int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t bloc
     if (present_mask) *present_mask = 0;
     uint64_t block;
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, true, nullptr, bad, cap, n_bad, n_blocks, true,
-                                     present_mask);
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks,
+                                     true, present_mask);
 }
 
 }  // extern "C"

@@ -87,6 +87,19 @@ class _ScrubSuspect(ctypes.Structure):
                 ("suspects", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+def _locate_files(call, base_filename: str, block_size: int, cap: int):
+    """One of the two full-volume file locates -> (n_blocks, n_bad, entries)."""
+    if cap < 0:
+        raise ValueError("negative cap")
+    bad = (_ScrubSuspect * cap)() if cap else None
+    n_bad, n_blocks = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    check_ec(call(base_filename.encode(), block_size, bad, cap, ctypes.byref(n_bad), ctypes.byref(n_blocks)))
+    got = min(cap, n_bad.value)
+    return (int(n_blocks.value), int(n_bad.value),
+            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
+             for i in range(got)])
+
+
 def locate_corrupt_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024):
     """verify_ec_files that also names the corrupt file of each bad block
     (hec_locate_corrupt_ec_files). Returns ``(n_blocks, n_bad, bad)`` with
@@ -94,16 +107,19 @@ def locate_corrupt_ec_files(base_filename: str, block_size: int = 0, cap: int = 
     ``.ec(c)`` alone explains a byte column of the block, bit 31 = a column no
     single file explains. Reads only: to repair, delete the named ``.ecNN``
     and call ``rebuild_ec_files``."""
-    if cap < 0:
-        raise ValueError("negative cap")
-    bad = (_ScrubSuspect * cap)() if cap else None
-    n_bad, n_blocks = ctypes.c_size_t(0), ctypes.c_uint64(0)
-    check_ec(lib.hec_locate_corrupt_ec_files(base_filename.encode(), block_size, bad, cap, ctypes.byref(n_bad),
-                                             ctypes.byref(n_blocks)))
-    got = min(cap, n_bad.value)
-    return (int(n_blocks.value), int(n_bad.value),
-            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
-             for i in range(got)])
+    return _locate_files(lib.hec_locate_corrupt_ec_files, base_filename, block_size, cap)
+
+
+def locate_corrupt_pairs_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024):
+    """locate_corrupt_ec_files that also names two files per byte column
+    (hec_locate_corrupt_pairs_ec_files): the same result shape; a column that
+    ``.ec(a)`` and ``.ec(b)`` together explain sets bits a and b, bit 31 = a
+    column no one or two files explain. Reads only: when the named files
+    number at most four over all blocks and bit 31 is clear everywhere, delete
+    them and call ``rebuild_ec_files``. Three wrong files in one column may
+    name an intact pair (include/hec.h); the stricter call is
+    locate_corrupt_ec_files."""
+    return _locate_files(lib.hec_locate_corrupt_pairs_ec_files, base_filename, block_size, cap)
 
 
 def locate_corrupt_ec_files_present(base_filename: str, block_size: int = 0, cap: int = 1024):

@@ -300,6 +300,69 @@ int hec_gpu_repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_
                          uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_present_masks,
                          uint32_t* d_unrepaired, void* stream);
 
+/* Locate out to the code's radius: hec_gpu_locate_corrupt_batch that also names
+ * TWO wrong shards of a byte column. RS(10,4) has distance 5, so with all 14
+ * shards present two wrong shards at unknown positions are still decodable
+ * (2t + e <= 4 with e = 0 erased); the call above names one and answers bit 31
+ * for two. Opt-in: arguments, clearing rules, footprint promise (words
+ * [0, n_stripes) of d_mismatch and d_suspects, no other byte anywhere),
+ * stream order and argument errors are exactly hec_gpu_locate_corrupt_batch's;
+ * RS(10,4) only. d_mismatch and d_bad_stripes are exactly
+ * hec_gpu_verify_batch's. Result contract of d_suspects[s], with H and syn(o)
+ * as above, per byte column o < shard_len:
+ *   - syn(o) == 0: nothing;
+ *   - a shard c and a byte v != 0 with syn(o) == v * H[:,c]: bit c (the rule
+ *     above, unchanged: on such columns both calls give the same bits);
+ *   - otherwise, shards a < b and bytes v, w != 0 with syn(o) == v * H[:,a] ^
+ *     w * H[:,b]: bits a and b. The pair is unique (two explanations would
+ *     make at most four columns of H dependent);
+ *   - otherwise HEC_SUSPECT_UNEXPLAINED (bit 31).
+ * The stripe's word is the OR over its columns. Guarantees:
+ *   - a column with at most 2 wrong shards names exactly those shards;
+ *   - a column with 3 wrong shards never names a SINGLE intact shard, but it
+ *     may name an intact PAIR: 91 * 255^2 of the 2^32 syndromes (0.138 %) are
+ *     pair-explainable, and about that share of random triple errors (182 of
+ *     200,000 in a CPU count) comes back as a pair, each time with an intact
+ *     shard in it. This is the price of decoding to the radius;
+ *   - 4 or more wrong shards in one column: no guarantee;
+ *   - a caller who wants the stricter "at most 3 wrong shards never blame an
+ *     intact shard" keeps calling hec_gpu_locate_corrupt_batch.
+ * The degraded calls below have no pair form: with a shard missing one wrong
+ * shard is already the bound (2t + e <= 4).
+ * Pass 2 is the same kernel walk; only waves that hold a column no single
+ * shard explains run the pair search (classical syndromes of the dual
+ * generalised Reed-Solomon code, a quadratic error locator evaluated at the
+ * 14 shard points; DESIGN.md §4 "Locate, two per column"). Measured on one
+ * MI355X, 4096 x 1 MiB stripes, medians of 9 alternating rounds
+ * (tools/bench_locate_pairs.py, profiles/locate_pairs/bench_locate_pairs.json):
+ * on the clean batch hec_gpu_locate_corrupt_batch 9.45 ms (9.38..9.78 over the
+ * rounds) and this call 9.46 ms, inside that spread; with 64 stripes holding
+ * one flipped byte 9.59 ms and 9.66 ms; with 64 stripes where two shards carry
+ * a corrupted 4 KiB run at the same offset this call 9.68 ms. */
+int hec_gpu_locate_corrupt_pairs_batch(const hec_rs_t* rs,
+                                       const uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                                       const uint8_t* d_parity, uint64_t parity_stripe_stride,
+                                       uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                       uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                                       void* stream);
+
+/* hec_gpu_repair_batch over hec_gpu_locate_corrupt_pairs_batch's words: the
+ * same three steps, arguments, footprint and errors, with step (1) the pair
+ * locate. Whole shards per stripe, as there: a stripe whose columns name 1 to
+ * 4 shards in total with bit 31 clear has those shards rebuilt from the other
+ * ten or more; any other stripe (five or more shards named over its columns,
+ * or bit 31) is left byte for byte and counted into *d_unrepaired. So a stripe
+ * with two shards wrong in one column and a third wrong elsewhere is repaired
+ * here and left alone by hec_gpu_repair_batch. The repair trusts the
+ * guarantees above. hec_gpu_verify_batch afterwards shows that every repaired
+ * stripe is a codeword again; in the three-wrong-shards case named as a pair
+ * it is a codeword 5 shards away from the one written, which no parity check
+ * can tell apart: a caller who cannot accept that keeps hec_gpu_repair_batch. */
+int hec_gpu_repair_pairs_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                               uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                               uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_present_masks,
+                               uint32_t* d_unrepaired, void* stream);
+
 /* ---- degraded scrub: check and locate with shards missing (RS(10,4)) -------
  * The calls above need all 14 shards. These take hec_gpu_reconstruct_batch's
  * in-place layout and d_present_masks (bit i set = shard i present) and use
@@ -548,6 +611,19 @@ typedef struct hec_scrub_suspect {
 } hec_scrub_suspect;
 int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                                 size_t* n_bad, uint64_t* n_blocks);
+/* hec_locate_corrupt_ec_files with hec_gpu_locate_corrupt_pairs_batch's
+ * suspects words: arguments, struct, block rules, errors and the read-only
+ * promise are identical; a byte column that two files explain sets both
+ * their bits instead of bit 31 (the same torn sector in two files, a stale
+ * file plus one bit-rot). Recipe: take the union of the named files over all
+ * bad blocks; when it holds at most four files and bit 31 is clear everywhere,
+ * delete the named .ecNN and call hec_rebuild_ec_files, then scrub again. With
+ * five or more files named in total or bit 31 set somewhere, rebuild nothing
+ * from the volume as a whole. The guarantees and their limit (three wrong
+ * files in one column may name an intact pair) are those of
+ * hec_gpu_locate_corrupt_pairs_batch. */
+int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
+                                      size_t cap, size_t* n_bad, uint64_t* n_blocks);
 /* hec_locate_corrupt_ec_files for a degraded volume: a missing .ecNN (ENOENT)
  * is an erased shard, not an error. *present_mask (optional) reports which
  * files were found (bit i = base.ec(i)). Each entry's parity_mask field
