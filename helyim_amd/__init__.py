@@ -27,6 +27,7 @@ from .ec import (  # noqa: F401
     rebuild_ecx_file, save_volume_info, to_ext, ec_shard_filename, ec_shard_base_filename, volume_ec_shards_generate, volume_ec_shards_rebuild,
     write_data_file, write_ec_files, write_index_file_from_ec_index, write_sorted_file_from_index,
     verify_ec_files, locate_corrupt_ec_files, locate_corrupt_ec_files_present, locate_corrupt_pairs_ec_files,
+    correct_ec_files,
 )
 
 SUSPECT_UNEXPLAINED = 0x80000000  # include/hec.h HEC_SUSPECT_UNEXPLAINED
@@ -34,6 +35,7 @@ SUSPECT_UNEXPLAINED = 0x80000000  # include/hec.h HEC_SUSPECT_UNEXPLAINED
 _BATCH_VERIFY = ("verify_batch", "verify_batch_sep", "host_verify_batch", "verify_kernel_name",
                  "locate_corrupt_batch", "locate_corrupt_batch_sep", "repair_batch",
                  "locate_corrupt_pairs_batch", "locate_corrupt_pairs_batch_sep", "repair_pairs_batch",
+                 "correct_batch", "correct_batch_sep",
                  "verify_present_batch", "locate_corrupt_present_batch", "reconstruct_checked_batch",
                  "check_kernel_name")
 

@@ -66,6 +66,10 @@ SIGNATURES = {
     "hec_locate_corrupt_ec_files": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S), ctypes.POINTER(_U64)]),
     "hec_locate_corrupt_pairs_ec_files": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S),
                                                ctypes.POINTER(_U64)]),
+    "hec_gpu_correct_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P]),
+    "hec_gpu_correct_pairs_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P]),
+    "hec_correct_ec_files": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S), ctypes.POINTER(_U64)]),
+    "hec_correct_pairs_ec_files": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S), ctypes.POINTER(_U64)]),
     "hec_gpu_verify_present_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P]),
     "hec_gpu_locate_corrupt_present_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P]),
     "hec_gpu_reconstruct_checked_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P, _P]),

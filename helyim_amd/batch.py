@@ -247,6 +247,64 @@ def repair_pairs_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.T
     return _repair(lib.hec_gpu_repair_pairs_batch, rs, stripes, mismatch, suspects, present_masks, unrepaired, stream)
 
 
+def _bytes_counter_arg(t: torch.Tensor, name: str):
+    """An optional accumulated 64-bit device word (corrected_bytes) -> its pointer or None."""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.numel() >= 1):
+        raise ValueError(f"{name} must be a 64-bit CUDA tensor")
+    _check_device(t)
+    return t.data_ptr()
+
+
+def correct_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
+                  suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, uncorrected: torch.Tensor = None,
+                  corrected_bytes: torch.Tensor = None, pairs: bool = False, stream=None):
+    """Locate, and fix in place every byte column one shard explains
+    (hec_gpu_correct_batch, RS(10,4) only; ``pairs=True``: also the columns two
+    shards explain, hec_gpu_correct_pairs_batch). Returns ``(mismatch,
+    suspects)`` as locate_corrupt_batch (locate_corrupt_pairs_batch), of the
+    bytes as they were before the call. Only wrong bytes of explained columns
+    change; a column that sets bit 31 keeps its bytes while the stripe's other
+    columns are still fixed. uncorrected (32-bit CUDA word, accumulated): plus
+    one per stripe with bit 31; corrected_bytes (64-bit CUDA word,
+    accumulated): the bytes changed. Unlike repair_batch this also restores a
+    stripe whose columns name five or more shards. Asynchronous on the
+    stream."""
+    _check_stripes(stripes, rs)
+    k = rs.data_shard_count()
+    S, n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    call = lib.hec_gpu_correct_pairs_batch if pairs else lib.hec_gpu_correct_batch
+    check(call(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
+               _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
+               _stream_ptr(stream)))
+    return mismatch, suspects
+
+
+def correct_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, mismatch: torch.Tensor = None,
+                      suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                      uncorrected: torch.Tensor = None, corrected_bytes: torch.Tensor = None, pairs: bool = False,
+                      stream=None):
+    """correct_batch of data[S, k, L] and the stored parity[S, m, L] (separate buffers, both fixed in place)."""
+    _check_stripes(data, rs, rs.data_shard_count())
+    _check_stripes(parity, rs, rs.parity_shard_count())
+    S, k, L = data.shape
+    if parity.shape[0] != S or parity.shape[2] != L:
+        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    call = lib.hec_gpu_correct_pairs_batch if pairs else lib.hec_gpu_correct_batch
+    check(call(rs.handle, data.data_ptr(), data.stride(0), data.stride(1), parity.data_ptr(), parity.stride(0),
+               parity.stride(1), L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
+               _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
+               _stream_ptr(stream)))
+    return mismatch, suspects
+
+
 def _masks_arg(S: int, present_masks: torch.Tensor) -> torch.Tensor:
     if not (present_masks.is_cuda and present_masks.dtype in (torch.int32, torch.uint32)
             and present_masks.numel() == S and present_masks.is_contiguous()):

@@ -68,4 +68,19 @@ inline ssize_t pread_full(int fd, uint8_t* dst, size_t n, uint64_t off) {
     return ssize_t(got);
 }
 
+// pwrite until n bytes are written, retrying EINTR and short writes; false
+// with errno set on an error.
+inline bool pwrite_full(int fd, const uint8_t* src, size_t n, uint64_t off) {
+    size_t put = 0;
+    while (put < n) {
+        const ssize_t w = ::pwrite(fd, src + put, n - put, off_t(off + put));
+        if (w < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        put += size_t(w);
+    }
+    return true;
+}
+
 }  // namespace hec

@@ -147,6 +147,45 @@ int hec_gpu_locate_corrupt_pairs_batch(const hec_rs_t* rs, const uint8_t* d_data
                         true);
 }
 
+// hec_gpu_correct_batch and its pairs form: one body.
+static int correct_batch(const hec_rs_t* rs, uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                         uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                         uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,
+                         uint32_t* d_bad_stripes, uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes,
+                         void* stream, bool pairs) {
+    HEC_TRY(check_batch_args(rs, d_data, d_parity, shard_len));
+    HEC_TRY(check_verify_args(rs, d_mismatch));
+    HEC_TRY(check_locate_args(rs, d_suspects));
+    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
+                                 parity_shard_stride, shard_len, n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    return run_correct(*gd, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
+                       parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes,
+                       d_uncorrected, d_corrected_bytes, static_cast<hipStream_t>(stream), pairs);
+}
+
+int hec_gpu_correct_batch(const hec_rs_t* rs, uint8_t* d_data, uint64_t data_stripe_stride,
+                          uint64_t data_shard_stride, uint8_t* d_parity, uint64_t parity_stripe_stride,
+                          uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch,
+                          uint32_t* d_suspects, uint32_t* d_bad_stripes, uint32_t* d_uncorrected,
+                          unsigned long long* d_corrected_bytes, void* stream) {
+    return correct_batch(rs, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
+                         parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes,
+                         d_uncorrected, d_corrected_bytes, stream, false);
+}
+
+int hec_gpu_correct_pairs_batch(const hec_rs_t* rs, uint8_t* d_data, uint64_t data_stripe_stride,
+                                uint64_t data_shard_stride, uint8_t* d_parity, uint64_t parity_stripe_stride,
+                                uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                                uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes, void* stream) {
+    return correct_batch(rs, d_data, data_stripe_stride, data_shard_stride, d_parity, parity_stripe_stride,
+                         parity_shard_stride, shard_len, n_stripes, d_mismatch, d_suspects, d_bad_stripes,
+                         d_uncorrected, d_corrected_bytes, stream, true);
+}
+
 // hec_gpu_repair_batch and its pairs form: one body.
 static int repair_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride, uint64_t shard_stride,
                         uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch, uint32_t* d_suspects,

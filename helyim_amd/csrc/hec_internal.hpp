@@ -226,6 +226,9 @@ struct GeomDevice {
     // VerifyArgs::pair_tabs): plan 0 = T, 4 x 4, classical syndromes S = T *
     // syn; plan 1 = 14 rows (alpha_c^2, alpha_c) over the inputs (D, N1)
     DevicePlanSet locate_pairs;
+    // RS(10,4) only: the correct kernel's constants (rs_kernels.hpp
+    // CorrectArgs::fix_tabs): plan 0 = 1 / P[0][c], 1 x 10; plan 1 = 1 / u_c, 1 x 14
+    DevicePlanSet correct;
     // RS(10,4) only, built on first use (ensure_check_plans): the degraded
     // scrub's plans. check: a dense LUT over the 2^14 present masks to one
     // plan per mask with 11 or more shards present (inputs B, outputs E,
@@ -464,6 +467,13 @@ inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
 int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
                const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
                uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s, bool pairs = false);
+// hec_gpu_correct_batch: run_locate with pass 2 fixing the columns it explains
+// in place (rs_kernels.hpp launch_correct). uncorrected, corrected_bytes:
+// optional device counters, accumulated.
+int run_correct(const GeomDevice& gd, uint8_t* data, uint64_t data_stripe, uint64_t data_shard, uint8_t* parity,
+                uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
+                uint32_t* suspects, uint32_t* bad, uint32_t* uncorrected, unsigned long long* corrected_bytes,
+                hipStream_t s, bool pairs);
 // The locate entry points' extra argument checks, after check_verify_args.
 inline int check_locate_args(const hec_rs* rs, const void* suspects) {
     if (!suspects) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");

@@ -187,6 +187,25 @@ int geom_device(const hec_rs* rs, GeomDevice** out) {
         pp.add(t, {0, 1, 2, 3}, {0, 1, 2, 3});
         pp.add(roots, {0, 1}, all_ids);
         if ((rc = gd->locate_pairs.upload(pp, nullptr, nullptr))) return rc;
+        // the correct kernel's constants (rs_kernels.hpp CorrectArgs::fix_tabs):
+        // 1 / P[0][c], the value of a wrong data shard from s[0], and 1 / u_c,
+        // the pair values' last factor. Both checked by multiplying back.
+        Mat inv_p0(1, rs->k), inv_u(1, n);
+        for (int c = 0; c < rs->k; ++c) {
+            inv_p0.at(0, c) = g.inv(par.at(0, c));
+            if (g.mul[par.at(0, c)][inv_p0.at(0, c)] != 1)
+                return fail(HEC_ERR_INVALID_ARGUMENT, "1 / P[0][c] does not multiply back to 1");
+        }
+        for (int c = 0; c < n; ++c) {
+            inv_u.at(0, c) = g.inv(dual.at(0, c));  // H'[0][c] = u_c
+            if (g.mul[dual.at(0, c)][inv_u.at(0, c)] != 1)
+                return fail(HEC_ERR_INVALID_ARGUMENT, "1 / u_c does not multiply back to 1");
+        }
+        HostPlans cp;
+        cp.add(inv_p0, in_ids, {0});
+        if (cp.add(inv_u, all_ids, {0}) != 1 || cp.plans[1].tab_off != uint32_t(kFixInvU))
+            return fail(HEC_ERR_INVALID_ARGUMENT, "correct plan layout");
+        if ((rc = gd->correct.upload(cp, nullptr, nullptr))) return rc;
     }
     *out = gd.get();
     g_geom[key] = std::move(gd);
@@ -367,6 +386,29 @@ int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, 
     v.pair_tabs = gd.locate_pairs.tabs;
     HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
     HEC_HIP(launch_locate(v, aligned, pairs, s));
+    return HEC_OK;
+}
+
+int run_correct(const GeomDevice& gd, uint8_t* data, uint64_t data_stripe, uint64_t data_shard, uint8_t* parity,
+                uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
+                uint32_t* suspects, uint32_t* bad, uint32_t* uncorrected, unsigned long long* corrected_bytes,
+                hipStream_t s, bool pairs) {
+    if (n_stripes == 0) return HEC_OK;
+    // pass 1: run_locate's
+    HEC_TRY(run_verify(gd.encode, 10, data, data_stripe, data_shard, parity, parity_stripe, parity_shard, len,
+                       n_stripes, mismatch, bad, s));
+    // pass 2: the locate's walk, fixing what it explains
+    CorrectArgs c{};
+    const bool aligned = fill_verify_args(c, gd.encode, data, data_stripe, data_shard, parity, parity_stripe,
+                                          parity_shard, len, n_stripes, mismatch, nullptr);
+    c.suspects = suspects;
+    c.ratio_tabs = gd.locate.tabs;
+    c.pair_tabs = gd.locate_pairs.tabs;
+    c.fix_tabs = gd.correct.tabs;
+    c.uncorrected = uncorrected;
+    c.corrected_bytes = corrected_bytes;
+    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_correct(c, aligned, pairs, s));
     return HEC_OK;
 }
 

@@ -27,7 +27,9 @@
 //  * The locate kernel (rs104_locate_kernel) is the scrub's second pass: it
 //    reads only the stripes the verify flagged and names the wrong shard of
 //    each byte column from its syndrome; its PAIRS form also names two wrong
-//    shards of a column (an error-locator step on the bytes left unexplained).
+//    shards of a column (an error-locator step on the bytes left unexplained);
+//    its CORRECT form (rs104_correct_kernel) also fixes, in place, every byte
+//    the names explain.
 //  * The masked verify and locate (rs104_check_kernel and siblings) are the
 //    degraded scrub: the mask-driven decode with its stores replaced by a
 //    compare against the spare present shards.
@@ -770,6 +772,7 @@ static void set_fast_map(ApplyArgs& a, uint32_t chunk_bytes, bool round_up) {
 static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
 static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
+static ApplyArgs& apply_args(CorrectArgs& c) { return c.a; }
 
 // A fast-mapped batch (set_fast_map), one workgroup per item: k32 where every
 // byte offset inside a shard fits 32 bits, k64 for shards of 4 GiB and more.
@@ -1009,6 +1012,50 @@ __device__ __forceinline__ uint32_t dword_of(const u32x4 v, int w) {
     return w == 0 ? v[0] : w == 1 ? v[1] : w == 2 ? v[2] : v[3];
 }
 
+// 1 / x bytewise (0 for 0): x^254 = (x^127)^2, x^127 the product of x^(2^i), i = 0..6.
+__device__ __forceinline__ uint32_t gf_inv_var(const uint32_t x) {
+    uint32_t p = x, acc = x;
+#pragma unroll 1
+    for (int i = 0; i < 6; ++i) {
+        p = gf_mul_var(p, p);
+        acc = gf_mul_var(acc, p);
+    }
+    return gf_mul_var(acc, acc);
+}
+
+// Correct (rs104_correct_kernel): the item a workgroup is fixing (uniform; the
+// addresses are derived from the kernel's arguments where a fix needs them,
+// not kept in registers across the walk) and how many bytes this lane has
+// changed.
+struct FixLane {
+    const ApplyArgs* a;
+    uint32_t stripe, chunk;
+    uint32_t changed;
+};
+
+struct NoFix {};  // the locate kernel's
+
+// XOR the error vector e into this lane's vector of shard c (wave-uniform).
+// Only a lane with an error for c touches c; e is zero in columns at or past
+// the shard's end (their syndrome is zero), and the last partial vector goes
+// through load_tail / store_tail, so no byte past the end is written.
+template <bool ALIGNED>
+__device__ __forceinline__ void fix_shard(FixLane& f, int c, const u32x4 e) {
+    if ((e[0] | e[1] | e[2] | e[3]) == 0) return;
+    const ApplyArgs& a = *f.a;
+    const uint64_t o = uint64_t(f.chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;  // < a.len: an error here
+    uint8_t* p = (c < 10 ? const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard
+                         : a.out_base + uint64_t(f.stripe) * a.out_stripe + uint64_t(c - 10) * a.out_shard) +
+                 o;
+    const uint64_t avail = a.len - o;
+    if (avail >= kVecBytes)
+        store_full(p, load_full(p, ALIGNED) ^ e, ALIGNED);
+    else
+        store_tail(p, load_tail(p, avail) ^ e, avail);
+    f.changed += uint32_t(__builtin_popcount(nz_bytes(e[0])) + __builtin_popcount(nz_bytes(e[1])) +
+                          __builtin_popcount(nz_bytes(e[2])) + __builtin_popcount(nz_bytes(e[3])));
+}
+
 constexpr int kPairSynWords = 4 * 4 * 5;  // T's tables; the root tables follow
 
 // s: the syndrome of this lane's 16 columns; unx[w]: 0x80 in the bytes of dword
@@ -1018,7 +1065,10 @@ constexpr int kPairSynWords = 4 * 4 * 5;  // T's tables; the root tables follow
 // = N1 with alpha_c, row c. One dword per round and a rolled loop over the
 // shards: the registers of one round, not of four at once (the kernel keeps
 // the single-shard kernel's occupancy).
-__device__ __forceinline__ uint32_t rs104_pair_search(const u32x4 (&s)[4], u32x4& unx, cu32p pt) {
+template <bool ALIGNED = false, bool CORRECT = false>
+__device__ __forceinline__ uint32_t rs104_pair_search(const u32x4 (&s)[4], u32x4& unx, cu32p pt,
+                                                      [[maybe_unused]] FixLane* fx = nullptr,
+                                                      [[maybe_unused]] cu32p inv_u = nullptr) {
     constexpr int N = 14;
     cu32p rt = pt + kPairSynWords;
     uint32_t named = 0;
@@ -1051,6 +1101,26 @@ __device__ __forceinline__ uint32_t rs104_pair_search(const u32x4 (&s)[4], u32x4
         const uint32_t keep = (two >> 7) * 0xFFu;
         lo &= keep;
         hi &= keep;
+        if constexpr (CORRECT) {
+            // the two values of a named pair (above): e_c = (X ^ alpha_c * Y) / u_c
+            // with q = D / N1, X = q * S1 ^ S0, Y = q * S0. N1 = D (a ^ b) is
+            // non-zero in every named byte; the others are masked out by the
+            // root flags (gf_inv_var(0) = 0 there).
+            if (__ballot(two != 0) != 0) {  // wave-uniform
+                const uint32_t q = gf_mul_var(D, gf_inv_var(N1));
+                const uint32_t Y = gf_mul_var(q, S[0]);
+                const uint32_t X = gf_mul_var(q, S[1]) ^ S[0];
+#pragma unroll 1
+                for (int c = 0; c < N; ++c) {
+                    const uint32_t is_root = ((c < 8 ? lo >> c : hi >> (c - 8)) & 0x01010101u) * 0xFFu;
+                    if (__ballot(is_root != 0) == 0) continue;  // wave-uniform: nobody fixes shard c
+                    const uint32_t e =
+                        gf_mul_const(X ^ gf_mul_const(Y, rt + (N + c) * 5), inv_u + c * 5) & is_root;
+                    fix_shard<ALIGNED>(*fx, c, u32x4{w == 0 ? e : 0u, w == 1 ? e : 0u, w == 2 ? e : 0u,
+                                                     w == 3 ? e : 0u});
+                }
+            }
+        }
         lo |= lo >> 16;
         hi |= hi >> 16;
         named |= ((lo | (lo >> 8)) & 0xFFu) | (((hi | (hi >> 8)) & 0x3Fu) << 8);
@@ -1061,13 +1131,29 @@ __device__ __forceinline__ uint32_t rs104_pair_search(const u32x4 (&s)[4], u32x4
     return named;
 }
 
-// PAIRS: bytes the single-shard method leaves unexplained go on to
-// rs104_pair_search; everything up to there is the same code. The pairs
-// instantiation asks for the five waves per SIMD the other one gets unasked
-// (95 VGPRs): without the bound it takes 103 VGPRs and four waves, and a clean
-// batch would pay for code it never reaches (profiles/locate_pairs/isa.md).
-template <bool ALIGNED, bool PAIRS = false>
-__global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(VerifyArgs v) {
+// The walk of the locate and the correct kernels. PAIRS: bytes the single-shard
+// method leaves unexplained go on to rs104_pair_search; everything up to there
+// is the same code.
+//
+// CORRECT (rs104_correct_kernel, hec.h hec_gpu_correct_batch): the same walk;
+// where a column is explained the lane also computes the error value the
+// classification implies and XORs it into the wrong byte (fix_shard): s[j] for
+// parity shard 10 + j, s[0] / P[0][c] for data shard c, the pair search's two
+// values. A lane's 16 columns belong to no other lane and its syndrome is
+// complete before its first store, so names and values are those of the bytes
+// as they were. Unexplained columns are not touched.
+//
+// The pairs instantiation asks for the five waves per SIMD the other one gets
+// unasked (95 VGPRs): without the bound it takes 103 VGPRs and four waves, and
+// a clean batch would pay for code it never reaches
+// (profiles/locate_pairs/isa.md). The correct forms ask for four: unasked they
+// take 130 / 135 VGPRs and three waves, and the clean walk, a chain of
+// dependent scalar loads that lives on resident waves, measured outside the
+// locate's spread; at four (128 VGPRs, 16 / 32 bytes of scratch in the fix
+// paths) it is inside (profiles/correct/isa.md, bench_correct.json).
+template <bool ALIGNED, bool PAIRS = false, bool CORRECT = false>
+__global__ __launch_bounds__(kThreads, CORRECT ? 4 : PAIRS ? 5 : 1) void rs104_locate_kernel(
+    std::conditional_t<CORRECT, CorrectArgs, VerifyArgs> v) {
     constexpr int K = 10, R = 4;
     const ApplyArgs& a = v.a;
     cu32p tab = as_const(a.tabs);        // encode plan: [K][R][5] words
@@ -1107,6 +1193,9 @@ __global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(V
 #pragma unroll
         for (int j = 0; j < R; ++j) any |= s[j][0] | s[j][1] | s[j][2] | s[j][3];
         if (__ballot(any != 0) == 0) continue;  // wave-uniform: this wave's 1 KiB is clean
+        [[maybe_unused]] std::conditional_t<CORRECT, FixLane, NoFix> fx;
+        if constexpr (CORRECT)
+            fx = FixLane{&a, stripe, chunk, 0};
 
         uint32_t one[R] = {0, 0, 0, 0};  // bytes where only s[j] is non-zero
         uint32_t all4[4];                // per dword: bytes where all four are
@@ -1144,8 +1233,16 @@ __global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(V
                     const uint32_t m = all4[w] & ~nz_bytes(diff);
                     matched[w] |= m;
                     hit |= m;
+                    if constexpr (CORRECT) e[0][w] = (m >> 7) * 0xFFu;  // the ratios are spent: the bytes c explains
                 }
                 bits |= (__ballot(hit != 0) != 0 ? 1u : 0u) << c;
+                if constexpr (CORRECT) {
+                    if (__ballot(hit != 0) != 0) {  // wave-uniform: somebody fixes data shard c
+                        u32x4 val[1] = {u32x4{0, 0, 0, 0}};
+                        gf_mac<1>(val, s[0], as_const(v.fix_tabs) + c * 5);  // s[0] / P[0][c]
+                        fix_shard<ALIGNED>(fx, c, val[0] & e[0]);
+                    }
+                }
             }
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
@@ -1155,7 +1252,12 @@ __global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(V
         }
         if constexpr (PAIRS) {
             if (__ballot(unexplained != 0) != 0) {  // wave-uniform: some column may name two shards
-                const uint32_t two = rs104_pair_search(s, unx, as_const(v.pair_tabs));
+                uint32_t two;
+                if constexpr (CORRECT)
+                    two = rs104_pair_search<ALIGNED, true>(s, unx, as_const(v.pair_tabs), &fx,
+                                                           as_const(v.fix_tabs) + kFixInvU);
+                else
+                    two = rs104_pair_search(s, unx, as_const(v.pair_tabs));
 #pragma unroll
                 for (int c = 0; c < K + R; ++c) bits |= (__ballot(((two >> c) & 1u) != 0) != 0 ? 1u : 0u) << c;
                 unexplained = unx[0] | unx[1] | unx[2] | unx[3];
@@ -1164,8 +1266,50 @@ __global__ __launch_bounds__(kThreads, PAIRS ? 5 : 1) void rs104_locate_kernel(V
 #pragma unroll
         for (int j = 0; j < R; ++j) bits |= (__ballot(one[j] != 0) != 0 ? 1u : 0u) << (K + j);
         if (__ballot(unexplained != 0) != 0) bits |= kSuspectUnexplained;
-        if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+        if constexpr (!CORRECT) {
+            if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+        } else {
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                if (__ballot(one[j] != 0) == 0) continue;  // wave-uniform: nobody fixes parity shard j
+                u32x4 e;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t others = 0;
+#pragma unroll
+                    for (int i = 0; i < R; ++i)
+                        if (i != j) others |= nz_bytes(s[i][w]);
+                    e[w] = s[j][w] & ((nz_bytes(s[j][w]) & ~others) >> 7) * 0xFFu;
+                }
+                fix_shard<ALIGNED>(fx, K + j, e);
+            }
+            // the bytes this wave changed, at most 32 a lane: six ballots
+            uint32_t total = 0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                total += uint32_t(__builtin_popcountll(__ballot(((fx.changed >> k) & 1u) != 0))) << k;
+            if ((threadIdx.x & 63u) == 0) {
+                // the atomicOr that first sets bit 31 counts the stripe
+                if (bits != 0 && (atomicOr(v.suspects + stripe, bits) & kSuspectUnexplained) == 0 &&
+                    (bits & kSuspectUnexplained) != 0 && v.uncorrected)
+                    atomicAdd(v.uncorrected, 1u);
+                if (total != 0 && v.corrected_bytes) atomicAdd(v.corrected_bytes, (unsigned long long)total);
+            }
+        }
     }
+}
+
+// rs104_correct_kernel<ALIGNED, PAIRS>: the locate kernel's CORRECT form, taking CorrectArgs.
+template <bool ALIGNED, bool PAIRS>
+constexpr auto rs104_correct_kernel = rs104_locate_kernel<ALIGNED, PAIRS, true>;
+
+hipError_t launch_correct(const CorrectArgs& c, bool aligned, bool pairs, hipStream_t stream) {
+    if (c.a.n_stripes == 0 || c.a.len == 0) return hipSuccess;
+    if (pairs)
+        return launch_stride(aligned ? rs104_correct_kernel<true, true> : rs104_correct_kernel<false, true>, c, stream,
+                             kLocateMaxBlocks);
+    return launch_stride(aligned ? rs104_correct_kernel<true, false> : rs104_correct_kernel<false, false>, c, stream,
+                         kLocateMaxBlocks);
 }
 
 hipError_t launch_locate(const VerifyArgs& v, bool aligned, bool pairs, hipStream_t stream) {

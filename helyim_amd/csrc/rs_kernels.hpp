@@ -171,6 +171,19 @@ constexpr uint32_t kSuspectUnexplained = 0x80000000u;  // hec.h HEC_SUSPECT_UNEX
 // ballot of its own, only in waves that hold such a column.
 hipError_t launch_locate(const VerifyArgs& v, bool aligned, bool pairs, hipStream_t stream);
 
+// Correct (hec.h hec_gpu_correct_batch): launch_locate's pass with one
+// addition -- where a column is explained, the error value is computed too and
+// XORed into the wrong byte(s) of v.a.in_base / v.a.out_base, in place.
+// Columns that set bit 31 are left as they are. The words are the locate's,
+// of the bytes as they were.
+constexpr int kFixInvU = 10 * 5;  // word offset of the second table set of fix_tabs
+struct CorrectArgs : VerifyArgs {        // as for launch_locate (pair_tabs with pairs), and:
+    const uint32_t* fix_tabs = nullptr;   // [10][kTabWords]: 1 / P[0][c]; then [14][kTabWords]: 1 / u_c
+    uint32_t* uncorrected = nullptr;      // optional: += stripes that get bit 31
+    unsigned long long* corrected_bytes = nullptr;  // optional: += bytes changed
+};
+hipError_t launch_correct(const CorrectArgs& c, bool aligned, bool pairs, hipStream_t stream);
+
 // Present masks of a repair from the suspects words (hec_gpu_repair_batch):
 // masks[s] = 0x3FFF & ~suspects[s] when the word names 1 to 4 shards and bit
 // 31 is clear, else 0x3FFF (the reconstruct's no-op); *unrepaired (optional)

@@ -3,7 +3,8 @@
 // also names the wrong shard file of each bad block;
 // hec_locate_corrupt_pairs_ec_files: that walk naming two files per column; and
 // hec_locate_corrupt_ec_files_present: that walk over a degraded volume, its
-// missing files treated as erased shards).
+// missing files treated as erased shards; hec_correct_ec_files and its pairs
+// form: the locate walk with the correct pass, whose fixes are written back).
 //
 // RS parity is bytewise: byte o of every parity file is a function of byte o
 // of the ten data files, whatever large / small block geometry laid the .dat
@@ -12,7 +13,10 @@
 // geometry. Chunks of whole blocks are pread into two pinned slots (shard
 // major: [14][chunk columns]); the verify kernels read a slot in place over
 // PCIe while the preads of the next chunk fill the other slot, and only one
-// word per block comes back. The files are opened read-only.
+// word per block comes back. The files are opened read-only, except by the
+// correct calls: their kernel fixes the slot in place (its stores cross PCIe
+// like the zero-copy encode's) and the changed rows of each bad block are
+// written back to their files.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -71,12 +75,17 @@ void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, u
         err.set(HEC_ERR_IO, "short read of " + name + " at offset " + std::to_string(off + uint64_t(got)));
 }
 
-enum class ScrubMode { Verify, Locate, LocatePairs };
+enum class ScrubMode { Verify, Locate, LocatePairs, Correct, CorrectPairs };
 
 // mode Locate / LocatePairs: every launch is run_locate instead of run_verify
 // (LocatePairs: with the pair search), a chunk's suspects words follow its
 // mismatch words at +per_chunk in the same result buffers, and the bad blocks
 // go to sus[] with their suspects word instead of to bad[].
+// mode Correct / CorrectPairs: the files are opened for writing, every launch
+// is run_correct, and once a chunk's event has fired each bad block's rows of
+// the shards its suspects word names are written back at the block's offset:
+// the only bytes of any file that are written. Every file written is
+// fdatasync'ed once before the return.
 // degraded (with locate): a missing file is an erased shard, not an error; its
 // row of a slot is neither read into nor read by the kernels, every launch is
 // run_locate_present with the volume's present mask, and the words are the
@@ -85,6 +94,8 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
                          hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks,
                          bool degraded = false, uint32_t* present_out = nullptr) {
     const bool locate = mode != ScrubMode::Verify;
+    const bool correct = mode == ScrubMode::Correct || mode == ScrubMode::CorrectPairs;
+    const bool pairs = mode == ScrubMode::LocatePairs || mode == ScrubMode::CorrectPairs;
     // files and sizes first: these failures need no device
     Fd fd[N];
     std::string names[N];
@@ -92,7 +103,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
     uint32_t present = 0;
     for (int i = 0; i < N; ++i) {
         names[i] = shard_name(base, i);
-        fd[i].fd = ::open(names[i].c_str(), O_RDONLY);
+        fd[i].fd = ::open(names[i].c_str(), correct ? O_RDWR : O_RDONLY);
         if (fd[i].fd < 0) {
             if (errno == ENOENT && degraded) continue;
             if (errno == ENOENT) return fail(HEC_ERR_SHARD_NOT_FOUND, "no shard file " + names[i]);
@@ -146,6 +157,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
     const uint64_t total_blocks = (size + block - 1) / block;
     const uint64_t n_chunks = (size + cols - 1) / cols;
     size_t found = 0;
+    bool written[N] = {};
     auto chunk_len = [&](uint64_t c) { return std::min(cols, size - c * cols); };
     // results of chunk c (its words are in words_host[c & 1] once done[c & 1] fired)
     auto collect = [&](uint64_t c) -> int {
@@ -162,6 +174,16 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
             else if (found < cap)
                 bad[found] = hec_scrub_bad{offset, length, w};
             ++found;
+            if (!correct) continue;
+            // the rows the kernel changed: the shards the block's word names
+            const uint32_t named = sc->words_host[q][per_chunk + b] & ((1u << N) - 1);
+            for (int i = 0; i < N; ++i) {
+                if (!((named >> i) & 1u)) continue;
+                const uint8_t* slot = sc->slot[q];
+                const uint8_t* row = slot + uint64_t(i) * pitch + b * block;
+                if (!pwrite_full(fd[i].fd, row, length, offset)) return io("write " + names[i]);
+                written[i] = true;
+            }
         }
         return HEC_OK;
     };
@@ -191,9 +213,13 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
             if (degraded)
                 return run_locate_present(*gd, d, block, pitch, blen, uint32_t(n), sc->masks_dev, wd + first,
                                           wd + per_chunk + first, nullptr, nullptr, sc->stream);
+            if (correct)
+                return run_correct(*gd, zs[q] + first * block, block, pitch, zs[q] + first * block + uint64_t(K) * pitch,
+                                   block, pitch, blen, uint32_t(n), wd + first, wd + per_chunk + first, nullptr, nullptr,
+                                   nullptr, sc->stream, pairs);
             if (locate)
                 return run_locate(*gd, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first,
-                                  wd + per_chunk + first, nullptr, sc->stream, mode == ScrubMode::LocatePairs);
+                                  wd + per_chunk + first, nullptr, sc->stream, pairs);
             return run_verify(gd->encode, K, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first, nullptr,
                               sc->stream);
         };
@@ -208,6 +234,8 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
     }
     if (n_chunks >= 2) HEC_TRY(collect(n_chunks - 2));
     HEC_TRY(collect(n_chunks - 1));
+    for (int i = 0; i < N; ++i)
+        if (written[i] && ::fdatasync(fd[i].fd) != 0) return io("sync " + names[i]);
     if (n_bad) *n_bad = found;
     if (n_blocks) *n_blocks = total_blocks;
     return HEC_OK;
@@ -249,6 +277,21 @@ int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_
     uint64_t block;
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
     return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::LocatePairs, nullptr, bad, cap, n_bad,
+                                     n_blocks);
+}
+
+int hec_correct_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                         size_t* n_bad, uint64_t* n_blocks) {
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks);
+}
+
+int hec_correct_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                               size_t* n_bad, uint64_t* n_blocks) {
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::CorrectPairs, nullptr, bad, cap, n_bad,
                                      n_blocks);
 }
 

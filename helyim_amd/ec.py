@@ -122,6 +122,18 @@ def locate_corrupt_pairs_ec_files(base_filename: str, block_size: int = 0, cap: 
     return _locate_files(lib.hec_locate_corrupt_pairs_ec_files, base_filename, block_size, cap)
 
 
+def correct_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024, pairs: bool = False):
+    """locate_corrupt_ec_files that also fixes what it explains, in the files
+    (hec_correct_ec_files; ``pairs=True``: hec_correct_pairs_ec_files, which
+    also fixes columns two files explain). The same result shape, with the
+    words from before the correction. Of each bad block only the files its
+    suspects word names are rewritten, at the block's offset; a column that
+    sets bit 31 keeps its bytes. A file that cannot be opened for writing
+    raises ``Io`` before any device work."""
+    call = lib.hec_correct_pairs_ec_files if pairs else lib.hec_correct_ec_files
+    return _locate_files(call, base_filename, block_size, cap)
+
+
 def locate_corrupt_ec_files_present(base_filename: str, block_size: int = 0, cap: int = 1024):
     """locate_corrupt_ec_files for a degraded volume
     (hec_locate_corrupt_ec_files_present): missing ``.ecNN`` files are erased

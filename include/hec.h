@@ -363,6 +363,69 @@ int hec_gpu_repair_pairs_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t s
                                uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_present_masks,
                                uint32_t* d_unrepaired, void* stream);
 
+/* Correct in place, per byte column: hec_gpu_locate_corrupt_batch's two passes
+ * with one addition -- where a column is explained, the error value the
+ * syndrome implies is computed too and XORed into the wrong byte. RS(10,4)
+ * only; d_data and d_parity are read and written. With H, syn(o) and the names
+ * exactly as above, per byte column o < shard_len:
+ *   - syn(o) == 0: nothing;
+ *   - one shard c explains it, syn(o) == v * H[:,c]: byte o of shard c becomes
+ *     stored ^ v (parity shard 10 + j: v = syn[j]; data shard c: v = syn[0] /
+ *     P[0][c]);
+ *   - (pairs call only) otherwise shards a < b explain it with v, w != 0: both
+ *     bytes are fixed;
+ *   - otherwise (bit 31): the column is left exactly as it is.
+ * d_mismatch[s] and d_suspects[s] carry exactly hec_gpu_locate_corrupt_batch's
+ * contracts (the pairs call: hec_gpu_locate_corrupt_pairs_batch's), evaluated
+ * on the bytes as they were BEFORE the call; d_bad_stripes is verify's.
+ * *d_uncorrected (device word, optional, accumulated) gets plus one per stripe
+ * whose word has bit 31; *d_corrected_bytes (device 64-bit word, optional,
+ * accumulated) the number of bytes changed. After the call:
+ *   - every column with at most one wrong shard (two with the pairs call)
+ *     holds the bytes that were written;
+ *   - a stripe whose word has bit 31 clear is a codeword again;
+ *   - a stripe with bit 31 set still has its other explainable columns fixed
+ *     (unlike the repair calls, which leave such a stripe alone);
+ *   - the set of bytes that differ from before is exactly the set of wrong
+ *     bytes of explained columns: no other byte of any shard, no byte at or
+ *     past shard_len and no byte between shards is written.
+ * Limits. Single call: a column with 2 or 3 wrong shards is never touched; 4
+ * or more carry no guarantee. Pairs call: 3 wrong shards in a column are
+ * "corrected" to a codeword five shards away in 0.138 % of cases, the pair
+ * locate's price (above); a caller who cannot accept that uses the single
+ * call. When to use which: for a shard that is wrong throughout (a stale
+ * file) the reconstruct of hec_gpu_repair_batch does less math per byte;
+ * correct is for scattered damage, writes only the wrong bytes' vectors, and
+ * repairs stripes that repair must leave alone (five or more shards named
+ * over the columns, or bit 31 somewhere). Measured on one MI355X, 4096 x 1 MiB
+ * stripes, medians of 9 alternating rounds (tools/bench_correct.py,
+ * profiles/correct/bench_correct.json): on the clean batch
+ * hec_gpu_locate_corrupt_batch 9.00 ms (8.99..9.05 over the rounds) and this
+ * call 9.03 ms, inside that spread; 64 stripes with one flipped byte, repair
+ * 9.81 ms and correct 9.24 ms; 64 stripes with a 4 KiB run wrong in two shards,
+ * the pairs call 9.47 ms; 64 stripes with five shards hit at five offsets
+ * (repair leaves all 64) 9.37 ms; 64 stripes whose shard 3 is wrong throughout,
+ * repair 10.11 ms and correct 9.96 ms: on this batch the reconstruct's
+ * smaller math did not show, its two extra passes (masks, decode walk) cost as
+ * much, so the choice between the two is one of contract, not of speed.
+ * Asynchronous on `stream`, no host synchronisation, nothing allocated.
+ * Argument errors are locate's, before any device work; n_stripes == 0
+ * returns HEC_OK and writes nothing. Any strides, bases and lengths (odd ones
+ * take the unaligned kernel). The arrays must not overlap one another or any
+ * shard (not checked). */
+int hec_gpu_correct_batch(const hec_rs_t* rs,
+                          uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                          uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                          uint64_t shard_len, uint32_t n_stripes,
+                          uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                          uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes, void* stream);
+int hec_gpu_correct_pairs_batch(const hec_rs_t* rs,
+                                uint8_t* d_data, uint64_t data_stripe_stride, uint64_t data_shard_stride,
+                                uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                                uint64_t shard_len, uint32_t n_stripes,
+                                uint32_t* d_mismatch, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                                uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes, void* stream);
+
 /* ---- degraded scrub: check and locate with shards missing (RS(10,4)) -------
  * The calls above need all 14 shards. These take hec_gpu_reconstruct_batch's
  * in-place layout and d_present_masks (bit i set = shard i present) and use
@@ -598,10 +661,12 @@ int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scru
  * arguments, block rules, errors and the read-only promise are identical;
  * each entry carries the block's suspects word (hec_gpu_locate_corrupt_batch's
  * contract: bit c = .ec(c) alone explains a byte column of the block, bit 31 =
- * a column no single file explains). How the result is used: when a volume's
- * blocks name one file (up to four) and bit 31 is clear everywhere, delete
- * the named .ecNN and call hec_rebuild_ec_files, which recreates them from the
- * other files; then scrub again. No file is written here. */
+ * a column no single file explains). How the result is used: scattered damage
+ * is fixed in place by hec_correct_ec_files (below). For whole-file damage,
+ * when a volume's blocks name one file (up to four) and bit 31 is clear
+ * everywhere, delete the named .ecNN and call hec_rebuild_ec_files, which
+ * recreates them from the other files; then scrub again. No file is written
+ * here. */
 typedef struct hec_scrub_suspect {
     uint64_t offset;
     uint32_t length;
@@ -615,8 +680,9 @@ int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, 
  * suspects words: arguments, struct, block rules, errors and the read-only
  * promise are identical; a byte column that two files explain sets both
  * their bits instead of bit 31 (the same torn sector in two files, a stale
- * file plus one bit-rot). Recipe: take the union of the named files over all
- * bad blocks; when it holds at most four files and bit 31 is clear everywhere,
+ * file plus one bit-rot). Scattered damage is fixed in place by
+ * hec_correct_pairs_ec_files (below). Recipe for whole-file damage: take the
+ * union of the named files over all bad blocks; when it holds at most four files and bit 31 is clear everywhere,
  * delete the named .ecNN and call hec_rebuild_ec_files, then scrub again. With
  * five or more files named in total or bit 31 set somewhere, rebuild nothing
  * from the volume as a whole. The guarantees and their limit (three wrong
@@ -624,6 +690,24 @@ int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, 
  * hec_gpu_locate_corrupt_pairs_batch. */
 int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
                                       size_t cap, size_t* n_bad, uint64_t* n_blocks);
+/* hec_locate_corrupt_ec_files that also fixes what it explains, in the files:
+ * arguments, block rules and entries are identical, and the entries carry the
+ * words from BEFORE the correction (hec_gpu_correct_batch's contract; the
+ * pairs form: hec_gpu_correct_pairs_batch's, with its limit). The 14 files are
+ * opened for reading and writing: one that cannot be (a read-only file) gives
+ * HEC_ERR_IO with its errno before any device work; the other errors are
+ * hec_verify_ec_files's. For each bad block, and each file .ec(c) whose bit c
+ * is set in the block's suspects word, that file's `length` bytes at the
+ * block's offset are rewritten with the corrected bytes. No other byte of any
+ * file is written, no file is written for a clean block, and a column that
+ * stays unexplained (bit 31) keeps its bytes. Each file that was written is
+ * fdatasync'ed once before the return. A second scrub reports only the blocks
+ * that hold unexplained columns. A degraded volume is out of scope: every
+ * file must be present. */
+int hec_correct_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                         size_t* n_bad, uint64_t* n_blocks);
+int hec_correct_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
+                               size_t* n_bad, uint64_t* n_blocks);
 /* hec_locate_corrupt_ec_files for a degraded volume: a missing .ecNN (ENOENT)
  * is an erased shard, not an error. *present_mask (optional) reports which
  * files were found (bit i = base.ec(i)). Each entry's parity_mask field

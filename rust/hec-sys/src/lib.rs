@@ -165,6 +165,17 @@ extern "C" {
                                       shard_len: u64, n_stripes: u32, d_mismatch: *mut u32, d_suspects: *mut u32,
                                       d_present_masks: *mut u32, d_unrepaired: *mut u32,
                                       stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_correct_batch(rs: *const hec_rs_t, d_data: *mut u8, data_stripe_stride: u64,
+                                 data_shard_stride: u64, d_parity: *mut u8, parity_stripe_stride: u64,
+                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32, d_mismatch: *mut u32,
+                                 d_suspects: *mut u32, d_bad_stripes: *mut u32, d_uncorrected: *mut u32,
+                                 d_corrected_bytes: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_correct_pairs_batch(rs: *const hec_rs_t, d_data: *mut u8, data_stripe_stride: u64,
+                                       data_shard_stride: u64, d_parity: *mut u8, parity_stripe_stride: u64,
+                                       parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                       d_mismatch: *mut u32, d_suspects: *mut u32, d_bad_stripes: *mut u32,
+                                       d_uncorrected: *mut u32, d_corrected_bytes: *mut u64,
+                                       stream: *mut c_void) -> c_int;
     pub fn hec_gpu_verify_present_batch(rs: *const hec_rs_t, d_shards: *const u8, stripe_stride: u64,
                                         shard_stride: u64, shard_len: u64, n_stripes: u32,
                                         d_present_masks: *const u32, d_check: *mut u32, d_bad_stripes: *mut u32,
@@ -217,6 +228,10 @@ extern "C" {
     pub fn hec_locate_corrupt_pairs_ec_files(base_filename: *const c_char, block_size: u64,
                                              bad: *mut hec_scrub_suspect, cap: usize, n_bad: *mut usize,
                                              n_blocks: *mut u64) -> c_int;
+    pub fn hec_correct_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_suspect,
+                                cap: usize, n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
+    pub fn hec_correct_pairs_ec_files(base_filename: *const c_char, block_size: u64, bad: *mut hec_scrub_suspect,
+                                      cap: usize, n_bad: *mut usize, n_blocks: *mut u64) -> c_int;
     pub fn hec_locate_corrupt_ec_files_present(base_filename: *const c_char, block_size: u64,
                                                bad: *mut hec_scrub_suspect, cap: usize, n_bad: *mut usize,
                                                n_blocks: *mut u64, present_mask: *mut u32) -> c_int;

@@ -475,6 +475,38 @@ pub fn verify_ec_files(base_filename: &str, block_size: u64, cap: usize)
     }
 }
 
+/// A bad column block with the shard files its byte columns name: `ScrubBad`
+/// plus `suspects` (bit c = `.ec(c)`, bit 31 = a column left unexplained).
+pub type ScrubSuspect = sys::hec_scrub_suspect;
+
+/// Scrub `base.ec00`..`base.ec13` and fix in place, per byte column, what one
+/// file explains (`hec_correct_ec_files`; `pairs`: also what two files
+/// explain, `hec_correct_pairs_ec_files`). The entries carry the words from
+/// before the correction. Of each bad block only the files its `suspects`
+/// word names are rewritten, at the block's offset. A shard file that cannot
+/// be opened for writing is an I/O error before any device work.
+pub fn correct_ec_files(base_filename: &str, block_size: u64, cap: usize, pairs: bool)
+                        -> Result<(u64, usize, Vec<ScrubSuspect>), EcShardError> {
+    let c = cstr(base_filename)?;
+    let mut bad = vec![ScrubSuspect::default(); cap];
+    let (mut n_bad, mut n_blocks) = (0usize, 0u64);
+    let p = if cap == 0 { std::ptr::null_mut() } else { bad.as_mut_ptr() };
+    let code = unsafe {
+        if pairs {
+            sys::hec_correct_pairs_ec_files(c.as_ptr(), block_size, p, cap, &mut n_bad, &mut n_blocks)
+        } else {
+            sys::hec_correct_ec_files(c.as_ptr(), block_size, p, cap, &mut n_bad, &mut n_blocks)
+        }
+    };
+    match code {
+        0 => {
+            bad.truncate(n_bad.min(cap));
+            Ok((n_blocks, n_bad, bad))
+        }
+        code => Err(file_err(code)),
+    }
+}
+
 /// Pinned host memory for the host-batch calls, freed on drop
 /// (`hec_host_alloc` / `hec_host_alloc_multi` + `hec_host_free`). Pinned
 /// batches are coded zero-copy.
