@@ -27,7 +27,7 @@ from .ec import (  # noqa: F401
     rebuild_ecx_file, save_volume_info, to_ext, ec_shard_filename, ec_shard_base_filename, volume_ec_shards_generate, volume_ec_shards_rebuild,
     write_data_file, write_ec_files, write_index_file_from_ec_index, write_sorted_file_from_index,
     verify_ec_files, locate_corrupt_ec_files, locate_corrupt_ec_files_present, locate_corrupt_pairs_ec_files,
-    correct_ec_files,
+    correct_ec_files, correct_ec_files_present,
 )
 
 SUSPECT_UNEXPLAINED = 0x80000000  # include/hec.h HEC_SUSPECT_UNEXPLAINED
@@ -37,6 +37,7 @@ _BATCH_VERIFY = ("verify_batch", "verify_batch_sep", "host_verify_batch", "verif
                  "locate_corrupt_pairs_batch", "locate_corrupt_pairs_batch_sep", "repair_pairs_batch",
                  "correct_batch", "correct_batch_sep",
                  "verify_present_batch", "locate_corrupt_present_batch", "reconstruct_checked_batch",
+                 "correct_present_batch", "reconstruct_corrected_batch",
                  "check_kernel_name")
 
 

@@ -73,9 +73,14 @@ SIGNATURES = {
     "hec_gpu_verify_present_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P]),
     "hec_gpu_locate_corrupt_present_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P]),
     "hec_gpu_reconstruct_checked_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hec_gpu_correct_present_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hec_gpu_reconstruct_corrected_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _U32, _P, _P, _P, _P, _P, _P,
+                                                 _P]),
     "hec_check_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
     "hec_locate_corrupt_ec_files_present": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S),
                                                  ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
+    "hec_correct_ec_files_present": (_I, [ctypes.c_char_p, _U64, _U32, _P, _S, ctypes.POINTER(_S),
+                                          ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
     "hec_host_encode_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32]),
     "hec_host_reconstruct_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P]),
     "hec_host_encode_batch_multi": (_I, [_P, _P, _S, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32]),

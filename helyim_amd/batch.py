@@ -385,6 +385,62 @@ def reconstruct_checked_batch(rs: ReedSolomon, stripes: torch.Tensor, present_ma
     return check, suspects, use_masks
 
 
+def correct_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor, min_spares: int = 2,
+                          check: torch.Tensor = None, suspects: torch.Tensor = None,
+                          bad_stripes: torch.Tensor = None, unchecked: torch.Tensor = None,
+                          uncorrected: torch.Tensor = None, corrected_bytes: torch.Tensor = None, stream=None):
+    """locate_corrupt_present_batch that also fixes, in place, every byte column
+    one present shard explains (hec_gpu_correct_present_batch). Returns
+    ``(check, suspects)`` of the bytes as they were before the call. Only
+    stripes with min_spares (2, 3 or 4) or more spare shards are written; only
+    wrong bytes of explained columns change, a column that sets bit 31 keeps
+    its bytes, absent shards are never touched. With two spares, two wrong
+    shards in one column may be taken for an intact one, which is then
+    written (include/hec.h has the rates); min_spares=3 rules that out.
+    uncorrected (32-bit CUDA word, accumulated): plus one per stripe left
+    inconsistent (bit 31, or dirty with fewer spares); corrected_bytes (64-bit
+    CUDA word, accumulated): the bytes changed. Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    check = _words_arg(S, check, "check")
+    suspects = _words_arg(S, suspects, "suspects")
+    check_status(lib.hec_gpu_correct_present_batch(
+        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(), int(min_spares),
+        check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        _counter_arg(unchecked, "unchecked"), _counter_arg(uncorrected, "uncorrected"),
+        _bytes_counter_arg(corrected_bytes, "corrected_bytes"), _stream_ptr(stream)))
+    return check, suspects
+
+
+def reconstruct_corrected_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
+                                min_spares: int = 2, check: torch.Tensor = None, suspects: torch.Tensor = None,
+                                use_masks: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                                unrepaired: torch.Tensor = None, corrected_bytes: torch.Tensor = None, stream=None):
+    """Correct the survivors, then rebuild the lost shards from them
+    (hec_gpu_reconstruct_corrected_batch). Returns ``(check, suspects,
+    use_masks)``: correct_present_batch's words; a clean or uncheckable stripe,
+    and a dirty one with min_spares or more spare shards whose columns were all
+    corrected (bit 31 clear), is rebuilt from its present shards (use mask =
+    present mask: no survivor is dropped); any other dirty stripe keeps its
+    holes (use mask 0x3FFF) and is counted into unrepaired. Unlike
+    reconstruct_checked_batch this also restores a stripe whose columns name
+    many different shards; a survivor that is wrong throughout is cheaper as
+    an erasure there. Run verify_batch afterwards for proof."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    check = _words_arg(S, check, "check")
+    suspects = _words_arg(S, suspects, "suspects")
+    use_masks = _words_arg(S, use_masks, "use_masks")
+    check_status(lib.hec_gpu_reconstruct_corrected_batch(
+        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(), int(min_spares),
+        check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        _counter_arg(unrepaired, "unrepaired"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
+        _stream_ptr(stream)))
+    return check, suspects, use_masks
+
+
 def check_kernel_name(L: int) -> str:
     """The kernel an aligned verify_present_batch of this shard length runs (hec_check_kernel_name)."""
     return lib.hec_check_kernel_name(L).decode()

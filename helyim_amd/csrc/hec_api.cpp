@@ -279,6 +279,52 @@ int hec_gpu_reconstruct_checked_batch(const hec_rs_t* rs, uint8_t* d_shards, uin
                      shard_stride, shard_len, n_stripes, d_use_masks, d_bad_stripes, s);
 }
 
+int hec_gpu_correct_present_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                  uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                  const uint32_t* d_present_masks, uint32_t min_spares, uint32_t* d_check,
+                                  uint32_t* d_suspects, uint32_t* d_bad_stripes, uint32_t* d_unchecked,
+                                  uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes, void* stream) {
+    if (rs && d_shards && d_present_masks && d_check && !d_suspects)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    HEC_TRY(check_present_args(rs, d_shards, d_present_masks, d_check, stripe_stride, shard_stride, shard_len,
+                               n_stripes));
+    HEC_TRY(check_min_spares(min_spares));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HEC_TRY(ensure_check_plans(rs, gd, s));
+    return run_correct_present(*gd, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks,
+                               min_spares, d_check, d_suspects, d_bad_stripes, d_unchecked, d_uncorrected,
+                               d_corrected_bytes, s);
+}
+
+int hec_gpu_reconstruct_corrected_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                        uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                        const uint32_t* d_present_masks, uint32_t min_spares, uint32_t* d_check,
+                                        uint32_t* d_suspects, uint32_t* d_use_masks, uint32_t* d_bad_stripes,
+                                        uint32_t* d_unrepaired, unsigned long long* d_corrected_bytes, void* stream) {
+    if (rs && d_shards && d_present_masks && d_check && (!d_suspects || !d_use_masks))
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    HEC_TRY(check_present_args(rs, d_shards, d_present_masks, d_check, stripe_stride, shard_stride, shard_len,
+                               n_stripes));
+    HEC_TRY(check_min_spares(min_spares));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // both plan sets before any launch: their first call uploads and waits
+    HEC_TRY(ensure_check_plans(rs, gd, s));
+    HEC_TRY(ensure_dense_decode(rs, gd, s));
+    HEC_TRY(run_correct_present(*gd, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks,
+                                min_spares, d_check, d_suspects, nullptr, nullptr, nullptr, d_corrected_bytes, s));
+    HEC_HIP(launch_use_masks_corrected(d_present_masks, d_check, d_suspects, d_use_masks, d_unrepaired, min_spares,
+                                       n_stripes, s));
+    // a stripe left alone has every shard "present": the reconstruct's no-op
+    return run_apply(gd->decode_dense, uint32_t(rs->k), d_shards, stripe_stride, shard_stride, d_shards, stripe_stride,
+                     shard_stride, shard_len, n_stripes, d_use_masks, d_bad_stripes, s);
+}
+
 const char* hec_check_kernel_name(uint64_t shard_len) { return check_kernel_name(shard_len); }
 
 int hec_gpu_fill_splitmix(uint8_t* d_base, uint64_t stripe_stride, uint64_t bytes_per_stripe, uint32_t n_stripes,

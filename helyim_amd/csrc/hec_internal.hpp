@@ -233,8 +233,9 @@ struct GeomDevice {
     // scrub's plans. check: a dense LUT over the 2^14 present masks to one
     // plan per mask with 11 or more shards present (inputs B, outputs E,
     // coefficients A_m, 4-row tables); check_ratio: the same plan ids with the
-    // masked locate's ratios A_m[j][c] / A_m[0][c] as 3-row tables.
-    DevicePlanSet check, check_ratio;
+    // masked locate's ratios A_m[j][c] / A_m[0][c] as 3-row tables; check_fix:
+    // the same plan ids with the masked correct's 1 / A_m[0][c] as 1-row tables.
+    DevicePlanSet check, check_ratio, check_fix;
     bool check_ready = false;
 };
 int geom_device(const hec_rs* rs, GeomDevice** out);
@@ -493,6 +494,18 @@ int run_check(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_strid
 int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
                        uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* suspects,
                        uint32_t* bad, uint32_t* unchecked, hipStream_t s);
+// hec_gpu_correct_present_batch: run_locate_present with pass 2 fixing, in
+// place, the columns it explains in stripes with min_spares or more spare
+// shards (rs_kernels.hpp launch_correct_present). uncorrected,
+// corrected_bytes: optional device counters, accumulated.
+int run_correct_present(const GeomDevice& gd, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+                        uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t min_spares, uint32_t* check,
+                        uint32_t* suspects, uint32_t* bad, uint32_t* unchecked, uint32_t* uncorrected,
+                        unsigned long long* corrected_bytes, hipStream_t s);
+inline int check_min_spares(uint32_t min_spares) {
+    if (min_spares < 2 || min_spares > 4) return fail(HEC_ERR_INVALID_ARGUMENT, "min_spares must be 2, 3 or 4");
+    return HEC_OK;
+}
 // Prologue of the masked entry points: nulls, the empty shard, the codec, the
 // layout. All before device work.
 inline int check_present_args(const hec_rs* rs, const void* shards, const void* masks, const void* check,

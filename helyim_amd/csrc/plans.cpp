@@ -276,11 +276,13 @@ int ensure_check_plans(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
     if (gd->check_ready) return HEC_OK;
     const int n = rs->n, k = rs->k;
     if (k != 10 || rs->m != 4) return fail(HEC_ERR_INVALID_ARGUMENT, "check plans are RS(10,4) only");
-    // plan ids count the masks with a spare shard in ascending order, in both
-    // sets: the tables of plan p start at p * 200 (check) and p * 150 (ratio) words
-    HostPlans hp, rp;
+    // plan ids count the masks with a spare shard in ascending order, in all
+    // three sets: the tables of plan p start at p * 200 (check), p * 150
+    // (ratio) and p * 50 (fix) words
+    HostPlans hp, rp, fp;
     hp.fixed_rows = 4;
     rp.fixed_rows = 3;
+    fp.fixed_rows = 1;
     std::vector<uint32_t> lut(size_t(1) << n, kNoPlan);
     uint8_t present[16];
     Mat coefs;
@@ -298,9 +300,21 @@ int ensure_check_plans(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
             for (int j = 1; j < coefs.rows; ++j) ratio.at(j - 1, c) = g.mul[coefs.at(j, c)][g.inv(coefs.at(0, c))];
         }
         rp.add(ratio, in_ids, {1, 2, 3});
+        // the masked correct's constants (rs_kernels.hpp CorrectPresentArgs::
+        // fix_tabs): 1 / A_m[0][c], the value of a wrong shard B[c] from
+        // syn[0]. Checked by multiplying back.
+        Mat inv_a0(1, k);
+        for (int c = 0; c < k; ++c) {
+            inv_a0.at(0, c) = g.inv(coefs.at(0, c));
+            if (g.mul[coefs.at(0, c)][inv_a0.at(0, c)] != 1)
+                return fail(HEC_ERR_INVALID_ARGUMENT, "1 / A_m[0][c] does not multiply back to 1");
+        }
+        if (fp.add(inv_a0, in_ids, {0}) != lut[mask] || fp.plans.back().tab_off != lut[mask] * uint32_t(k * kTabWords))
+            return fail(HEC_ERR_INVALID_ARGUMENT, "check fix plan layout");
     }
     HEC_TRY(gd->check.upload(hp, &lut, s));
     HEC_TRY(gd->check_ratio.upload(rp, nullptr, s));
+    HEC_TRY(gd->check_fix.upload(fp, nullptr, s));
     gd->check.fast104 = true;
     gd->check.lut_bits = uint32_t(n);
     gd->check_ready = true;
@@ -417,6 +431,7 @@ int run_correct(const GeomDevice& gd, uint8_t* data, uint64_t data_stripe, uint6
 static bool fill_check_args(CheckArgs& v, const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride,
                             uint64_t shard_stride, uint64_t len, uint32_t n_stripes, const uint32_t* masks,
                             uint32_t* check, uint32_t* bad, uint32_t* unchecked) {
+    // out_* = in_*: the check kernels only read; the masked correct writes through in_base (fix_shard)
     v.check = check;
     v.unchecked = unchecked;
     v.a.masks = masks;
@@ -451,6 +466,27 @@ int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t str
     v.ratio_tabs = gd.check_ratio.tabs;
     HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
     HEC_HIP(launch_locate_present(v, aligned, s));
+    return HEC_OK;
+}
+
+int run_correct_present(const GeomDevice& gd, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+                        uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t min_spares, uint32_t* check,
+                        uint32_t* suspects, uint32_t* bad, uint32_t* unchecked, uint32_t* uncorrected,
+                        unsigned long long* corrected_bytes, hipStream_t s) {
+    if (n_stripes == 0) return HEC_OK;
+    HEC_TRY(run_check(gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked, s));
+    // pass 2: the masked locate's walk, fixing what it explains
+    CorrectPresentArgs v{};
+    const bool aligned =
+        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, nullptr, nullptr);
+    v.suspects = suspects;
+    v.ratio_tabs = gd.check_ratio.tabs;
+    v.fix_tabs = gd.check_fix.tabs;
+    v.uncorrected = uncorrected;
+    v.corrected_bytes = corrected_bytes;
+    v.min_spares = min_spares;
+    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
+    HEC_HIP(launch_correct_present(v, aligned, s));
     return HEC_OK;
 }
 

@@ -773,6 +773,7 @@ static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
 static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CorrectArgs& c) { return c.a; }
+static ApplyArgs& apply_args(CorrectPresentArgs& c) { return c.a; }
 
 // A fast-mapped batch (set_fast_map), one workgroup per item: k32 where every
 // byte offset inside a shard fits 32 bits, k64 for shards of 4 GiB and more.
@@ -1039,14 +1040,21 @@ struct NoFix {};  // the locate kernel's
 // Only a lane with an error for c touches c; e is zero in columns at or past
 // the shard's end (their syndrome is zero), and the last partial vector goes
 // through load_tail / store_tail, so no byte past the end is written.
-template <bool ALIGNED>
+// IN_PLACE (the masked correct): the batch is one in-place layout and c is a
+// shard index 0..13 of it, so every c is addressed from in_base (out_base
+// equals in_base there: the c - 10 path would put shard 12's fix into shard 2).
+template <bool ALIGNED, bool IN_PLACE = false>
 __device__ __forceinline__ void fix_shard(FixLane& f, int c, const u32x4 e) {
     if ((e[0] | e[1] | e[2] | e[3]) == 0) return;
     const ApplyArgs& a = *f.a;
     const uint64_t o = uint64_t(f.chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;  // < a.len: an error here
-    uint8_t* p = (c < 10 ? const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard
-                         : a.out_base + uint64_t(f.stripe) * a.out_stripe + uint64_t(c - 10) * a.out_shard) +
-                 o;
+    uint8_t* p;
+    if constexpr (IN_PLACE)
+        p = const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard + o;
+    else
+        p = (c < 10 ? const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard
+                    : a.out_base + uint64_t(f.stripe) * a.out_stripe + uint64_t(c - 10) * a.out_shard) +
+            o;
     const uint64_t avail = a.len - o;
     if (avail >= kVecBytes)
         store_full(p, load_full(p, ALIGNED) ^ e, ALIGNED);
@@ -1499,8 +1507,19 @@ hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream) {
 //    j = 1..r-1 (no entry of A_m is zero and no two columns of H_m are
 //    proportional, for every mask: tests/test_check_model.py);
 //  * anything else is unexplained.
-template <bool ALIGNED>
-__global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(CheckArgs v) {
+//
+// CORRECT (rs104_correct_present_kernel, hec.h hec_gpu_correct_present_batch):
+// the same walk over CorrectPresentArgs; in a stripe with r >= min_spares
+// (wave-uniform: one scalar compare) a lane also XORs the error value into the
+// wrong byte of every column it explains (fix_shard, addressed in place):
+// s[j] for shard E[j], s[0] / A_m[0][c] for shard B[c], each masked to the
+// bytes that name that shard. A lane's 16 columns belong to no other lane and
+// its syndrome is complete before its first store, so names and values are
+// those of the bytes as they were. Unexplained columns, and every column of a
+// stripe with fewer spares, are not touched.
+template <bool ALIGNED, bool CORRECT = false>
+__global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
+    std::conditional_t<CORRECT, CorrectPresentArgs, CheckArgs> v) {
     constexpr int K = 10, N = 14, R = 4;
     const ApplyArgs& a = v.a;
     cu32p flagged = as_const(v.check);
@@ -1553,6 +1572,12 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(CheckArg
 #pragma unroll
         for (int j = 0; j < R; ++j) any |= s[j][0] | s[j][1] | s[j][2] | s[j][3];
         if (__ballot(any != 0) == 0) continue;  // wave-uniform: this wave's 1 KiB is clean
+        [[maybe_unused]] std::conditional_t<CORRECT, FixLane, NoFix> fx;
+        [[maybe_unused]] bool write = false;  // wave-uniform: the stripe has the spares the caller asked for
+        if constexpr (CORRECT) {
+            fx = FixLane{&a, stripe, chunk, 0};
+            write = r >= v.min_spares;
+        }
 
         // rows at or past r count as non-zero in "all rows"; with one row
         // nothing is ever named
@@ -1593,8 +1618,16 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(CheckArg
                     const uint32_t mt = allr[w] & ~nz_bytes(diff);
                     matched[w] |= mt;
                     hit |= mt;
+                    if constexpr (CORRECT) e[0][w] = (mt >> 7) * 0xFFu;  // the ratios are spent: the bytes B[c] explains
                 }
                 bits |= (__ballot(hit != 0) != 0 ? 1u : 0u) << __builtin_ctz(bm);
+                if constexpr (CORRECT) {
+                    if (write && __ballot(hit != 0) != 0) {  // wave-uniform: somebody fixes shard B[c]
+                        u32x4 val[1] = {u32x4{0, 0, 0, 0}};
+                        gf_mac<1>(val, s[0], as_const(v.fix_tabs) + pid * (K * 5) + c * 5);  // s[0] / A_m[0][c]
+                        fix_shard<ALIGNED, true>(fx, __builtin_ctz(bm), val[0] & e[0]);
+                    }
+                }
                 bm &= bm - 1;
             }
 #pragma unroll
@@ -1603,13 +1636,59 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(CheckArg
 #pragma unroll
         for (int j = 0; j < R; ++j) bits |= (__ballot(one[j] != 0) != 0 ? 1u : 0u) << out_id[j];
         if (__ballot(unexplained != 0) != 0) bits |= kSuspectUnexplained;
-        if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+        if constexpr (!CORRECT) {
+            if (bits != 0 && (threadIdx.x & 63u) == 0) atomicOr(v.suspects + stripe, bits);
+        } else {
+            if (write) {
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    if (__ballot(one[j] != 0) == 0) continue;  // wave-uniform: nobody fixes shard E[j]
+                    u32x4 e;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        uint32_t others = 0;
+#pragma unroll
+                        for (int i = 0; i < R; ++i)
+                            if (i != j) others |= nz_bytes(s[i][w]);
+                        e[w] = s[j][w] & ((nz_bytes(s[j][w]) & ~others) >> 7) * 0xFFu;
+                    }
+                    fix_shard<ALIGNED, true>(fx, int(out_id[j]), e);
+                }
+            }
+            // the bytes this wave changed, at most 16 a lane: five ballots
+            uint32_t total = 0;
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                total += uint32_t(__builtin_popcountll(__ballot(((fx.changed >> k) & 1u) != 0))) << k;
+            if ((threadIdx.x & 63u) == 0) {
+                // a stripe the call leaves inconsistent is counted once: with the
+                // spares, by the atomicOr that first sets bit 31; without them, by
+                // the one that finds the word zero (bits != 0 in every wave here)
+                if (bits != 0) {
+                    const uint32_t old = atomicOr(v.suspects + stripe, bits);
+                    const bool first = write ? (old & kSuspectUnexplained) == 0 && (bits & kSuspectUnexplained) != 0
+                                             : old == 0;
+                    if (first && v.uncorrected) atomicAdd(v.uncorrected, 1u);
+                }
+                if (total != 0 && v.corrected_bytes) atomicAdd(v.corrected_bytes, (unsigned long long)total);
+            }
+        }
     }
 }
+
+// rs104_correct_present_kernel<ALIGNED>: the masked locate's CORRECT form, taking CorrectPresentArgs.
+template <bool ALIGNED>
+constexpr auto rs104_correct_present_kernel = rs104_locate_present_kernel<ALIGNED, true>;
 
 hipError_t launch_locate_present(const CheckArgs& v, bool aligned, hipStream_t stream) {
     if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
     return launch_stride(aligned ? rs104_locate_present_kernel<true> : rs104_locate_present_kernel<false>, v, stream,
+                         kLocateMaxBlocks);
+}
+
+hipError_t launch_correct_present(const CorrectPresentArgs& v, bool aligned, hipStream_t stream) {
+    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
+    return launch_stride(aligned ? rs104_correct_present_kernel<true> : rs104_correct_present_kernel<false>, v, stream,
                          kLocateMaxBlocks);
 }
 
@@ -1647,6 +1726,43 @@ hipError_t launch_use_masks(const uint32_t* present, const uint32_t* check, cons
     const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
     hipLaunchKernelGGL(use_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects, use,
                        unrepaired, n_stripes);
+    return hipGetLastError();
+}
+
+// The use masks after rs104_correct_present_kernel (min_spares: the call's):
+// nothing is dropped; a stripe is rebuilt from its own survivors when they are
+// consistent (clean, unchecked, or corrected with bit 31 clear) and left
+// alone, holes included, otherwise. Same rounds and count as use_masks_kernel.
+__global__ __launch_bounds__(kThreads) void use_masks_corrected_kernel(const uint32_t* present, const uint32_t* check,
+                                                                       const uint32_t* suspects, uint32_t* use,
+                                                                       uint32_t* unrepaired, uint32_t min_spares,
+                                                                       uint32_t n_stripes) {
+    constexpr uint32_t kAll = (1u << 14) - 1;
+    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
+    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
+        bool left = false;
+        if (s < n_stripes) {
+            const uint32_t m = present[s] & kAll;
+            const bool consistent =
+                check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
+                                  (suspects[s] & kSuspectUnexplained) == 0);
+            use[s] = consistent ? m : kAll;
+            left = !consistent;
+        }
+        const unsigned long long b = __ballot(left);
+        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
+    }
+}
+
+hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* check, const uint32_t* suspects,
+                                      uint32_t* use, uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
+                                      hipStream_t stream) {
+    if (n_stripes == 0) return hipSuccess;
+    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
+    hipLaunchKernelGGL(use_masks_corrected_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects,
+                       use, unrepaired, min_spares, n_stripes);
     return hipGetLastError();
 }
 

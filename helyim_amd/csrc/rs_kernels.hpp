@@ -217,12 +217,34 @@ hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream);
 // with the stripe's own A_m, ratio tables and row count; stripes whose check
 // word is 0 are not read. Same grid rule as launch_locate.
 hipError_t launch_locate_present(const CheckArgs& v, bool aligned, hipStream_t stream);
+// Masked correct (hec.h hec_gpu_correct_present_batch): launch_locate_present's
+// pass with one addition -- where a column of a stripe with r >= min_spares is
+// explained, the error value is computed too and XORed into the wrong byte of
+// v.a.in_base, in place (the batch is one in-place layout: every shard id is
+// addressed from in_base). Columns that set bit 31 and stripes with fewer
+// spares are left as they are. The words are the locate's, of the bytes as
+// they were.
+struct CorrectPresentArgs : CheckArgs {  // as for launch_locate_present, and:
+    const uint32_t* fix_tabs = nullptr;  // per plan [10][kTabWords]: 1 / A_m[0][c]
+    uint32_t* uncorrected = nullptr;     // optional: += stripes left inconsistent (bit 31, or dirty with r < min_spares)
+    unsigned long long* corrected_bytes = nullptr;  // optional: += bytes changed
+    uint32_t min_spares = 2;             // 2..4: stripes with fewer spare shards are classified, not written
+};
+hipError_t launch_correct_present(const CorrectPresentArgs& v, bool aligned, hipStream_t stream);
 // Use masks of a checked reconstruct (hec_gpu_reconstruct_checked_batch):
 // use[s] = m = present[s] & 0x3FFF when check[s] == 0; m & ~suspects[s] when
 // bit 31 is clear, a shard is named and at least 10 bits remain; else 0x3FFF
 // (the reconstruct's no-op) and *unrepaired (optional) += 1.
 hipError_t launch_use_masks(const uint32_t* present, const uint32_t* check, const uint32_t* suspects, uint32_t* use,
                             uint32_t* unrepaired, uint32_t n_stripes, hipStream_t stream);
+// Use masks of a corrected reconstruct (hec_gpu_reconstruct_corrected_batch),
+// after launch_correct_present with the same min_spares: use[s] = m when
+// check[s] == 0, or when the stripe has min_spares or more spare shards and
+// bit 31 of suspects[s] is clear (its survivors are consistent again: nothing
+// is dropped); else 0x3FFF and *unrepaired (optional) += 1.
+hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* check, const uint32_t* suspects,
+                                      uint32_t* use, uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
+                                      hipStream_t stream);
 // Name of the kernel an aligned masked verify of this shard length runs.
 const char* check_kernel_name(uint64_t len);
 

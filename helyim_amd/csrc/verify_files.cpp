@@ -4,7 +4,8 @@
 // hec_locate_corrupt_pairs_ec_files: that walk naming two files per column; and
 // hec_locate_corrupt_ec_files_present: that walk over a degraded volume, its
 // missing files treated as erased shards; hec_correct_ec_files and its pairs
-// form: the locate walk with the correct pass, whose fixes are written back).
+// form: the locate walk with the correct pass, whose fixes are written back;
+// hec_correct_ec_files_present: the degraded walk with the masked correct pass).
 //
 // RS parity is bytewise: byte o of every parity file is a function of byte o
 // of the ten data files, whatever large / small block geometry laid the .dat
@@ -90,11 +91,15 @@ enum class ScrubMode { Verify, Locate, LocatePairs, Correct, CorrectPairs };
 // row of a slot is neither read into nor read by the kernels, every launch is
 // run_locate_present with the volume's present mask, and the words are the
 // masked calls' (shard-index bits). *present_out (optional) = the files found.
+// degraded with mode Correct (hec_correct_ec_files_present): the present files
+// are opened for writing and every launch is run_correct_present with
+// min_spares, a named row is written back as above (the kernel names present
+// shards only); a volume with fewer spare files is only located.
 int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode, hec_scrub_bad* bad,
                          hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks,
-                         bool degraded = false, uint32_t* present_out = nullptr) {
+                         bool degraded = false, uint32_t* present_out = nullptr, uint32_t min_spares = 2) {
     const bool locate = mode != ScrubMode::Verify;
-    const bool correct = mode == ScrubMode::Correct || mode == ScrubMode::CorrectPairs;
+    bool correct = mode == ScrubMode::Correct || mode == ScrubMode::CorrectPairs;
     const bool pairs = mode == ScrubMode::LocatePairs || mode == ScrubMode::CorrectPairs;
     // files and sizes first: these failures need no device
     Fd fd[N];
@@ -118,6 +123,7 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
         return fail(HEC_ERR_TOO_FEW_SHARDS_PRESENT, std::to_string(n_present) + " of " + std::to_string(N) +
                                                         " shard files present, the check needs at least " +
                                                         std::to_string(K + 1));
+    if (degraded && correct && uint32_t(n_present - K) < min_spares) correct = false;  // too few spares: the locate
     const int first_present = __builtin_ctz(present);
     for (int i = 0; i < N; ++i) {
         if (fd[i].fd < 0) continue;
@@ -210,6 +216,10 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
         auto launch = [&](uint64_t first, uint64_t blen, uint64_t n) -> int {
             const uint8_t* d = zs[q] + first * block;
             const uint8_t* p = d + uint64_t(K) * pitch;
+            if (degraded && correct)
+                return run_correct_present(*gd, zs[q] + first * block, block, pitch, blen, uint32_t(n), sc->masks_dev,
+                                           min_spares, wd + first, wd + per_chunk + first, nullptr, nullptr, nullptr,
+                                           nullptr, sc->stream);
             if (degraded)
                 return run_locate_present(*gd, d, block, pitch, blen, uint32_t(n), sc->masks_dev, wd + first,
                                           wd + per_chunk + first, nullptr, nullptr, sc->stream);
@@ -302,6 +312,17 @@ int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t bloc
     HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
     return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks,
                                      true, present_mask);
+}
+
+int hec_correct_ec_files_present(const char* base_filename, uint64_t block_size, uint32_t min_spares,
+                                 hec_scrub_suspect* bad, size_t cap, size_t* n_bad, uint64_t* n_blocks,
+                                 uint32_t* present_mask) {
+    if (present_mask) *present_mask = 0;
+    uint64_t block;
+    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
+    HEC_TRY(hec::check_min_spares(min_spares));
+    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks,
+                                     true, present_mask, min_spares);
 }
 
 }  // extern "C"

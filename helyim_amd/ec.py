@@ -134,6 +134,20 @@ def correct_ec_files(base_filename: str, block_size: int = 0, cap: int = 1024, p
     return _locate_files(call, base_filename, block_size, cap)
 
 
+def _scrub_present(call, head, cap):
+    """One of the degraded file scrubs: call(*head, bad, cap, &n_bad, &n_blocks,
+    &present_mask) -> (n_blocks, n_bad, bad, present_mask)."""
+    if cap < 0:
+        raise ValueError("negative cap")
+    bad = (_ScrubSuspect * cap)() if cap else None
+    n_bad, n_blocks, present = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    check_ec(call(*head, bad, cap, ctypes.byref(n_bad), ctypes.byref(n_blocks), ctypes.byref(present)))
+    got = min(cap, n_bad.value)
+    return (int(n_blocks.value), int(n_bad.value),
+            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
+             for i in range(got)], int(present.value))
+
+
 def locate_corrupt_ec_files_present(base_filename: str, block_size: int = 0, cap: int = 1024):
     """locate_corrupt_ec_files for a degraded volume
     (hec_locate_corrupt_ec_files_present): missing ``.ecNN`` files are erased
@@ -143,18 +157,24 @@ def locate_corrupt_ec_files_present(base_filename: str, block_size: int = 0, cap
     (``ErasureCoding(TooFewShardsPresent)`` below that, ``ShardNotFound`` with none). Reads
     only. To repair: when blocks name files and bit 31 is clear everywhere,
     delete the named files too (at most four missing in all), call
-    ``rebuild_ec_files``, scrub again."""
-    if cap < 0:
-        raise ValueError("negative cap")
-    bad = (_ScrubSuspect * cap)() if cap else None
-    n_bad, n_blocks, present = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
-    check_ec(lib.hec_locate_corrupt_ec_files_present(base_filename.encode(), block_size, bad, cap,
-                                                     ctypes.byref(n_bad), ctypes.byref(n_blocks),
-                                                     ctypes.byref(present)))
-    got = min(cap, n_bad.value)
-    return (int(n_blocks.value), int(n_bad.value),
-            [(int(bad[i].offset), int(bad[i].length), int(bad[i].parity_mask), int(bad[i].suspects))
-             for i in range(got)], int(present.value))
+    ``rebuild_ec_files``, scrub again; ``correct_ec_files_present`` heals
+    scattered damage in the survivors in place instead."""
+    return _scrub_present(lib.hec_locate_corrupt_ec_files_present, (base_filename.encode(), block_size), cap)
+
+
+def correct_ec_files_present(base_filename: str, block_size: int = 0, min_spares: int = 2, cap: int = 1024):
+    """locate_corrupt_ec_files_present that also fixes what it explains, in the
+    present files (hec_correct_ec_files_present). The same result shape, with
+    the words from before the correction. Of each bad block only the present
+    files its suspects word names are rewritten, at the block's offset; a
+    column that sets bit 31 keeps its bytes; a missing file is not created.
+    min_spares (2, 3 or 4): a volume with fewer spare files is only located
+    (with two spares, two wrong files in one byte column may be taken for an
+    intact one, which is then written: include/hec.h has the rates; 3 rules
+    that out). A present file that cannot be opened for writing raises ``Io``
+    before any device work. The recipe for a degraded volume: this call, then
+    ``rebuild_ec_files`` when bit 31 is clear everywhere, then scrub again."""
+    return _scrub_present(lib.hec_correct_ec_files_present, (base_filename.encode(), block_size, min_spares), cap)
 
 
 # --- EC volume files around the shards (helyim-ec host-side byte formats) ---

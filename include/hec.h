@@ -538,6 +538,97 @@ int hec_gpu_reconstruct_checked_batch(const hec_rs_t* rs, uint8_t* d_shards, uin
                                       uint32_t* d_use_masks, uint32_t* d_bad_stripes, uint32_t* d_unrepaired,
                                       void* stream);
 
+/* Masked correct: the masked locate that also fixes, in place, every byte
+ * column one present shard explains -- hec_gpu_correct_batch for a degraded
+ * stripe. d_check, d_suspects, d_bad_stripes and d_unchecked carry exactly
+ * hec_gpu_locate_corrupt_present_batch's contracts, evaluated on the bytes as
+ * they were BEFORE the call. min_spares must be 2, 3 or 4
+ * (HEC_ERR_INVALID_ARGUMENT otherwise, before device work): a stripe with
+ * r < min_spares is classified but never written. Per byte column o <
+ * shard_len of a stripe with r >= min_spares:
+ *   - syn(o) == 0: nothing;
+ *   - one present shard c explains it, syn(o) == v * H_m[:,c]: byte o of shard
+ *     c becomes stored ^ v (shard E[j]: v = syn[j]; shard B[c]: v = syn[0] /
+ *     A_m[0][c]);
+ *   - otherwise (bit 31): the column is left exactly as it is.
+ * *d_uncorrected (device word, optional, accumulated) gets plus one per stripe,
+ * exactly once, that the call leaves inconsistent as far as it can tell: bit 31
+ * in its suspects word, or a non-zero check word with r < min_spares.
+ * *d_corrected_bytes (device 64-bit word, optional, accumulated): the bytes
+ * changed. After the call:
+ *   - a stripe with r >= min_spares and bit 31 clear has consistent present
+ *     shards: a masked verify gives 0, and a reconstruct from it is the
+ *     original whenever the guarantees below held;
+ *   - a stripe with bit 31 set still has its other explainable columns fixed;
+ *   - the set of bytes that differ from before is exactly the set of wrong
+ *     bytes of explained columns; absent shards are never read or written, and
+ *     no byte at or past shard_len and no byte between shards is written.
+ * Guarantees, per byte column:
+ *   r   one wrong survivor   two wrong in one column      three wrong in one column
+ *   4   corrected (as        bit 31, untouched            bit 31, untouched
+ *       hec_gpu_correct_batch)
+ *   3   corrected            bit 31, untouched            may be taken for one intact
+ *                                                         shard, which is "corrected"
+ *   2   corrected            NO GUARANTEE: may be taken   --
+ *                            for an intact shard, which
+ *                            is then written
+ *   1   bit 31, nothing written
+ * Why min_spares exists: with r = 2 the present shards have distance 3, and two
+ * wrong survivors in one column look like one wrong intact shard in 10 * 255 /
+ * 65535 = 3.9 % of cases (the CPU model of tests/correct_present_model.py:
+ * 786 of 20,000 random cases with shards 0 and 12 lost named an intact shard,
+ * none named one of the wrong two); with r = 3, three wrong survivors do so in
+ * about 0.015 %. A caller who cannot accept r = 2's limit passes 3: then no
+ * intact byte is ever changed while at most two shards of a column are wrong.
+ * The counters are accumulated and optional. Asynchronous on `stream`, no host
+ * synchronisation (only the first plan upload on a device waits), nothing
+ * allocated. Argument errors are the masked locate's plus min_spares, all
+ * before device work; n_stripes == 0 returns HEC_OK and writes nothing. Any
+ * strides, bases and lengths (odd ones take the unaligned kernel). */
+int hec_gpu_correct_present_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                  uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                  const uint32_t* d_present_masks, uint32_t min_spares,
+                                  uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                                  uint32_t* d_unchecked, uint32_t* d_uncorrected,
+                                  unsigned long long* d_corrected_bytes, void* stream);
+
+/* Corrected reconstruct: correct the survivors, then rebuild the lost shards
+ * from them. In stream order:
+ *  (1) hec_gpu_correct_present_batch into d_check / d_suspects (the count of
+ *      uncorrected stripes is not reported; *d_corrected_bytes is its);
+ *  (2) d_use_masks[s] = m when d_check[s] == 0 (clean stripes, and unchecked
+ *      stripes with p <= 10, decoded on faith exactly as
+ *      hec_gpu_reconstruct_batch does); = m also when r >= min_spares and bit
+ *      31 of d_suspects[s] is clear (every dirty column was corrected);
+ *      otherwise 0x3FFF: the stripe's holes stay, and *d_unrepaired (device
+ *      word, optional, accumulated) gets plus one;
+ *  (3) hec_gpu_reconstruct_batch with d_use_masks; *d_bad_stripes is its count.
+ * Unlike hec_gpu_reconstruct_checked_batch no survivor is dropped, so a stripe
+ * whose columns name many different shards (one lost and five survivors each
+ * wrong at another offset: 13 - 5 = 8 trusted shards, which the checked call
+ * must leave alone) is rebuilt in full. When to prefer which: a survivor that
+ * is wrong throughout (a stale file) is cheaper as an erasure, the checked
+ * call's way; scattered damage needs this call. Measured on one MI355X, 4096 x
+ * 1 MiB stripes with one shard of each erased, medians of 9 alternating rounds
+ * (tools/bench_correct_present.py,
+ * profiles/correct_present/bench_correct_present.json): on the clean batch
+ * hec_gpu_locate_corrupt_present_batch 8.65 ms (8.58..8.78 over the rounds) and
+ * hec_gpu_correct_present_batch 8.71 ms, inside that spread; 64 stripes with
+ * one flipped byte, the checked reconstruct 16.59 ms and this call 16.64 ms;
+ * 64 stripes with five survivors hit at five offsets (the checked reconstruct
+ * leaves all 64) 16.96 ms; 64 stripes with one survivor wrong throughout, the
+ * checked reconstruct 17.02 ms and this call 17.26 ms. The guarantees are the masked
+ * correct's, r = 2's limit and min_spares included; hec_gpu_verify_batch
+ * afterwards is the proof. d_check, d_suspects and d_use_masks hold n_stripes
+ * words each, are overwritten, and must be distinct arrays that overlap nothing
+ * else. Argument errors as the masked correct plus a null d_use_masks. */
+int hec_gpu_reconstruct_corrected_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                        uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                        const uint32_t* d_present_masks, uint32_t min_spares,
+                                        uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_use_masks,
+                                        uint32_t* d_bad_stripes, uint32_t* d_unrepaired,
+                                        unsigned long long* d_corrected_bytes, void* stream);
+
 /* ---- host-memory batches (the path helyim runs: bytes start and end in host
  * memory, encoder.rs:169-195 / 263-304) -------------------------------------
  * Same strided layout as above but on HOST pointers; synchronous on return.
@@ -702,8 +793,8 @@ int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_
  * file is written, no file is written for a clean block, and a column that
  * stays unexplained (bit 31) keeps its bytes. Each file that was written is
  * fdatasync'ed once before the return. A second scrub reports only the blocks
- * that hold unexplained columns. A degraded volume is out of scope: every
- * file must be present. */
+ * that hold unexplained columns. Every file must be present; a degraded
+ * volume goes to hec_correct_ec_files_present. */
 int hec_correct_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                          size_t* n_bad, uint64_t* n_blocks);
 int hec_correct_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
@@ -721,13 +812,32 @@ int hec_correct_pairs_ec_files(const char* base_filename, uint64_t block_size, h
  * not all equal -> HEC_ERR_UNEXPECTED_EC_SHARD_SIZE with hec_last_error_values
  * = (size of the first present file, size of the first that differs). Block,
  * cap and bad rules are unchanged.
- * Recipe for a degraded volume: scrub it with this call; if blocks name files
- * and bit 31 is clear everywhere, delete the named files too (at most four
- * missing in total); then hec_rebuild_ec_files; then scrub again. With bit 31
- * set somewhere (always so with three files missing) the volume has damage
- * this library cannot attribute: rebuild nothing from it. */
+ * Recipe for a degraded volume: scrub it with hec_correct_ec_files_present
+ * (below), which heals the surviving files in place; if bit 31 is clear in
+ * every entry, hec_rebuild_ec_files; then scrub again. (Read-only
+ * alternative, for files that are wrong throughout: scrub with this call,
+ * delete the named files too -- at most four missing in total -- and rebuild.)
+ * With bit 31 set somewhere (always so with three files missing) the volume
+ * has damage this library cannot attribute: rebuild nothing from it. */
 int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
                                         size_t cap, size_t* n_bad, uint64_t* n_blocks, uint32_t* present_mask);
+/* hec_locate_corrupt_ec_files_present that also fixes what it explains, in the
+ * present files (every launch is hec_gpu_correct_present_batch's kernel with
+ * min_spares: 2, 3 or 4, HEC_ERR_INVALID_ARGUMENT otherwise). The entries
+ * equal hec_locate_corrupt_ec_files_present's and hold the words from BEFORE
+ * the correction. The present files are opened for reading and writing: one
+ * that cannot be (a read-only file) gives HEC_ERR_IO with its errno before
+ * any device work; ENOENT is an erased shard; the other errors are
+ * hec_locate_corrupt_ec_files_present's. For each bad block, and each present
+ * file .ec(c) whose bit c is set in the block's suspects word, that file's
+ * `length` bytes at the block's offset are rewritten from the corrected
+ * block; nothing else is written, no missing file is created, and each file
+ * written is fdatasync'ed once before the return. A volume with fewer than
+ * min_spares spare files (r < min_spares) is only located: nothing is
+ * written. */
+int hec_correct_ec_files_present(const char* base_filename, uint64_t block_size, uint32_t min_spares,
+                                 hec_scrub_suspect* bad, size_t cap, size_t* n_bad, uint64_t* n_blocks,
+                                 uint32_t* present_mask);
 
 /* ---- EC volume files around the shards (host-side byte formats) ----------- */
 /* write_sorted_file_from_index(base, ext) (encoder.rs:21-37): replay base.idx

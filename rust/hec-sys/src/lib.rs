@@ -190,6 +190,18 @@ extern "C" {
                                              d_present_masks: *const u32, d_check: *mut u32, d_suspects: *mut u32,
                                              d_use_masks: *mut u32, d_bad_stripes: *mut u32,
                                              d_unrepaired: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_correct_present_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64,
+                                         shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                         d_present_masks: *const u32, min_spares: u32, d_check: *mut u32,
+                                         d_suspects: *mut u32, d_bad_stripes: *mut u32, d_unchecked: *mut u32,
+                                         d_uncorrected: *mut u32, d_corrected_bytes: *mut u64,
+                                         stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_reconstruct_corrected_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64,
+                                               shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                               d_present_masks: *const u32, min_spares: u32, d_check: *mut u32,
+                                               d_suspects: *mut u32, d_use_masks: *mut u32,
+                                               d_bad_stripes: *mut u32, d_unrepaired: *mut u32,
+                                               d_corrected_bytes: *mut u64, stream: *mut c_void) -> c_int;
     pub fn hec_host_verify_batch(rs: *const hec_rs_t, h_data: *const u8, data_stripe_stride: u64,
                                  data_shard_stride: u64, h_parity: *const u8, parity_stripe_stride: u64,
                                  parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
@@ -235,6 +247,9 @@ extern "C" {
     pub fn hec_locate_corrupt_ec_files_present(base_filename: *const c_char, block_size: u64,
                                                bad: *mut hec_scrub_suspect, cap: usize, n_bad: *mut usize,
                                                n_blocks: *mut u64, present_mask: *mut u32) -> c_int;
+    pub fn hec_correct_ec_files_present(base_filename: *const c_char, block_size: u64, min_spares: u32,
+                                        bad: *mut hec_scrub_suspect, cap: usize, n_bad: *mut usize,
+                                        n_blocks: *mut u64, present_mask: *mut u32) -> c_int;
     pub fn hec_write_sorted_file_from_index(base_filename: *const c_char, ext: *const c_char) -> c_int;
     pub fn hec_rebuild_ecx_file(base_filename: *const c_char) -> c_int;
     pub fn hec_save_volume_info(filename: *const c_char, version: u32) -> c_int;

@@ -507,6 +507,31 @@ pub fn correct_ec_files(base_filename: &str, block_size: u64, cap: usize, pairs:
     }
 }
 
+/// `correct_ec_files` for a degraded volume (`hec_correct_ec_files_present`):
+/// missing `.ecNN` files are erased shards, and what one present file explains
+/// is fixed in place in volumes with `min_spares` (2, 3 or 4) or more spare
+/// files. Returns the blocks checked, the bad blocks, the first `min(cap,
+/// bad)` entries (the masked locate's words, from before the correction) and
+/// the mask of the files found. Then `rebuild_ec_files`, then scrub again.
+pub fn correct_ec_files_present(base_filename: &str, block_size: u64, min_spares: u32, cap: usize)
+                                -> Result<(u64, usize, Vec<ScrubSuspect>, u32), EcShardError> {
+    let c = cstr(base_filename)?;
+    let mut bad = vec![ScrubSuspect::default(); cap];
+    let (mut n_bad, mut n_blocks, mut present) = (0usize, 0u64, 0u32);
+    let p = if cap == 0 { std::ptr::null_mut() } else { bad.as_mut_ptr() };
+    let code = unsafe {
+        sys::hec_correct_ec_files_present(c.as_ptr(), block_size, min_spares, p, cap, &mut n_bad, &mut n_blocks,
+                                          &mut present)
+    };
+    match code {
+        0 => {
+            bad.truncate(n_bad.min(cap));
+            Ok((n_blocks, n_bad, bad, present))
+        }
+        code => Err(file_err(code)),
+    }
+}
+
 /// Pinned host memory for the host-batch calls, freed on drop
 /// (`hec_host_alloc` / `hec_host_alloc_multi` + `hec_host_free`). Pinned
 /// batches are coded zero-copy.
