@@ -87,6 +87,8 @@ SIGNATURES = {
     "hec_host_reconstruct_batch_multi": (_I, [_P, _P, _S, _P, _U64, _U64, _U64, _U32, _P, _P]),
     "hec_gpu_encode_ragged": (_I, [_P, _P, _P, _U32, _P]),
     "hec_gpu_reconstruct_ragged": (_I, [_P, _P, _P, _U32, _P, _P]),
+    "hec_gpu_verify_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P]),
+    "hec_gpu_locate_corrupt_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "hec_gpu_fill_splitmix": (_I, [_P, _U64, _U64, _U32, _U64, _P]),
     "hec_write_ec_files": (_I, [ctypes.c_char_p]),
     "hec_write_ec_files_ex": (_I, [ctypes.c_char_p, _U64, _U64, _U64]),
@@ -133,6 +135,7 @@ SIGNATURES = {
     "hec_encode_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
     "hec_decode_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
     "hec_ragged_kernel_name": (ctypes.c_char_p, [_P, _U32, _I]),
+    "hec_ragged_scrub_kernel_name": (ctypes.c_char_p, [_P, _U32]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

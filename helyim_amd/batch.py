@@ -581,6 +581,46 @@ def reconstruct_ragged(rs: ReedSolomon, base: torch.Tensor, descs, bad_stripes: 
                                          _stream_ptr(stream)))
 
 
+def verify_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: torch.Tensor = None,
+                  bad_stripes: torch.Tensor = None, unchecked: torch.Tensor = None, stream=None) -> torch.Tensor:
+    """Scrub stripes of mixed lengths and present masks in one pass
+    (hec_gpu_verify_ragged, RS(10,4) only); descs as reconstruct_ragged's.
+    Returns the int32 ``[S]`` check words (``check``, allocated when not
+    given), verify_present_batch's contract stripe by stripe: bit e (shard
+    index) set when spare present shard e differs from what the stripe's ten
+    lowest present shards imply over its own shard length. Stripes with ten
+    or fewer shards present give 0, are not read and are counted into
+    unchecked; bad_stripes counts the non-zero words (32-bit CUDA words,
+    accumulated). Nothing but the words is written. Asynchronous on the
+    stream."""
+    d = _desc_array(descs, base, rs.total_shard_count())
+    check = _words_arg(len(d), check, "check")
+    check_status(lib.hec_gpu_verify_ragged(
+        rs.handle, base.data_ptr(), d.ctypes.data, len(d), check.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
+    return check
+
+
+def locate_corrupt_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: torch.Tensor = None,
+                          suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                          unchecked: torch.Tensor = None, stream=None):
+    """verify_ragged that also names the corrupt shard
+    (hec_gpu_locate_corrupt_ragged). Returns ``(check, suspects)``,
+    locate_corrupt_present_batch's words stripe by stripe: bit c of
+    suspects[s] = present shard c alone explains a byte column of stripe s,
+    ``helyim_amd.SUSPECT_UNEXPLAINED`` = a column no single shard explains (every
+    dirty column of a stripe with one spare shard). To repair, clear the named
+    bits in the stripe's present mask and call reconstruct_ragged; verify_ragged
+    with the original masks is the proof."""
+    d = _desc_array(descs, base, rs.total_shard_count())
+    check = _words_arg(len(d), check, "check")
+    suspects = _words_arg(len(d), suspects, "suspects")
+    check_status(lib.hec_gpu_locate_corrupt_ragged(
+        rs.handle, base.data_ptr(), d.ctypes.data, len(d), check.data_ptr(), suspects.data_ptr(),
+        _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
+    return check, suspects
+
+
 def host_zero_copy(t: torch.Tensor) -> bool:
     """True when host batches on t's bytes are coded zero-copy on the current
     device (hec_host_zero_copy_view): t is one pinned, GPU-addressable range."""
@@ -600,6 +640,16 @@ def ragged_kernel_name(descs, decode: bool) -> str:
         np.array([tuple(int(x) for x in r) for r in descs], dtype=desc_dtype())
     d = np.ascontiguousarray(d)
     return lib.hec_ragged_kernel_name(d.ctypes.data if len(d) else None, len(d), int(bool(decode))).decode()
+
+
+def ragged_scrub_kernel_name(descs) -> str:
+    """The pass-1 kernel verify_ragged / locate_corrupt_ragged runs on these
+    descriptors (hec_ragged_scrub_kernel_name: the launch's own choice)."""
+    import numpy as np
+    d = descs if isinstance(descs, np.ndarray) and descs.dtype == desc_dtype() else \
+        np.array([tuple(int(x) for x in r) for r in descs], dtype=desc_dtype())
+    d = np.ascontiguousarray(d)
+    return lib.hec_ragged_scrub_kernel_name(d.ctypes.data if len(d) else None, len(d)).decode()
 
 
 def fill_splitmix(t: torch.Tensor, bytes_per_stripe: int, seed_base: int, stream=None) -> None:

@@ -248,10 +248,17 @@ int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const s
 namespace hec {
 namespace {
 
+// What a device-resident ragged call does with its stripes.
+enum class RaggedOp { Encode, Decode, Scrub };
+
 // Workgroups of one ragged stripe: none for a decode of a stripe whose 14
-// shards are all present (upstream's no-op), so those launch nothing.
-uint64_t ragged_chunks(const hec_stripe_desc& d, bool decode, uint32_t chunk_bytes) {
-    if (decode && (d.present_mask & 0x3FFFu) == 0x3FFFu) return 0;
+// shards are all present (upstream's no-op), none for a scrub of a stripe
+// with no spare shard (nothing to compare: it is not read), so those launch
+// nothing.
+uint64_t ragged_chunks(const hec_stripe_desc& d, RaggedOp op, uint32_t chunk_bytes) {
+    const uint32_t m = d.present_mask & 0x3FFFu;
+    if (op == RaggedOp::Decode && m == 0x3FFFu) return 0;
+    if (op == RaggedOp::Scrub && __builtin_popcount(m) <= 10) return 0;
     return (uint64_t(d.shard_len) + chunk_bytes - 1) / chunk_bytes;
 }
 
@@ -275,18 +282,27 @@ const char* ragged_name(const RaggedPick& p, bool decode) {
     return "rs104_ragged_kernel<DEC=false> (table lookup, XCD eighths)";
 }
 
-// Device-resident ragged batches: stripe descriptors come from the host, data
-// stays in HBM. Descriptors -> RaggedItems + workgroup map in pinned staging,
-// uploaded on the caller's stream ahead of the kernel.
-int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool decode,
-               uint32_t* d_bad, hipStream_t stream) {
+// Pass 1 of a ragged scrub, shared by gpu_ragged_scrub and
+// hec_ragged_scrub_kernel_name: bit-sliced when every stripe has all 14 shards
+// and a length that is a multiple of 8 KiB (the table check on full masks runs
+// 1.13x the bit-sliced verify on strided batches), else the
+// table check over each stripe's own mask.
+RaggedPick ragged_scrub_pick(const hec_stripe_desc* descs, uint32_t n) {
+    RaggedPick p;
+    p.bitslice = true;
+    for (uint32_t j = 0; j < n && p.bitslice; ++j)
+        p.bitslice = descs[j].shard_len % kBsChunk == 0 && (descs[j].present_mask & 0x3FFFu) == 0x3FFFu;
+    return p;
+}
+
+// The argument and descriptor checks of every device-resident ragged call,
+// all before device work; *n_blocks = the workgroup map's entries.
+int ragged_check_args(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, RaggedOp op,
+                      uint32_t chunk_bytes, uint64_t* n_blocks) {
     if (!rs || !d_base || (n && !descs)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     if (!(rs->k == 10 && rs->m == 4))
         return fail(HEC_ERR_INVALID_ARGUMENT, "ragged device batches are RS(10,4) only");
-    const RaggedPick pick = ragged_pick(descs, n, decode);
-    const bool bitslice = pick.bitslice;
-    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
-    uint64_t n_blocks = 0;
+    *n_blocks = 0;
     for (uint32_t j = 0; j < n; ++j) {
         const hec_stripe_desc& d = descs[j];
         if (d.shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "stripe " + std::to_string(j));
@@ -295,51 +311,120 @@ int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs
             return fail(HEC_ERR_INVALID_ARGUMENT, "stripe " + std::to_string(j) +
                                                       ": offset/stride must be 16-byte aligned, stride >= len");
         // 64-bit: a shard_len near 2^32 must not wrap to 0 or 1 chunks
-        n_blocks += ragged_chunks(d, decode, chunk_bytes);
-        if (n_blocks > UINT32_MAX) return fail(HEC_ERR_INVALID_ARGUMENT, "ragged batch above 2^32 workgroups");
+        *n_blocks += ragged_chunks(d, op, chunk_bytes);
+        if (*n_blocks > UINT32_MAX) return fail(HEC_ERR_INVALID_ARGUMENT, "ragged batch above 2^32 workgroups");
     }
+    return HEC_OK;
+}
+
+// Descriptors -> RaggedItems + workgroup map in a pinned metadata slot,
+// uploaded on the caller's stream ahead of the kernels that read it. The
+// caller records slot->free after the last of them.
+struct RaggedMeta {
+    Lease<RaggedScratch> lease;
+    MetaSlot* slot = nullptr;
+    size_t map_off = 0, bytes = 0;
+    // waits for this slot's previous kernels only
+    int reserve(uint32_t n, uint64_t n_blocks) {
+        HEC_TRY(lease_slot(lease));
+        map_off = round_up(size_t(n) * sizeof(RaggedItem), 256);
+        bytes = map_off + n_blocks * 4;
+        slot = &lease.sc->slots[lease.sc->next_slot++ % kMetaSlots];
+        return slot->reserve(bytes);
+    }
+    // items and workgroup map written straight into the pinned slot
+    int upload(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, uint8_t* d_base,
+               uint64_t n_blocks, hipStream_t stream, RaggedArgs& ra) {
+        RaggedItem* items = reinterpret_cast<RaggedItem*>(slot->h.p);
+        uint32_t* block_item = reinterpret_cast<uint32_t*>(slot->h + map_off);
+        uint32_t first = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const hec_stripe_desc& d = descs[j];
+            const uint32_t chunks = uint32_t(ragged_chunks(d, op, chunk_bytes));
+            items[j] = RaggedItem{d.offset, d.shard_stride, d.shard_len, d.present_mask, first, 0, 0};
+            std::fill(block_item + first, block_item + first + chunks, j);
+            first += chunks;
+        }
+        HEC_HIP(hipMemcpyAsync(slot->d, slot->h, bytes, hipMemcpyHostToDevice, stream));
+        ra.base = d_base;
+        ra.items = reinterpret_cast<const RaggedItem*>(slot->d.p);
+        ra.block_item = reinterpret_cast<const uint32_t*>(slot->d + map_off);
+        ra.n_blocks = uint32_t(n_blocks);
+        return HEC_OK;
+    }
+};
+
+// Device-resident ragged batches: stripe descriptors come from the host, data
+// stays in HBM.
+int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool decode,
+               uint32_t* d_bad, hipStream_t stream) {
+    const RaggedOp op = decode ? RaggedOp::Decode : RaggedOp::Encode;
+    const bool bitslice = (n == 0 || descs) && ragged_pick(descs, n, decode).bitslice;  // a null list fails below
+    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
+    uint64_t n_blocks;
+    HEC_TRY(ragged_check_args(rs, d_base, descs, n, op, chunk_bytes, &n_blocks));
     if (n == 0) return HEC_OK;
     GeomDevice* gd;
     int rc = geom_device(rs, &gd);
     if (rc) return rc;
-    Lease<RaggedScratch> lease;
-    if ((rc = lease_slot(lease))) return rc;
-    RaggedScratch* sc = lease.sc;
-    const size_t items_bytes = size_t(n) * sizeof(RaggedItem);
-    const size_t map_off = round_up(items_bytes, 256);
-    const size_t meta = map_off + n_blocks * 4;
-    MetaSlot& slot = sc->slots[sc->next_slot++ % kMetaSlots];
-    if ((rc = slot.reserve(meta))) return rc;  // waits for this slot's previous kernel only
-    if (decode && (rc = ensure_dense_decode(rs, gd, sc->stream))) return rc;
-    // items and workgroup map written straight into the pinned slot
-    RaggedItem* items = reinterpret_cast<RaggedItem*>(slot.h.p);
-    uint32_t* block_item = reinterpret_cast<uint32_t*>(slot.h + map_off);
-    uint32_t first = 0;
-    for (uint32_t j = 0; j < n; ++j) {
-        const hec_stripe_desc& d = descs[j];
-        const uint32_t chunks = uint32_t(ragged_chunks(d, decode, chunk_bytes));
-        items[j] = RaggedItem{d.offset, d.shard_stride, d.shard_len, d.present_mask, first, 0, 0};
-        std::fill(block_item + first, block_item + first + chunks, j);
-        first += chunks;
-    }
-    HEC_HIP(hipMemcpyAsync(slot.d, slot.h, meta, hipMemcpyHostToDevice, stream));
+    RaggedMeta meta;
+    if ((rc = meta.reserve(n, n_blocks))) return rc;
+    if (decode && (rc = ensure_dense_decode(rs, gd, meta.lease.sc->stream))) return rc;
     RaggedArgs ra{};
-    ra.base = d_base;
-    ra.items = reinterpret_cast<const RaggedItem*>(slot.d.p);
-    ra.block_item = reinterpret_cast<const uint32_t*>(slot.d + map_off);
-    ra.n_blocks = uint32_t(n_blocks);
+    if ((rc = meta.upload(descs, n, op, chunk_bytes, d_base, n_blocks, stream, ra))) return rc;
     ra.tabs = decode ? gd->decode_dense.tabs : gd->encode.tabs;
     ra.lut = decode ? gd->decode_dense.lut : nullptr;
     ra.bad_count = d_bad;
     if (n_blocks == 0) {  // every stripe already complete (upstream no-op)
-        HEC_HIP(hipEventRecord(slot.free, stream));
+        HEC_HIP(hipEventRecord(meta.slot->free, stream));
         return HEC_OK;
     }
     if (bitslice)
         HEC_HIP(launch_rs104_bs_ragged(ra, stream));
     else
         HEC_HIP(launch_rs104_ragged(ra, decode, stream));
-    HEC_HIP(hipEventRecord(slot.free, stream));
+    HEC_HIP(hipEventRecord(meta.slot->free, stream));
+    return HEC_OK;
+}
+
+// hec_gpu_verify_ragged (d_suspects == nullptr, locate == false) and
+// hec_gpu_locate_corrupt_ragged: the masked verify, and its locate pass over
+// the flagged stripes, on a ragged batch. Pass 2 walks pass 1's map.
+int gpu_ragged_scrub(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool locate,
+                     uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad, uint32_t* d_unchecked,
+                     hipStream_t stream) {
+    if (!d_check || (locate && !d_suspects)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    const bool bitslice = (n == 0 || descs) && ragged_scrub_pick(descs, n).bitslice;  // a null list fails below
+    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
+    uint64_t n_blocks;
+    HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Scrub, chunk_bytes, &n_blocks));
+    if (n == 0) return HEC_OK;
+    uint32_t unchecked = 0;  // stripes without a spare shard: no map entry, never read
+    for (uint32_t j = 0; j < n; ++j) unchecked += __builtin_popcount(descs[j].present_mask & 0x3FFFu) <= 10;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    HEC_TRY(ensure_check_plans(rs, gd, stream));  // before any launch: its first call uploads and waits
+    RaggedMeta meta;
+    HEC_TRY(meta.reserve(n, n_blocks));
+    RaggedScrubArgs v{};
+    HEC_TRY(meta.upload(descs, n, RaggedOp::Scrub, chunk_bytes, const_cast<uint8_t*>(d_base) /* only read */,
+                        n_blocks, stream, v.a));
+    v.a.tabs = gd->check.tabs;
+    v.a.lut = gd->check.lut;
+    v.a.bad_count = d_bad;
+    v.check = d_check;
+    v.suspects = d_suspects;
+    v.ratio_tabs = gd->check_ratio.tabs;
+    // the kernels only ever OR bits in: stale words must not leak through
+    HEC_HIP(hipMemsetAsync(d_check, 0, size_t(n) * 4, stream));
+    if (locate) HEC_HIP(hipMemsetAsync(d_suspects, 0, size_t(n) * 4, stream));
+    if (unchecked && d_unchecked) HEC_HIP(launch_add_word(d_unchecked, unchecked, stream));
+    if (n_blocks) {
+        HEC_HIP(launch_ragged_check(v, bitslice, stream));
+        // pass 2: only the stripes pass 1 flagged are read again (the counts are pass 1's)
+        if (locate) HEC_HIP(launch_ragged_locate(v, bitslice, stream));
+    }
+    HEC_HIP(hipEventRecord(meta.slot->free, stream));
     return HEC_OK;
 }
 
@@ -356,6 +441,25 @@ int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_
 int hec_gpu_reconstruct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
                                uint32_t n_stripes, uint32_t* d_bad_stripes, void* stream) {
     return hec::gpu_ragged(rs, d_base, descs, n_stripes, true, d_bad_stripes, static_cast<hipStream_t>(stream));
+}
+
+int hec_gpu_verify_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
+                          uint32_t n_stripes, uint32_t* d_check, uint32_t* d_bad_stripes, uint32_t* d_unchecked,
+                          void* stream) {
+    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, false, d_check, nullptr, d_bad_stripes, d_unchecked,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int hec_gpu_locate_corrupt_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
+                                  uint32_t n_stripes, uint32_t* d_check, uint32_t* d_suspects,
+                                  uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream) {
+    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, true, d_check, d_suspects, d_bad_stripes, d_unchecked,
+                                 static_cast<hipStream_t>(stream));
+}
+
+const char* hec_ragged_scrub_kernel_name(const hec_stripe_desc* descs, uint32_t n_stripes) {
+    if (n_stripes && !descs) return "invalid argument";
+    return hec::ragged_scrub_kernel_name(hec::ragged_scrub_pick(descs, n_stripes).bitslice);
 }
 
 const char* hec_ragged_kernel_name(const hec_stripe_desc* descs, uint32_t n_stripes, int decode) {

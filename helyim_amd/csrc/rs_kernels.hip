@@ -33,6 +33,9 @@
 //  * The masked verify and locate (rs104_check_kernel and siblings) are the
 //    degraded scrub: the mask-driven decode with its stores replaced by a
 //    compare against the spare present shards.
+//  * The ragged scrub (rs104_bs_ragged_verify_kernel, rs104_ragged_check_kernel
+//    and the masked locate's RAGGED walk) is that scrub over stripes of mixed
+//    lengths and masks: the ragged workgroup map in front of the same bodies.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -673,17 +676,25 @@ __global__ __launch_bounds__(kThreads) void rs104_bs_ragged_kernel(RaggedArgs a)
     if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
 }
 
+// The batch of either ragged kernel argument struct.
+static RaggedArgs& ragged_args(RaggedArgs& a) { return a; }
+static RaggedArgs& ragged_args(RaggedScrubArgs& v) { return v.a; }
+
 // A ragged batch through `kern`, in launches of at most kMaxLaunchBlocks
 // workgroups (launch_split.hpp).
-static hipError_t launch_ragged(void (*kern)(RaggedArgs), const RaggedArgs& a, hipStream_t stream) {
+template <typename Args>
+static hipError_t launch_ragged(void (*kern)(Args), const Args& v, hipStream_t stream) {
+    Args w = v;
+    RaggedArgs& r = ragged_args(w);
+    const RaggedArgs a = r;
     for (uint64_t i = 0, n = n_ranges(a.n_blocks, kMaxLaunchBlocks); i < n; ++i) {
         const BlockLaunch l = block_launch(a.n_blocks, kMaxLaunchBlocks, i);
-        RaggedArgs r = a;
+        r = a;
         r.block_base = l.block_base;
         r.map_q8 = l.map_q8;
         r.map_r8 = l.map_r8;
         if (!l.last) r.done_flag = nullptr;  // the last launch signals
-        hipLaunchKernelGGL(kern, dim3(l.n_blocks), dim3(kThreads), 0, stream, r);
+        hipLaunchKernelGGL(kern, dim3(l.n_blocks), dim3(kThreads), 0, stream, w);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1517,17 +1528,51 @@ hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream) {
 // its syndrome is complete before its first store, so names and values are
 // those of the bytes as they were. Unexplained columns, and every column of a
 // stripe with fewer spares, are not touched.
-template <bool ALIGNED, bool CORRECT = false>
+//
+// RAGGED (rs104_ragged_locate_kernel, hec.h hec_gpu_locate_corrupt_ragged): the
+// same classification over a ragged batch. Only the walk differs: the items
+// are the 4 KiB ranges of pass 1's workgroup map (two per entry when that map
+// is the bit-sliced one: no second map is built), and the stripe's base,
+// stride, length and mask come from its RaggedItem. An item of a clean stripe
+// costs the scalar loads of block_item[entry] and check[stripe]; neither its
+// RaggedItem nor a shard is touched. The two walks are compile-time branches
+// in the body, not device functions over the argument structs: with accessor
+// functions that take the arguments by reference, or the body as a function
+// of its own, the backend allocates the registers of the strided form
+// differently (profiles/ragged_scrub/isa.md); written this way the strided
+// forms keep their instruction streams.
+template <bool ALIGNED, bool CORRECT = false, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
-    std::conditional_t<CORRECT, CorrectPresentArgs, CheckArgs> v) {
+    std::conditional_t<RAGGED, RaggedScrubArgs, std::conditional_t<CORRECT, CorrectPresentArgs, CheckArgs>> v) {
+    static_assert(!(RAGGED && CORRECT), "the ragged walk only classifies");
     constexpr int K = 10, N = 14, R = 4;
-    const ApplyArgs& a = v.a;
+    const auto& a = v.a;  // ApplyArgs, or the ragged batch
     cu32p flagged = as_const(v.check);
-    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
-        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
-        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+    uint64_t n_items;
+    if constexpr (RAGGED)
+        n_items = uint64_t(a.n_blocks) << v.half_shift;
+    else
+        n_items = a.n_items;
+    for (uint64_t item = stride_first_item(); item < n_items; item += gridDim.x) {
+        uint32_t stripe, chunk;
+        if constexpr (RAGGED) {
+            stripe = as_const(a.block_item)[item >> v.half_shift];
+            // the range within its entry; the entry's place in the stripe is added past the flag check
+            chunk = uint32_t(item) & ((1u << v.half_shift) - 1u);
+        } else {
+            stripe = uint32_t(item / a.chunks_per_stripe);
+            chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        }
         if (flagged[stripe] == 0) continue;  // pass 1 found the stripe clean, or had nothing to check
-        const uint32_t mask = as_const(a.masks)[stripe] & ((1u << N) - 1);
+        [[maybe_unused]] const __attribute__((address_space(4))) RaggedItem* it = nullptr;
+        uint32_t mask;
+        if constexpr (RAGGED) {
+            it = as_const(a.items) + stripe;
+            chunk += (uint32_t(item >> v.half_shift) - it->first_block) << v.half_shift;
+            mask = it->mask & ((1u << N) - 1);
+        } else {
+            mask = as_const(a.masks)[stripe] & ((1u << N) - 1);
+        }
         const uint32_t pid = as_const(a.lut)[mask];
         if (pid == kNoPlan) continue;  // never flagged by pass 1
         const uint32_t r = uint32_t(__builtin_popcount(mask)) - K;
@@ -1545,27 +1590,37 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
         }
         cu32p tab = as_const(a.tabs) + pid * (K * R * 5);              // A_m: [K][R][5] words
         cu32p rat = as_const(v.ratio_tabs) + pid * (K * (R - 1) * 5);  // [K][R - 1][5] words
-        const uint8_t* b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        const uint8_t* b;  // the stripe's shard 0; its shard stride and length
+        uint64_t shard, len;
+        if constexpr (RAGGED) {
+            b = a.base + it->off;
+            shard = it->shard_stride;
+            len = it->len;
+        } else {
+            b = a.in_base + uint64_t(stripe) * a.in_stripe;
+            shard = a.in_shard;
+            len = a.len;
+        }
         const uint64_t o = uint64_t(chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;
         u32x4 s[R];
 #pragma unroll
         for (int j = 0; j < R; ++j) s[j] = u32x4{0, 0, 0, 0};
-        if (o < a.len) {
-            const uint64_t avail = a.len - o;
+        if (o < len) {
+            const uint64_t avail = len - o;
             if (avail >= kVecBytes) {
                 u32x4 d[K];
 #pragma unroll
-                for (int i = 0; i < K; ++i) d[i] = load_full(b + uint64_t(in_id[i]) * a.in_shard + o, ALIGNED);
+                for (int i = 0; i < K; ++i) d[i] = load_full(b + uint64_t(in_id[i]) * shard + o, ALIGNED);
 #pragma unroll
                 for (int i = 0; i < K; ++i) gf_mac<R>(s, d[i], tab + i * (R * 5));
 #pragma unroll
                 for (int j = 0; j < R; ++j)
-                    if (uint32_t(j) < r) s[j] ^= load_full(b + uint64_t(out_id[j]) * a.in_shard + o, ALIGNED);
+                    if (uint32_t(j) < r) s[j] ^= load_full(b + uint64_t(out_id[j]) * shard + o, ALIGNED);
             } else {
                 for (int i = 0; i < K; ++i)
-                    gf_mac<R>(s, load_tail(b + uint64_t(in_id[i]) * a.in_shard + o, avail), tab + i * (R * 5));
+                    gf_mac<R>(s, load_tail(b + uint64_t(in_id[i]) * shard + o, avail), tab + i * (R * 5));
                 for (int j = 0; j < R; ++j)
-                    if (uint32_t(j) < r) s[j] ^= load_tail(b + uint64_t(out_id[j]) * a.in_shard + o, avail);
+                    if (uint32_t(j) < r) s[j] ^= load_tail(b + uint64_t(out_id[j]) * shard + o, avail);
             }
         }
         uint32_t any = 0;
@@ -1690,6 +1745,131 @@ hipError_t launch_correct_present(const CorrectPresentArgs& v, bool aligned, hip
     if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
     return launch_stride(aligned ? rs104_correct_present_kernel<true> : rs104_correct_present_kernel<false>, v, stream,
                          kLocateMaxBlocks);
+}
+
+// ---------------------------------------------------------------------------
+// Ragged scrub (hec.h hec_gpu_verify_ragged / hec_gpu_locate_corrupt_ragged):
+// the masked verify and locate over stripes of mixed lengths and masks. Pass 1
+// is one workgroup per map entry (launch_ragged: XCD eighths, launches of at
+// most kMaxLaunchBlocks), pass 2 the masked locate's RAGGED walk over the same
+// map. The stripe index of a map entry is the entry itself (block_item), so
+// both passes reach the stripe's result words without a search.
+// ---------------------------------------------------------------------------
+// Every mask full and every length a multiple of 8 KiB:
+// rs104_bs_ragged_kernel's addressing over the verify form of rs104_bs_chunk
+// (the stored parity handed over as base + offset, as rs104_bs_verify_kernel
+// does). Its bits are by parity row; the check word's are by shard index.
+__global__ __launch_bounds__(kThreads) void rs104_bs_ragged_verify_kernel(RaggedScrubArgs v) {
+    const RaggedArgs& a = v.a;
+    const uint32_t blk = ragged_block(a);
+    const uint32_t stripe = as_const(a.block_item)[blk];
+    const __attribute__((address_space(4))) RaggedItem* it = as_const(a.items) + stripe;
+    const uint64_t off = it->off, stride = it->shard_stride;
+    const uint32_t first = it->first_block;
+    const uint32_t bits =
+        rs104_bs_chunk<uint32_t, true>(a.base + off, a.base, stride, stride, blk - first, off + 10 * stride);
+    report_mismatch(v.check + stripe, a.bad_count, bits << 10);
+}
+
+// Everything else: rs104_check_kernel's loads-first shape at rs104_chunk's 16
+// bytes per lane, one 4 KiB range per workgroup, any length >= 1. The ten B
+// loads and the r stored E loads are issued before the math and the plan
+// lookup overlaps them; the last vector of a shard goes through load_tail,
+// which zero-fills from the length on, inputs and stored rows alike, so bytes
+// at or past it compare equal whatever memory holds there. Lanes past the end
+// load nothing and keep zeros; they still take part in the ballots.
+__global__ __launch_bounds__(kThreads) void rs104_ragged_check_kernel(RaggedScrubArgs v) {
+    constexpr int K = 10, N = 14, R = 4;
+    const RaggedArgs& a = v.a;
+    const uint32_t blk = ragged_block(a);
+    const uint32_t stripe = as_const(a.block_item)[blk];
+    const __attribute__((address_space(4))) RaggedItem* it = as_const(a.items) + stripe;
+    const uint64_t off = it->off, stride = it->shard_stride;
+    const uint32_t len = it->len, first = it->first_block;
+    const uint32_t mask = it->mask & ((1u << N) - 1);
+    const uint32_t present = __builtin_popcount(mask);
+    if (present <= K) return;  // owns no map entry (the host counts it): never taken
+    const uint32_t r = present - K;
+    uint32_t in_id[K], out_id[R];
+    uint32_t m = mask;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {  // B: the ten lowest present shards
+        in_id[i] = __builtin_ctz(m);
+        m &= m - 1;
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {  // E: the other present shards, ascending
+        out_id[j] = m ? __builtin_ctz(m) : 0;
+        m &= m - 1;
+    }
+    uint32_t plan = as_const(a.lut)[mask];  // first used after the data loads
+    const uint8_t* b = a.base + off;
+    const uint32_t o = (blk - first) * uint32_t(kThreads * kVecBytes) + threadIdx.x * kVecBytes;
+    u32x4 acc[R], st[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j] = st[j] = u32x4{0, 0, 0, 0};
+    if (o < len) {
+        const uint32_t avail = len - o;
+        if (avail >= uint32_t(kVecBytes)) {
+            u32x4 d[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) d[i] = load_at(b + uint64_t(in_id[i]) * stride, o);
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+                if (uint32_t(j) < r) st[j] = load_at(b + uint64_t(out_id[j]) * stride, o);
+            __builtin_amdgcn_sched_barrier(0);  // every load in flight before the math
+            asm volatile("" : "+s"(plan));
+            cu32p tab = as_const(a.tabs) + plan * (K * R * 5);
+#pragma unroll
+            for (int i = 0; i < K; i += 2)
+                gf_mac2<R>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), r);
+        } else {
+            asm volatile("" : "+s"(plan));
+            cu32p tab = as_const(a.tabs) + plan * (K * R * 5);
+            // rows at or past r: zero tables, no stored row
+            for (int i = 0; i < K; ++i)
+                gf_mac<R>(acc, load_tail(b + uint64_t(in_id[i]) * stride + o, avail), tab + i * (R * 5));
+            for (int j = 0; j < R; ++j)
+                if (uint32_t(j) < r) st[j] = load_tail(b + uint64_t(out_id[j]) * stride + o, avail);
+        }
+    }
+    // rows at or past r: acc and st are both zero, the ballot is empty
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const u32x4 x = acc[j] ^ st[j];
+        bits |= (__ballot((x[0] | x[1] | x[2] | x[3]) != 0) != 0 ? 1u : 0u) << out_id[j];
+    }
+    report_mismatch(v.check + stripe, a.bad_count, bits);
+}
+
+constexpr const char* kBsRaggedVerifyName = "rs104_bs_ragged_verify_kernel (bit-sliced, XCD eighths)";
+constexpr const char* kRaggedCheckName = "rs104_ragged_check_kernel (table lookup, XCD eighths)";
+
+const char* ragged_scrub_kernel_name(bool bitslice) { return bitslice ? kBsRaggedVerifyName : kRaggedCheckName; }
+
+hipError_t launch_ragged_check(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream) {
+    return launch_ragged(bitslice ? rs104_bs_ragged_verify_kernel : rs104_ragged_check_kernel, v, stream);
+}
+
+// rs104_ragged_locate_kernel: the masked locate's RAGGED form, taking RaggedScrubArgs.
+constexpr auto rs104_ragged_locate_kernel = rs104_locate_present_kernel<true, false, true>;
+
+hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream) {
+    RaggedScrubArgs w = v;
+    w.half_shift = bitslice ? 1u : 0u;  // an 8 KiB entry is two of the walk's 4 KiB ranges
+    const uint64_t items = uint64_t(w.a.n_blocks) << w.half_shift;
+    if (items == 0) return hipSuccess;
+    const uint64_t grid = std::min<uint64_t>(items, kLocateMaxBlocks);  // grid-stride covers the rest
+    hipLaunchKernelGGL(rs104_ragged_locate_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, w);
+    return hipGetLastError();
+}
+
+__global__ void add_word_kernel(uint32_t* word, uint32_t n) { atomicAdd(word, n); }
+
+hipError_t launch_add_word(uint32_t* word, uint32_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(add_word_kernel, dim3(1), dim3(1), 0, stream, word, n);
+    return hipGetLastError();
 }
 
 // repair_masks_kernel with the present mask and the check word taken into

@@ -248,6 +248,37 @@ hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* c
 // Name of the kernel an aligned masked verify of this shard length runs.
 const char* check_kernel_name(uint64_t len);
 
+// Ragged scrub (hec.h hec_gpu_verify_ragged / hec_gpu_locate_corrupt_ragged):
+// the masked verify and locate over a ragged batch, every stripe with its own
+// length and present mask (RaggedItem::mask). a: the batch, only read -- base,
+// items, the workgroup map, tabs / lut = the check plan set (its dense LUT
+// holds the full mask's plan too), bad_count = the optional count of stripes
+// with a non-zero word. Stripes with 10 or fewer shards present own no map
+// entry: they are never read, and the host counts them. check and suspects
+// must be zero at launch.
+struct RaggedScrubArgs {
+    RaggedArgs a;
+    uint32_t* check;                       // one word per stripe, bits by shard index
+    uint32_t* suspects = nullptr;          // launch_ragged_locate only
+    const uint32_t* ratio_tabs = nullptr;  // launch_ragged_locate only: CheckArgs::ratio_tabs
+    uint32_t half_shift = 0;               // launch_ragged_locate sets it: 2^half_shift 4 KiB ranges per map entry
+};
+// Pass 1, one workgroup per map entry. bitslice: every mask full and every
+// length a multiple of kBsChunk, the map in kBsChunk entries
+// (rs104_bs_chunk<uint32_t, true>, its four bits moved to shards 10..13);
+// otherwise 4 KiB entries and the table check over lut[mask], any length >= 1.
+hipError_t launch_ragged_check(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream);
+// Name of the kernel launch_ragged_check runs.
+const char* ragged_scrub_kernel_name(bool bitslice);
+// Pass 2 after launch_ragged_check on the same stream and the same map:
+// launch_locate_present's classification, a grid-stride loop over the map
+// entries on at most kLocateMaxBlocks workgroups; an entry of a stripe whose
+// check word is 0 costs two scalar loads. A bit-sliced map is walked as two
+// 4 KiB halves per entry.
+hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream);
+// *word += n, in stream order (the ragged scrub's count of unchecked stripes).
+hipError_t launch_add_word(uint32_t* word, uint32_t n, hipStream_t stream);
+
 // splitmix64 byte stream per stripe (bench/test data generator):
 // stripe s: bytes_per_stripe bytes at base + s*stripe_stride, word n (n>=1) =
 // mix(seed_base + s + n*gamma), little endian.

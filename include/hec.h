@@ -703,6 +703,68 @@ int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_
 int hec_gpu_reconstruct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
                                uint32_t n_stripes, uint32_t* d_bad_stripes, void* stream);
 
+/* Ragged scrub (RS(10,4)): the masked verify and the masked locate over a
+ * ragged batch, stripes of mixed lengths and mixed present masks in one pass
+ * over HBM (plus, for the locate, a second pass over the flagged stripes
+ * only). The result contracts are exactly hec_gpu_verify_present_batch's and
+ * hec_gpu_locate_corrupt_present_batch's, evaluated per stripe with m =
+ * descs[s].present_mask & 0x3FFF and that stripe's own shard_len:
+ *   - d_check[s]: bit e, by shard index, for every spare shard e in E whose
+ *     syndrome row is non-zero somewhere in the stripe;
+ *   - d_suspects[s]: bit c when present shard c alone explains a byte column,
+ *     HEC_SUSPECT_UNEXPLAINED (bit 31) for every other non-zero column and for
+ *     every non-zero column when r == 1;
+ *   - a stripe with p <= 10 present shards is not read: its words are 0 and it
+ *     adds one to *d_unchecked (device word, optional, accumulated);
+ *   - *d_bad_stripes (device word, optional, accumulated): plus one per stripe
+ *     with a non-zero check word, exactly once however many column ranges,
+ *     waves or launches report the stripe;
+ *   - a full mask gives hec_gpu_locate_corrupt_batch's words, d_check = its
+ *     d_mismatch shifted left by 10.
+ * Words [0, n_stripes) of each result array are cleared on `stream` and then
+ * written; no other byte anywhere is written (no shard, no gap, not word
+ * n_stripes), absent shards are never read, and bytes at or past a stripe's
+ * shard_len take no part. d_check and d_suspects are distinct device arrays
+ * that overlap nothing else (not checked). descs are HOST memory; layout and
+ * alignment rules are hec_gpu_encode_ragged's (d_base, offset and stride
+ * 16-byte aligned, stride >= shard_len >= 1). Errors, all before any device
+ * work: a null rs, d_base, d_check (for the locate also d_suspects), or descs
+ * with n_stripes > 0, and a misaligned or overlapping stripe:
+ * HEC_ERR_INVALID_ARGUMENT; any other codec: HEC_ERR_INVALID_ARGUMENT, the
+ * detail says "RS(10,4) only"; shard_len == 0: HEC_ERR_EMPTY_SHARD, the detail
+ * names the stripe; a batch above 2^32 column ranges: HEC_ERR_INVALID_ARGUMENT.
+ * With valid pointers n_stripes == 0 returns HEC_OK and writes nothing.
+ * Asynchronous on `stream`; the host waits only as the other ragged calls do
+ * (for the call four ragged calls ago that used the same metadata slot, and
+ * once per device for the plan upload).
+ * Pass 1 runs bit-sliced when every stripe has all 14 shards and a length that
+ * is a multiple of 8 KiB, otherwise as a table check that takes any length
+ * (hec_ragged_scrub_kernel_name reports which).
+ * Repair is the caller's, with the calls that exist: read d_suspects, clear
+ * the named bits in the stripe's present_mask on the host (where bit 31 is
+ * clear and at least 10 bits remain), and call hec_gpu_reconstruct_ragged;
+ * hec_gpu_verify_ragged with the original masks is the proof.
+ * Measured on one MI355X against the strided calls on the same bytes in the
+ * same process, 4096 x 1 MiB stripes with a 64 KiB shard pad, medians of 9
+ * alternating rounds, the map's upload included (tools/bench_ragged_scrub.py,
+ * profiles/ragged_scrub/bench_ragged_scrub.json): full masks, bit-sliced,
+ * 8.86 ms against hec_gpu_verify_batch's 8.75 (8.73..8.78 over the rounds),
+ * 1.012x, outside that spread (1.005x in two other runs of the tool, inside
+ * the spread in one of them); one shard of every stripe erased 8.48 ms against
+ * hec_gpu_verify_present_batch's 8.13 (8.10..8.26), 1.044x, outside; the locate
+ * with 64 stripes holding a flipped byte 9.50 ms against
+ * hec_gpu_locate_corrupt_batch's 9.12 (9.10..9.14), 1.041x, outside. A uniform
+ * batch is cheaper through the strided calls; what this call is for is the
+ * mixed batch: 2048 stripes of 64 KiB..4 MiB with 0..3 shards lost each, 25.2
+ * GB read in 4.09 ms, 6.17 TB/s, 0.77 of 8 TB/s, in one call (6.26 and 6.53
+ * TB/s in the other two runs). */
+int hec_gpu_verify_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
+                          uint32_t n_stripes, uint32_t* d_check, uint32_t* d_bad_stripes,
+                          uint32_t* d_unchecked, void* stream);
+int hec_gpu_locate_corrupt_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
+                                  uint32_t n_stripes, uint32_t* d_check, uint32_t* d_suspects,
+                                  uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream);
+
 /* Deterministic splitmix64 stripe data (bench / test inputs): stripe s gets
  * bytes_per_stripe bytes at d_base + s*stripe_stride, 64-bit word n (n >= 1)
  * = splitmix64_mix(seed_base + s + n * 0x9E3779B97F4A7C15), little endian. */
@@ -1002,6 +1064,9 @@ const char* hec_check_kernel_name(uint64_t shard_len);
  * (decode != 0) runs on these descriptors: the same choice the launch makes
  * (static string). */
 const char* hec_ragged_kernel_name(const hec_stripe_desc* descs, uint32_t n_stripes, int decode);
+/* Pass-1 kernel hec_gpu_verify_ragged / hec_gpu_locate_corrupt_ragged run on
+ * these descriptors: the same choice the launch makes (static string). */
+const char* hec_ragged_scrub_kernel_name(const hec_stripe_desc* descs, uint32_t n_stripes);
 
 #ifdef __cplusplus
 }

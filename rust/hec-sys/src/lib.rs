@@ -224,6 +224,13 @@ extern "C" {
                                  n_stripes: u32, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_reconstruct_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
                                       n_stripes: u32, d_bad_stripes: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_verify_ragged(rs: *const hec_rs_t, d_base: *const u8, descs: *const hec_stripe_desc,
+                                 n_stripes: u32, d_check: *mut u32, d_bad_stripes: *mut u32,
+                                 d_unchecked: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_locate_corrupt_ragged(rs: *const hec_rs_t, d_base: *const u8, descs: *const hec_stripe_desc,
+                                         n_stripes: u32, d_check: *mut u32, d_suspects: *mut u32,
+                                         d_bad_stripes: *mut u32, d_unchecked: *mut u32,
+                                         stream: *mut c_void) -> c_int;
     pub fn hec_gpu_fill_splitmix(d_base: *mut u8, stripe_stride: u64, bytes_per_stripe: u64, n_stripes: u32,
                                  seed_base: u64, stream: *mut c_void) -> c_int;
 
@@ -303,4 +310,5 @@ extern "C" {
     pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_check_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_ragged_kernel_name(descs: *const hec_stripe_desc, n_stripes: u32, decode: c_int) -> *const c_char;
+    pub fn hec_ragged_scrub_kernel_name(descs: *const hec_stripe_desc, n_stripes: u32) -> *const c_char;
 }
