@@ -39,7 +39,8 @@ _BATCH_VERIFY = ("verify_batch", "verify_batch_sep", "host_verify_batch", "verif
                  "verify_present_batch", "locate_corrupt_present_batch", "reconstruct_checked_batch",
                  "correct_present_batch", "reconstruct_corrected_batch",
                  "check_kernel_name",
-                 "verify_ragged", "locate_corrupt_ragged", "ragged_scrub_kernel_name")
+                 "verify_ragged", "locate_corrupt_ragged", "ragged_scrub_kernel_name",
+                 "correct_ragged", "reconstruct_corrected_ragged")
 
 
 def __getattr__(name):

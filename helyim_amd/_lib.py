@@ -89,6 +89,8 @@ SIGNATURES = {
     "hec_gpu_reconstruct_ragged": (_I, [_P, _P, _P, _U32, _P, _P]),
     "hec_gpu_verify_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P]),
     "hec_gpu_locate_corrupt_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    "hec_gpu_correct_ragged": (_I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "hec_gpu_reconstruct_corrected_ragged": (_I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "hec_gpu_fill_splitmix": (_I, [_P, _U64, _U64, _U32, _U64, _P]),
     "hec_write_ec_files": (_I, [ctypes.c_char_p]),
     "hec_write_ec_files_ex": (_I, [ctypes.c_char_p, _U64, _U64, _U64]),

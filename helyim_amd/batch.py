@@ -621,6 +621,53 @@ def locate_corrupt_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: tor
     return check, suspects
 
 
+def correct_ragged(rs: ReedSolomon, base: torch.Tensor, descs, min_spares: int = 2, check: torch.Tensor = None,
+                   suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, unchecked: torch.Tensor = None,
+                   uncorrected: torch.Tensor = None, corrected_bytes: torch.Tensor = None, stream=None):
+    """locate_corrupt_ragged that also fixes, in place, every byte column one
+    present shard explains (hec_gpu_correct_ragged): correct_present_batch's
+    contract stripe by stripe, each stripe with its own length and present
+    mask. Returns ``(check, suspects)`` of the bytes as they were before the
+    call. Only stripes with min_spares (2, 3 or 4) or more spare shards are
+    written; a column that sets bit 31 keeps its bytes; absent shards, bytes
+    at or past a stripe's length and the gaps between stripes are never
+    touched. uncorrected, corrected_bytes: as correct_present_batch's.
+    Asynchronous on the stream."""
+    d = _desc_array(descs, base, rs.total_shard_count())
+    check = _words_arg(len(d), check, "check")
+    suspects = _words_arg(len(d), suspects, "suspects")
+    check_status(lib.hec_gpu_correct_ragged(
+        rs.handle, base.data_ptr(), d.ctypes.data, len(d), int(min_spares), check.data_ptr(), suspects.data_ptr(),
+        _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"),
+        _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
+        _stream_ptr(stream)))
+    return check, suspects
+
+
+def reconstruct_corrected_ragged(rs: ReedSolomon, base: torch.Tensor, descs, min_spares: int = 2,
+                                 check: torch.Tensor = None, suspects: torch.Tensor = None,
+                                 use_masks: torch.Tensor = None, bad_stripes: torch.Tensor = None,
+                                 unrepaired: torch.Tensor = None, corrected_bytes: torch.Tensor = None, stream=None):
+    """Correct the survivors of a ragged batch, then rebuild the lost shards
+    from them, in one call (hec_gpu_reconstruct_corrected_ragged):
+    reconstruct_corrected_batch's steps stripe by stripe. Returns ``(check,
+    suspects, use_masks)``: a clean or uncheckable stripe, and a dirty one
+    with min_spares or more spare shards whose columns were all corrected, is
+    rebuilt from its present shards (use mask = present mask); any other dirty
+    stripe keeps its holes (use mask 0x3FFF) and is counted into unrepaired.
+    bad_stripes counts the stripes with fewer than ten shards. Run
+    verify_ragged with full masks afterwards for proof."""
+    d = _desc_array(descs, base, rs.total_shard_count())
+    check = _words_arg(len(d), check, "check")
+    suspects = _words_arg(len(d), suspects, "suspects")
+    use_masks = _words_arg(len(d), use_masks, "use_masks")
+    check_status(lib.hec_gpu_reconstruct_corrected_ragged(
+        rs.handle, base.data_ptr(), d.ctypes.data, len(d), int(min_spares), check.data_ptr(), suspects.data_ptr(),
+        use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unrepaired, "unrepaired"),
+        _bytes_counter_arg(corrected_bytes, "corrected_bytes"), _stream_ptr(stream)))
+    return check, suspects, use_masks
+
+
 def host_zero_copy(t: torch.Tensor) -> bool:
     """True when host batches on t's bytes are coded zero-copy on the current
     device (hec_host_zero_copy_view): t is one pinned, GPU-addressable range."""

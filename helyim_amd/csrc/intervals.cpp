@@ -320,23 +320,32 @@ int ragged_check_args(const hec_rs_t* rs, const uint8_t* d_base, const hec_strip
 // Descriptors -> RaggedItems + workgroup map in a pinned metadata slot,
 // uploaded on the caller's stream ahead of the kernels that read it. The
 // caller records slot->free after the last of them.
+// The corrected reconstruct keeps a second pair in the same slot, the decode's
+// (its map has entries for every stripe with a shard missing, the scrub's for
+// every stripe with a spare one, so first_block differs between the two).
 struct RaggedMeta {
     Lease<RaggedScratch> lease;
     MetaSlot* slot = nullptr;
     size_t map_off = 0, bytes = 0;
+    size_t items2_off = 0, map2_off = 0;  // the second pair, when there is one
     // waits for this slot's previous kernels only
-    int reserve(uint32_t n, uint64_t n_blocks) {
+    int reserve(uint32_t n, uint64_t n_blocks, bool second = false, uint64_t n_blocks2 = 0) {
         HEC_TRY(lease_slot(lease));
         map_off = round_up(size_t(n) * sizeof(RaggedItem), 256);
         bytes = map_off + n_blocks * 4;
+        if (second) {
+            items2_off = round_up(bytes, 256);
+            map2_off = items2_off + map_off;
+            bytes = map2_off + n_blocks2 * 4;
+        }
         slot = &lease.sc->slots[lease.sc->next_slot++ % kMetaSlots];
         return slot->reserve(bytes);
     }
-    // items and workgroup map written straight into the pinned slot
-    int upload(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, uint8_t* d_base,
-               uint64_t n_blocks, hipStream_t stream, RaggedArgs& ra) {
-        RaggedItem* items = reinterpret_cast<RaggedItem*>(slot->h.p);
-        uint32_t* block_item = reinterpret_cast<uint32_t*>(slot->h + map_off);
+    // items and workgroup map of one pair written straight into the pinned slot
+    void fill(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, size_t items_at,
+              size_t map_at, uint8_t* d_base, uint64_t n_blocks, RaggedArgs& ra) {
+        RaggedItem* items = reinterpret_cast<RaggedItem*>(slot->h + items_at);
+        uint32_t* block_item = reinterpret_cast<uint32_t*>(slot->h + map_at);
         uint32_t first = 0;
         for (uint32_t j = 0; j < n; ++j) {
             const hec_stripe_desc& d = descs[j];
@@ -345,11 +354,18 @@ struct RaggedMeta {
             std::fill(block_item + first, block_item + first + chunks, j);
             first += chunks;
         }
-        HEC_HIP(hipMemcpyAsync(slot->d, slot->h, bytes, hipMemcpyHostToDevice, stream));
         ra.base = d_base;
-        ra.items = reinterpret_cast<const RaggedItem*>(slot->d.p);
-        ra.block_item = reinterpret_cast<const uint32_t*>(slot->d + map_off);
+        ra.items = reinterpret_cast<const RaggedItem*>(slot->d + items_at);
+        ra.block_item = reinterpret_cast<const uint32_t*>(slot->d + map_at);
         ra.n_blocks = uint32_t(n_blocks);
+    }
+    // decode2: the arguments of the second pair, a 4 KiB decode map of n_blocks2 entries
+    int upload(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, uint8_t* d_base,
+               uint64_t n_blocks, hipStream_t stream, RaggedArgs& ra, RaggedArgs* decode2 = nullptr,
+               uint64_t n_blocks2 = 0) {
+        fill(descs, n, op, chunk_bytes, 0, map_off, d_base, n_blocks, ra);
+        if (decode2) fill(descs, n, RaggedOp::Decode, 4096, items2_off, map2_off, d_base, n_blocks2, *decode2);
+        HEC_HIP(hipMemcpyAsync(slot->d, slot->h, bytes, hipMemcpyHostToDevice, stream));
         return HEC_OK;
     }
 };
@@ -428,10 +444,89 @@ int gpu_ragged_scrub(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe
     return HEC_OK;
 }
 
+// hec_gpu_correct_ragged (d_use == nullptr, reconstruct == false) and
+// hec_gpu_reconstruct_corrected_ragged: gpu_ragged_scrub's locate with pass 2
+// fixing in place; the reconstruct then sets the use masks and decodes the
+// stripes whose survivors are consistent, from a map of its own in the same
+// metadata slot. d_bad: the scrub's count for the correct, the decode's for
+// the reconstruct; d_left: uncorrected, or unrepaired.
+int gpu_ragged_correct(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n,
+                       uint32_t min_spares, bool reconstruct, uint32_t* d_check, uint32_t* d_suspects,
+                       uint32_t* d_use, uint32_t* d_bad, uint32_t* d_unchecked, uint32_t* d_left,
+                       unsigned long long* d_corrected_bytes, hipStream_t stream) {
+    if (!d_check || !d_suspects || (reconstruct && !d_use)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    const bool bitslice = (n == 0 || descs) && ragged_scrub_pick(descs, n).bitslice;  // a null list fails below
+    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
+    uint64_t n_blocks, n_decode = 0;
+    HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Scrub, chunk_bytes, &n_blocks));
+    if (reconstruct) HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Decode, 4096, &n_decode));
+    HEC_TRY(check_min_spares(min_spares));
+    if (n == 0) return HEC_OK;
+    uint32_t unchecked = 0;  // stripes without a spare shard: no scrub map entry, never read
+    for (uint32_t j = 0; j < n; ++j) unchecked += __builtin_popcount(descs[j].present_mask & 0x3FFFu) <= 10;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    // every plan set before any launch: their first call uploads and waits
+    HEC_TRY(ensure_check_plans(rs, gd, stream));
+    if (reconstruct) HEC_TRY(ensure_dense_decode(rs, gd, stream));
+    RaggedMeta meta;
+    HEC_TRY(meta.reserve(n, n_blocks, reconstruct, n_decode));
+    RaggedCorrectArgs v{};
+    RaggedArgs dec{};
+    HEC_TRY(meta.upload(descs, n, RaggedOp::Scrub, chunk_bytes, d_base, n_blocks, stream, v.a,
+                        reconstruct ? &dec : nullptr, n_decode));
+    v.a.tabs = gd->check.tabs;
+    v.a.lut = gd->check.lut;
+    v.a.bad_count = reconstruct ? nullptr : d_bad;
+    v.check = d_check;
+    v.suspects = d_suspects;
+    v.ratio_tabs = gd->check_ratio.tabs;
+    v.fix_tabs = gd->check_fix.tabs;
+    v.min_spares = min_spares;
+    v.uncorrected = reconstruct ? nullptr : d_left;
+    v.corrected_bytes = d_corrected_bytes;
+    // the kernels only ever OR bits in: stale words must not leak through
+    HEC_HIP(hipMemsetAsync(d_check, 0, size_t(n) * 4, stream));
+    HEC_HIP(hipMemsetAsync(d_suspects, 0, size_t(n) * 4, stream));
+    if (unchecked && d_unchecked) HEC_HIP(launch_add_word(d_unchecked, unchecked, stream));
+    if (n_blocks) {
+        HEC_HIP(launch_ragged_check(v, bitslice, stream));
+        HEC_HIP(launch_ragged_correct(v, bitslice, stream));
+    }
+    if (reconstruct) {
+        HEC_HIP(launch_ragged_use_masks_corrected(v.a.items, const_cast<RaggedItem*>(dec.items), d_check, d_suspects,
+                                                  d_use, d_left, min_spares, n, stream));
+        dec.tabs = gd->decode_dense.tabs;
+        dec.lut = gd->decode_dense.lut;
+        dec.bad_count = d_bad;
+        if (n_decode) HEC_HIP(launch_rs104_ragged(dec, true, stream));
+    }
+    HEC_HIP(hipEventRecord(meta.slot->free, stream));
+    return HEC_OK;
+}
+
 }  // namespace
 }  // namespace hec
 
 extern "C" {
+
+int hec_gpu_correct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n_stripes,
+                           uint32_t min_spares, uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                           uint32_t* d_unchecked, uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes,
+                           void* stream) {
+    return hec::gpu_ragged_correct(rs, d_base, descs, n_stripes, min_spares, false, d_check, d_suspects, nullptr,
+                                   d_bad_stripes, d_unchecked, d_uncorrected, d_corrected_bytes,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int hec_gpu_reconstruct_corrected_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
+                                         uint32_t n_stripes, uint32_t min_spares, uint32_t* d_check,
+                                         uint32_t* d_suspects, uint32_t* d_use_masks, uint32_t* d_bad_stripes,
+                                         uint32_t* d_unrepaired, unsigned long long* d_corrected_bytes, void* stream) {
+    return hec::gpu_ragged_correct(rs, d_base, descs, n_stripes, min_spares, true, d_check, d_suspects, d_use_masks,
+                                   d_bad_stripes, nullptr, d_unrepaired, d_corrected_bytes,
+                                   static_cast<hipStream_t>(stream));
+}
 
 int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n_stripes,
                           void* stream) {

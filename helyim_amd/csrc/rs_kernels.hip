@@ -35,7 +35,8 @@
 //    compare against the spare present shards.
 //  * The ragged scrub (rs104_bs_ragged_verify_kernel, rs104_ragged_check_kernel
 //    and the masked locate's RAGGED walk) is that scrub over stripes of mixed
-//    lengths and masks: the ragged workgroup map in front of the same bodies.
+//    lengths and masks: the ragged workgroup map in front of the same bodies;
+//    with CORRECT too (rs104_ragged_correct_kernel) the walk fixes in place.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -1045,6 +1046,14 @@ struct FixLane {
     uint32_t changed;
 };
 
+// The ragged correct's (rs104_ragged_correct_kernel): the batch, and the stripe
+// whose RaggedItem a fix reads again (scalar loads: a fix is rare).
+struct RaggedFixLane {
+    const RaggedArgs* a;
+    uint32_t stripe, chunk;
+    uint32_t changed;
+};
+
 struct NoFix {};  // the locate kernel's
 
 // XOR the error vector e into this lane's vector of shard c (wave-uniform).
@@ -1054,19 +1063,31 @@ struct NoFix {};  // the locate kernel's
 // IN_PLACE (the masked correct): the batch is one in-place layout and c is a
 // shard index 0..13 of it, so every c is addressed from in_base (out_base
 // equals in_base there: the c - 10 path would put shard 12's fix into shard 2).
-template <bool ALIGNED, bool IN_PLACE = false>
-__device__ __forceinline__ void fix_shard(FixLane& f, int c, const u32x4 e) {
+// RAGGED (the ragged correct, always in place): shard c of the stripe is at
+// base + item.off + c * item.shard_stride, and the tail rule uses item.len.
+template <bool ALIGNED, bool IN_PLACE = false, bool RAGGED = false>
+__device__ __forceinline__ void fix_shard(std::conditional_t<RAGGED, RaggedFixLane, FixLane>& f, int c,
+                                          const u32x4 e) {
     if ((e[0] | e[1] | e[2] | e[3]) == 0) return;
-    const ApplyArgs& a = *f.a;
-    const uint64_t o = uint64_t(f.chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;  // < a.len: an error here
+    const auto& a = *f.a;
+    const uint64_t o = uint64_t(f.chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;  // < len: an error here
     uint8_t* p;
-    if constexpr (IN_PLACE)
-        p = const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard + o;
-    else
-        p = (c < 10 ? const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard
-                    : a.out_base + uint64_t(f.stripe) * a.out_stripe + uint64_t(c - 10) * a.out_shard) +
-            o;
-    const uint64_t avail = a.len - o;
+    uint64_t len;
+    if constexpr (RAGGED) {
+        static_assert(IN_PLACE, "a ragged batch is one in-place layout");
+        const __attribute__((address_space(4))) RaggedItem* it = as_const(a.items) + f.stripe;
+        p = a.base + it->off + uint64_t(c) * it->shard_stride + o;
+        len = it->len;
+    } else {
+        if constexpr (IN_PLACE)
+            p = const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard + o;
+        else
+            p = (c < 10 ? const_cast<uint8_t*>(a.in_base) + uint64_t(f.stripe) * a.in_stripe + uint64_t(c) * a.in_shard
+                        : a.out_base + uint64_t(f.stripe) * a.out_stripe + uint64_t(c - 10) * a.out_shard) +
+                o;
+        len = a.len;
+    }
+    const uint64_t avail = len - o;
     if (avail >= kVecBytes)
         store_full(p, load_full(p, ALIGNED) ^ e, ALIGNED);
     else
@@ -1541,10 +1562,15 @@ hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream) {
 // of its own, the backend allocates the registers of the strided form
 // differently (profiles/ragged_scrub/isa.md); written this way the strided
 // forms keep their instruction streams.
+//
+// RAGGED and CORRECT (rs104_ragged_correct_kernel, hec.h hec_gpu_correct_ragged):
+// the ragged walk with the fixes, over RaggedCorrectArgs. fix_shard's RAGGED
+// form reads the stripe's RaggedItem again where a fix happens and addresses
+// shard c from the stripe's own base, stride and length.
 template <bool ALIGNED, bool CORRECT = false, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
-    std::conditional_t<RAGGED, RaggedScrubArgs, std::conditional_t<CORRECT, CorrectPresentArgs, CheckArgs>> v) {
-    static_assert(!(RAGGED && CORRECT), "the ragged walk only classifies");
+    std::conditional_t<RAGGED, std::conditional_t<CORRECT, RaggedCorrectArgs, RaggedScrubArgs>,
+                       std::conditional_t<CORRECT, CorrectPresentArgs, CheckArgs>> v) {
     constexpr int K = 10, N = 14, R = 4;
     const auto& a = v.a;  // ApplyArgs, or the ragged batch
     cu32p flagged = as_const(v.check);
@@ -1627,10 +1653,11 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
 #pragma unroll
         for (int j = 0; j < R; ++j) any |= s[j][0] | s[j][1] | s[j][2] | s[j][3];
         if (__ballot(any != 0) == 0) continue;  // wave-uniform: this wave's 1 KiB is clean
-        [[maybe_unused]] std::conditional_t<CORRECT, FixLane, NoFix> fx;
+        using Fix = std::conditional_t<RAGGED, RaggedFixLane, FixLane>;
+        [[maybe_unused]] std::conditional_t<CORRECT, Fix, NoFix> fx;
         [[maybe_unused]] bool write = false;  // wave-uniform: the stripe has the spares the caller asked for
         if constexpr (CORRECT) {
-            fx = FixLane{&a, stripe, chunk, 0};
+            fx = Fix{&a, stripe, chunk, 0};
             write = r >= v.min_spares;
         }
 
@@ -1680,7 +1707,7 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
                     if (write && __ballot(hit != 0) != 0) {  // wave-uniform: somebody fixes shard B[c]
                         u32x4 val[1] = {u32x4{0, 0, 0, 0}};
                         gf_mac<1>(val, s[0], as_const(v.fix_tabs) + pid * (K * 5) + c * 5);  // s[0] / A_m[0][c]
-                        fix_shard<ALIGNED, true>(fx, __builtin_ctz(bm), val[0] & e[0]);
+                        fix_shard<ALIGNED, true, RAGGED>(fx, __builtin_ctz(bm), val[0] & e[0]);
                     }
                 }
                 bm &= bm - 1;
@@ -1707,7 +1734,7 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
                             if (i != j) others |= nz_bytes(s[i][w]);
                         e[w] = s[j][w] & ((nz_bytes(s[j][w]) & ~others) >> 7) * 0xFFu;
                     }
-                    fix_shard<ALIGNED, true>(fx, int(out_id[j]), e);
+                    fix_shard<ALIGNED, true, RAGGED>(fx, int(out_id[j]), e);
                 }
             }
             // the bytes this wave changed, at most 16 a lane: five ballots
@@ -1865,6 +1892,19 @@ hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStre
     return hipGetLastError();
 }
 
+// rs104_ragged_correct_kernel: the masked locate's RAGGED and CORRECT form, taking RaggedCorrectArgs.
+constexpr auto rs104_ragged_correct_kernel = rs104_locate_present_kernel<true, true, true>;
+
+hipError_t launch_ragged_correct(const RaggedCorrectArgs& v, bool bitslice, hipStream_t stream) {
+    RaggedCorrectArgs w = v;
+    w.half_shift = bitslice ? 1u : 0u;  // as launch_ragged_locate
+    const uint64_t items = uint64_t(w.a.n_blocks) << w.half_shift;
+    if (items == 0) return hipSuccess;
+    const uint64_t grid = std::min<uint64_t>(items, kLocateMaxBlocks);  // grid-stride covers the rest
+    hipLaunchKernelGGL(rs104_ragged_correct_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, w);
+    return hipGetLastError();
+}
+
 __global__ void add_word_kernel(uint32_t* word, uint32_t n) { atomicAdd(word, n); }
 
 hipError_t launch_add_word(uint32_t* word, uint32_t n, hipStream_t stream) {
@@ -1943,6 +1983,45 @@ hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* c
     const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
     hipLaunchKernelGGL(use_masks_corrected_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects,
                        use, unrepaired, min_spares, n_stripes);
+    return hipGetLastError();
+}
+
+// use_masks_corrected_kernel after rs104_ragged_correct_kernel: the present
+// masks come from the scrub's items, and a stripe left alone also gets mask
+// 0x3FFF in the decode's own items (a vector store into their device copy,
+// read by the scalar loads of the decode kernel that follows on the stream),
+// where rs104_chunk<DEC> returns at once: it keeps its holes.
+__global__ __launch_bounds__(kThreads) void ragged_use_masks_corrected_kernel(
+    const RaggedItem* scrub_items, RaggedItem* decode_items, const uint32_t* check, const uint32_t* suspects,
+    uint32_t* use, uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes) {
+    constexpr uint32_t kAll = (1u << 14) - 1;
+    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
+    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
+        bool left = false;
+        if (s < n_stripes) {
+            const uint32_t m = scrub_items[s].mask & kAll;
+            const bool consistent =
+                check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
+                                  (suspects[s] & kSuspectUnexplained) == 0);
+            use[s] = consistent ? m : kAll;
+            if (!consistent) decode_items[s].mask = kAll;
+            left = !consistent;
+        }
+        const unsigned long long b = __ballot(left);
+        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
+    }
+}
+
+hipError_t launch_ragged_use_masks_corrected(const RaggedItem* scrub_items, RaggedItem* decode_items,
+                                             const uint32_t* check, const uint32_t* suspects, uint32_t* use,
+                                             uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
+                                             hipStream_t stream) {
+    if (n_stripes == 0) return hipSuccess;
+    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
+    hipLaunchKernelGGL(ragged_use_masks_corrected_kernel, dim3(grid), dim3(kThreads), 0, stream, scrub_items,
+                       decode_items, check, suspects, use, unrepaired, min_spares, n_stripes);
     return hipGetLastError();
 }
 

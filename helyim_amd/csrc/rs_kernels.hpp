@@ -276,6 +276,28 @@ const char* ragged_scrub_kernel_name(bool bitslice);
 // check word is 0 costs two scalar loads. A bit-sliced map is walked as two
 // 4 KiB halves per entry.
 hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream);
+// Ragged correct (hec.h hec_gpu_correct_ragged): launch_ragged_locate's pass
+// with launch_correct_present's addition -- where a column of a stripe with
+// r >= min_spares is explained, the error value is XORed into the wrong byte
+// of shard c at a.base + item.off + c * item.shard_stride, in place, bytes at
+// or past the stripe's own length never written. The words are the locate's,
+// of the bytes as they were.
+struct RaggedCorrectArgs : RaggedScrubArgs {  // as for launch_ragged_locate, and:
+    const uint32_t* fix_tabs = nullptr;  // CorrectPresentArgs::fix_tabs
+    uint32_t* uncorrected = nullptr;     // optional: += stripes left inconsistent
+    unsigned long long* corrected_bytes = nullptr;  // optional: += bytes changed
+    uint32_t min_spares = 2;             // 2..4
+};
+hipError_t launch_ragged_correct(const RaggedCorrectArgs& v, bool bitslice, hipStream_t stream);
+// Use masks of a corrected ragged reconstruct (hec_gpu_reconstruct_corrected_ragged),
+// after launch_ragged_correct with the same min_spares: launch_use_masks_corrected's
+// rule with the present masks read from the scrub's items. A stripe left alone
+// also gets mask 0x3FFF in decode_items, the device copy of the items the
+// ragged decode launched next on the stream reads: its workgroups do nothing.
+hipError_t launch_ragged_use_masks_corrected(const RaggedItem* scrub_items, RaggedItem* decode_items,
+                                             const uint32_t* check, const uint32_t* suspects, uint32_t* use,
+                                             uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
+                                             hipStream_t stream);
 // *word += n, in stream order (the ragged scrub's count of unchecked stripes).
 hipError_t launch_add_word(uint32_t* word, uint32_t n, hipStream_t stream);
 

@@ -740,10 +740,12 @@ int hec_gpu_reconstruct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_st
  * Pass 1 runs bit-sliced when every stripe has all 14 shards and a length that
  * is a multiple of 8 KiB, otherwise as a table check that takes any length
  * (hec_ragged_scrub_kernel_name reports which).
- * Repair is the caller's, with the calls that exist: read d_suspects, clear
- * the named bits in the stripe's present_mask on the host (where bit 31 is
- * clear and at least 10 bits remain), and call hec_gpu_reconstruct_ragged;
- * hec_gpu_verify_ragged with the original masks is the proof.
+ * Repair on the device, with no host round trip: hec_gpu_correct_ragged and
+ * hec_gpu_reconstruct_corrected_ragged, below. The checked recipe (drop the
+ * named survivors) stays the caller's: read d_suspects, clear the named bits
+ * in the stripe's present_mask on the host (where bit 31 is clear and at least
+ * 10 bits remain), and call hec_gpu_reconstruct_ragged; hec_gpu_verify_ragged
+ * with the original masks is the proof.
  * Measured on one MI355X against the strided calls on the same bytes in the
  * same process, 4096 x 1 MiB stripes with a 64 KiB shard pad, medians of 9
  * alternating rounds, the map's upload included (tools/bench_ragged_scrub.py,
@@ -764,6 +766,59 @@ int hec_gpu_verify_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_s
 int hec_gpu_locate_corrupt_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
                                   uint32_t n_stripes, uint32_t* d_check, uint32_t* d_suspects,
                                   uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream);
+
+/* Ragged correct and corrected reconstruct (RS(10,4)): the masked correct calls
+ * over a ragged batch, in one call with no host round trip.
+ * hec_gpu_correct_ragged has exactly hec_gpu_correct_present_batch's contract,
+ * evaluated per stripe with m = descs[s].present_mask & 0x3FFF and that
+ * stripe's own shard_len: d_check, d_suspects, *d_bad_stripes and *d_unchecked
+ * are hec_gpu_locate_corrupt_ragged's, of the bytes as they were before the
+ * call; in a stripe with r >= min_spares (2, 3 or 4) every byte column that
+ * one present shard explains gets its error value XORed into the wrong byte,
+ * in place; a bit-31 column keeps its bytes; a stripe with r < min_spares is
+ * classified and never written; *d_uncorrected (optional, accumulated) gets
+ * plus one, once, per stripe left inconsistent; *d_corrected_bytes (optional,
+ * accumulated) counts the bytes changed. The guarantee table and the reason
+ * for min_spares are hec_gpu_correct_present_batch's, above. Nothing else is
+ * written: no absent shard, no byte at or past shard_len, no slack up to the
+ * stride, no gap between stripes, not word n_stripes of a result array. A
+ * stripe with p <= 10 is not read.
+ * hec_gpu_reconstruct_corrected_ragged is hec_gpu_reconstruct_corrected_batch's
+ * three steps in stream order: (1) the ragged correct (the uncorrected count
+ * is not reported); (2) d_use_masks[s] = m when d_check[s] == 0, or when r >=
+ * min_spares and bit 31 of d_suspects[s] is clear, otherwise 0x3FFF and
+ * *d_unrepaired (optional, accumulated) gets plus one; (3)
+ * hec_gpu_reconstruct_ragged with those masks: *d_bad_stripes is that
+ * reconstruct's count of stripes with fewer than ten shards, no survivor is
+ * dropped, and a stripe left alone keeps its holes.
+ * Errors, all before any device work: everything hec_gpu_locate_corrupt_ragged
+ * refuses; min_spares outside 2..4; a null d_use_masks:
+ * HEC_ERR_INVALID_ARGUMENT. With valid pointers n_stripes == 0 returns HEC_OK
+ * and writes nothing. Host waits are those of the other ragged calls. Pass 1
+ * is the ragged scrub's (hec_ragged_scrub_kernel_name reports it); pass 2 is
+ * rs104_ragged_correct_kernel; the reconstruct decodes from a workgroup map of
+ * its own kept in the same metadata slot.
+ * Measured on one MI355X, 4096 x 1 MiB stripes with a 64 KiB shard pad, one
+ * shard of every stripe erased, medians of 9 alternating rounds in one process,
+ * the maps' upload included (tools/bench_ragged_correct.py,
+ * profiles/ragged_correct/bench_ragged_correct.json): on a clean batch the
+ * correct 9.01 ms against hec_gpu_locate_corrupt_ragged's 8.96 (8.86..9.03 over
+ * the rounds), 1.005x, inside that spread; with 64 stripes holding a flipped
+ * byte 9.24 ms against the locate's 9.11 (8.98..9.15), 1.014x, outside, and
+ * against hec_gpu_correct_present_batch's 8.78 on the same bytes, 1.052x,
+ * outside; the corrected reconstruct 17.04 ms against
+ * hec_gpu_reconstruct_corrected_batch's 16.51 (16.39..16.55), 1.032x, outside.
+ * A config-5 batch (2048 clean stripes of 64 KiB..4 MiB, 0..3 shards lost)
+ * is corrected and rebuilt in 7.25 ms, 43.6 GB moved, 6.02 TB/s, 0.75 of 8
+ * TB/s. */
+int hec_gpu_correct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n_stripes,
+                           uint32_t min_spares, uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad_stripes,
+                           uint32_t* d_unchecked, uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes,
+                           void* stream);
+int hec_gpu_reconstruct_corrected_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
+                                         uint32_t n_stripes, uint32_t min_spares, uint32_t* d_check,
+                                         uint32_t* d_suspects, uint32_t* d_use_masks, uint32_t* d_bad_stripes,
+                                         uint32_t* d_unrepaired, unsigned long long* d_corrected_bytes, void* stream);
 
 /* Deterministic splitmix64 stripe data (bench / test inputs): stripe s gets
  * bytes_per_stripe bytes at d_base + s*stripe_stride, 64-bit word n (n >= 1)

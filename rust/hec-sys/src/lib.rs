@@ -231,6 +231,15 @@ extern "C" {
                                          n_stripes: u32, d_check: *mut u32, d_suspects: *mut u32,
                                          d_bad_stripes: *mut u32, d_unchecked: *mut u32,
                                          stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_correct_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
+                                  n_stripes: u32, min_spares: u32, d_check: *mut u32, d_suspects: *mut u32,
+                                  d_bad_stripes: *mut u32, d_unchecked: *mut u32, d_uncorrected: *mut u32,
+                                  d_corrected_bytes: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_reconstruct_corrected_ragged(rs: *const hec_rs_t, d_base: *mut u8,
+                                                descs: *const hec_stripe_desc, n_stripes: u32, min_spares: u32,
+                                                d_check: *mut u32, d_suspects: *mut u32, d_use_masks: *mut u32,
+                                                d_bad_stripes: *mut u32, d_unrepaired: *mut u32,
+                                                d_corrected_bytes: *mut u64, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_fill_splitmix(d_base: *mut u8, stripe_stride: u64, bytes_per_stripe: u64, n_stripes: u32,
                                  seed_base: u64, stream: *mut c_void) -> c_int;
 

@@ -1,0 +1,55 @@
+"""tests/test_gpu_ragged_correct.py again, against
+build/variants/libhec_smallgrid.so (kMaxLaunchBlocks = 100, kLocateMaxBlocks =
+4; tests/test_gpu_small_grid.py has the reasons): the file's clean batch and
+its batch of single wrong bytes have more than 100 map entries each, so pass 1
+goes in several launches, and with four workgroups the correct pass runs second
+and later rounds of its grid-stride loop over the map on every batch with more
+than four 4 KiB ranges; the decode of the corrected reconstruct goes through
+launch_ragged's launches from its own map.
+
+One child process (`python -m pytest tests/test_gpu_ragged_correct.py -m gpu`
+with HEC_LIB_PATH set); tests/small_grid_probe.py runs first in the child and
+ends it unless the limits are live. Nothing is deselected. The child has a time
+limit of its own, and is not started when an earlier small-grid child died of a
+signal or ran out of time."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+import test_gpu_small_grid as G
+from test_gpu_small_grid import ROOT, VARIANT, child_env, tail
+
+NAME = "test_gpu_ragged_correct.py"
+CHILD_TIMEOUT = 300  # seconds; the file takes well under a minute with the product library
+
+
+def test_the_batches_pass_one_launch_of_the_variant():
+    """The entry counts the docstring relies on, from the file's own shapes."""
+    import small_grid_probe as probe
+    import test_gpu_ragged_correct as T
+    clean = T.Ragged(T.clean_shapes())
+    flips = T.Ragged([(L, m) for L, m, _, _ in T.single_flip_cases("table")])
+    assert clean.entries() > probe.MAX_LAUNCH_BLOCKS and flips.entries() > 2 * probe.MAX_LAUNCH_BLOCKS
+    assert clean.entries() > probe.LOCATE_MAX_BLOCKS and flips.entries() > probe.LOCATE_MAX_BLOCKS
+
+
+@pytest.mark.gpu
+def test_ragged_correct_suite_against_small_grid(gpu):
+    assert not G._stopped, "not started: " + G._stopped[0]
+    assert os.path.exists(VARIANT), VARIANT + " is missing: `make all` builds it"
+    cmd = [sys.executable, "-m", "pytest", "-p", "small_grid_probe", os.path.join("tests", NAME), "-m", "gpu", "-q",
+           "--maxfail=5", "-p", "no:cacheprovider"]
+    try:
+        r = subprocess.run(cmd, env=child_env(), cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+    except subprocess.TimeoutExpired as e:
+        G._stopped.append(f"the child of {NAME} was killed after {CHILD_TIMEOUT} s")
+        out = e.stdout if isinstance(e.stdout, str) else (e.stdout or b"").decode(errors="replace")
+        pytest.fail(G._stopped[0] + "\n" + tail(out))
+    out = r.stdout + r.stderr
+    if r.returncode < 0:
+        G._stopped.append(f"the child of {NAME} died of signal {-r.returncode}")
+        pytest.fail(G._stopped[0] + "\n" + tail(out))
+    assert r.returncode == 0, f"{NAME} under the small-grid variant (return code {r.returncode}):\n{tail(out)}"
+    assert G.count("passed", r.stdout) > 0 and G.count("deselected", r.stdout) == 0, tail(out)

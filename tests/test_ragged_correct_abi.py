@@ -1,0 +1,112 @@
+"""The ragged correct entry points without a GPU: the symbols, and every
+argument and descriptor check that precedes device work (fake non-null
+pointers are never touched). The descriptor checks are those of
+tests/test_ragged_scrub_abi.py, repeated for both calls."""
+import os
+
+import pytest
+
+from conftest import ROOT
+from test_ragged_scrub_abi import EMPTY_SHARD, FULL, INVALID_ARGUMENT, P, descs_of, two
+
+NAMES = ("hec_gpu_correct_ragged", "hec_gpu_reconstruct_corrected_ragged")
+
+
+def correct(lib, rs, base=P, descs="two", n=None, res=P, sus=P, min_spares=2):
+    d = two() if isinstance(descs, str) else descs
+    return lib.hec_gpu_correct_ragged(rs, base, None if d is None else d.ctypes.data,
+                                      (0 if d is None else len(d)) if n is None else n, min_spares, res, sus, None,
+                                      None, None, None, None)
+
+
+def reconstruct(lib, rs, base=P, descs="two", n=None, res=P, sus=P, use=P, min_spares=2):
+    d = two() if isinstance(descs, str) else descs
+    return lib.hec_gpu_reconstruct_corrected_ragged(rs, base, None if d is None else d.ctypes.data,
+                                                    (0 if d is None else len(d)) if n is None else n, min_spares,
+                                                    res, sus, use, None, None, None, None)
+
+
+CALLS = {correct: ("base", "res", "sus"), reconstruct: ("base", "res", "sus", "use")}
+
+
+def test_symbols_signatures_and_python_names():
+    import helyim_amd as H
+    from helyim_amd import _lib
+    header = open(os.path.join(ROOT, "include", "hec.h")).read()
+    for name in NAMES:
+        assert hasattr(H.lib, name), name
+        assert name in _lib.SIGNATURES, name
+        assert name + "(" in header, name
+        assert len(_lib.SIGNATURES[name][1]) == 12, name
+    for name in ("correct_ragged", "reconstruct_corrected_ragged"):
+        assert callable(getattr(H, name)), name
+
+
+@pytest.mark.parametrize("call", list(CALLS), ids=lambda f: f.__name__)
+def test_arguments_checked_before_device(call):
+    import helyim_amd as H
+    lib, rs = H.lib, H.ReedSolomon(10, 4)
+    assert call(lib, rs.handle, n=0) == 0
+    assert call(lib, rs.handle, descs=None, n=0) == 0
+    assert call(lib, None) == INVALID_ARGUMENT
+    assert "null" in H._lib.last_detail()
+    for pointer in CALLS[call]:
+        assert call(lib, rs.handle, **{pointer: None}) == INVALID_ARGUMENT, pointer
+        assert "null" in H._lib.last_detail()
+        assert call(lib, rs.handle, n=0, **{pointer: None}) == INVALID_ARGUMENT, pointer
+    assert call(lib, rs.handle, descs=None, n=2) == INVALID_ARGUMENT
+    assert "null" in H._lib.last_detail()
+    # alignment and overlap, as hec_gpu_encode_ragged
+    assert call(lib, rs.handle, base=P + 8) == INVALID_ARGUMENT
+    assert call(lib, rs.handle, descs=two(offset=14 * 4096 + 8)) == INVALID_ARGUMENT
+    assert "stripe 1" in H._lib.last_detail()
+    assert call(lib, rs.handle, descs=two(shard_stride=1000)) == INVALID_ARGUMENT     # 1000 % 16 != 0
+    assert "stripe 1" in H._lib.last_detail()
+    assert call(lib, rs.handle, descs=two(shard_stride=992)) == INVALID_ARGUMENT      # stride < len
+    assert call(lib, rs.handle, descs=two(shard_len=0)) == EMPTY_SHARD
+    assert "stripe 1" in H._lib.last_detail()
+    # a stripe that will not be read (nine shards present) is still checked
+    assert call(lib, rs.handle, descs=two(shard_len=0, present_mask=0x1FF)) == EMPTY_SHARD
+    assert call(lib, rs.handle, n=0) == 0
+
+
+@pytest.mark.parametrize("call", list(CALLS), ids=lambda f: f.__name__)
+def test_min_spares_outside_2_to_4_is_refused(call):
+    import helyim_amd as H
+    lib, rs = H.lib, H.ReedSolomon(10, 4)
+    for bad in (0, 1, 5):
+        assert call(lib, rs.handle, min_spares=bad) == INVALID_ARGUMENT, bad
+        assert "min_spares" in H._lib.last_detail()
+        assert call(lib, rs.handle, n=0, min_spares=bad) == INVALID_ARGUMENT, bad
+    for good in (2, 3, 4):
+        assert call(lib, rs.handle, n=0, min_spares=good) == 0, good
+
+
+def test_null_suspects_and_use_masks_are_refused():
+    import helyim_amd as H
+    lib, rs = H.lib, H.ReedSolomon(10, 4)
+    assert correct(lib, rs.handle, sus=None) == INVALID_ARGUMENT
+    assert "null" in H._lib.last_detail()
+    assert reconstruct(lib, rs.handle, sus=None) == INVALID_ARGUMENT
+    assert "null" in H._lib.last_detail()
+    assert reconstruct(lib, rs.handle, use=None) == INVALID_ARGUMENT
+    assert "null" in H._lib.last_detail()
+
+
+@pytest.mark.parametrize("k,m", [(5, 5), (10, 2), (10, 6)])
+def test_other_codecs_are_refused_with_the_reason(k, m):
+    import helyim_amd as H
+    rs = H.ReedSolomon(k, m)
+    for call in CALLS:
+        assert call(H.lib, rs.handle) == INVALID_ARGUMENT
+        assert "RS(10,4) only" in H._lib.last_detail()
+
+
+def test_above_2_32_map_entries_is_refused():
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    big = (1 << 32) - 16  # 2^20 entries of 4 KiB each; 4097 such stripes pass 2^32
+    d = descs_of([(0, 1 << 32, big, FULL & ~1)] * 4097)
+    for call in CALLS:
+        assert call(H.lib, rs.handle, descs=d) == INVALID_ARGUMENT
+        assert "2^32" in H._lib.last_detail()

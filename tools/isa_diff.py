@@ -56,16 +56,33 @@ def main():
     names = demangle(sorted(set(pb) | set(hb)))
     print("| symbol | | instructions | VGPRs | SGPRs | scratch B | LDS B |")
     print("|---|---|---|---|---|---|---|")
+    # A kernel whose parameter type is spelled differently has another mangled
+    # name: a parent-only symbol is paired with the one head-only symbol of the
+    # same template-id (the demangled name up to its parameter list).
+    head_only = {}
+    for sym in set(hb) - set(pb):
+        head_only.setdefault(names[sym].split("(")[0], []).append(sym)
+    renamed = {}
+    for sym in set(pb) - set(hb):
+        twins = head_only.get(names[sym].split("(")[0], [])
+        if len(twins) == 1:
+            renamed[sym] = twins[0]
     for sym in sorted(names, key=names.get):
-        a, b = pb.get(sym), hb.get(sym)
+        if sym in renamed.values():
+            continue
+        other = renamed.get(sym, sym)
+        a, b = pb.get(sym), hb.get(other)
         if a is None or b is None:
             verdict = "ONLY PARENT" if b is None else "ONLY HEAD"
         else:
-            verdict = "SAME" if a == b else "DIFF"
+            strip = lambda body, name: [ln.replace(name, "@") for ln in body]  # noqa: E731
+            verdict = "SAME" if strip(a, sym) == strip(b, other) else "DIFF"
+            if other != sym:
+                verdict += " (parameter type respelled)"
         cells = [f"{instr(a) if a is not None else '-'} / {instr(b) if b is not None else '-'}"]
         for key in ("vgpr", "sgpr", "scratch", "lds"):
-            cells.append(f"{pr.get(sym, {}).get(key, '-')} / {hr.get(sym, {}).get(key, '-')}")
-        print(f"| `{names[sym]}` | {verdict} | " + " | ".join(cells) + " |")
+            cells.append(f"{pr.get(sym, {}).get(key, '-')} / {hr.get(other, {}).get(key, '-')}")
+        print(f"| `{names[other]}` | {verdict} | " + " | ".join(cells) + " |")
 
 
 if __name__ == "__main__":
