@@ -892,7 +892,9 @@ def test_files_longer_than_the_two_slots(gpu, tmp_path):
     for i in range(14):
         if i not in absent:
             bufs[i].tofile(base + ".ec%02d" % i)
-    for block in (65536, 0):
+    # 5 MiB blocks are larger than a chunk's 4 MiB: one block per chunk, and the
+    # last chunk is a short block alone, whose words are the slot's first
+    for block in (65536, 0, 5 << 20):
         width = block or 1 << 20  # HEC_SMALL_BLOCK_SIZE
         n_blocks = -(-size // width)
         # every block of the random volume is bad, so both slots and all 14 rows were filled
@@ -903,7 +905,7 @@ def test_files_longer_than_the_two_slots(gpu, tmp_path):
             want.append((lo, hi - lo) + block_words(bufs, mask, lo, hi))
         assert all(w[2] and w[3] for w in want)
         assert want[-1][:2] == (size // width * width, size % width)
-        if block:
+        if block == 65536:
             assert [w[3] for w in want] == [1 << 11, 1 << 2, 1 << 13, want[3][3], 1 << 0, 1 << 10, 1 << 4]
         assert H.locate_corrupt_ec_files_present(base, block) == (n_blocks, len(want), want, mask), hex(block)
     assert not any(os.path.exists(base + ".ec%02d" % i) for i in absent)

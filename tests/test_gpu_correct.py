@@ -18,8 +18,9 @@ import correct_model as CM
 import footprint as F
 import locate_model as M
 import locate_pairs_model as PM
-from test_gpu_locate_pairs import (ALL, LAYOUTS, LENGTHS, UNEXPLAINED, bits, gather, hex_list, in_place_layout,
-                                   read_words, result_words, unexplained_triple)
+from test_gpu_locate_pairs import (ALL, BIG_BLOCKS, BIG_SIZE, EDGE, LAYOUTS, LENGTHS, NEIGHBOURS, RUN, SINGLES, TRIPLE_AT,
+                                   UNEXPLAINED, big_entries, big_volume, bits, ec_names, gather, hex_list,
+                                   in_place_layout, read_words, result_words, unexplained_triple)
 from test_gpu_verify import clean_case, copies, flip_positions, oracle_words, shard_of
 
 pytestmark = pytest.mark.gpu
@@ -379,3 +380,74 @@ def test_files(gpu, tmp_path):
     for shard in (2, 13):
         expect[shard][run:run + 4096] = good[shard][run:run + 4096]
     assert [bytearray(open(n, "rb").read()) for n in names(base)] == expect
+
+
+def test_files_longer_than_the_two_slots(gpu, tmp_path):
+    """hec_correct_pairs_ec_files and hec_correct_ec_files over three chunks
+    (64 KiB and 1 MiB blocks: slot 0 is used twice, and a chunk's rows are
+    written back from its slot while later chunks are in flight) and with a
+    5 MiB block, larger than a chunk, whose last chunk is one short block. The
+    volume and its damage are test_gpu_locate_pairs.big_volume's. Pairs: the
+    entries are the pair locate's from before, every file equals its original
+    but for the triple's column, files no word names are not written, and a
+    second scrub reports the triple's block alone. Single: every column with
+    one wrong file is restored, those at the chunk edge inside the run
+    included, the run's pair columns and the triple keep their bytes; with
+    cap = 2 every fix is still written."""
+    import helyim_amd as H
+    good, bad, cols, triple = big_volume(2029)
+    base = str(tmp_path / "big")
+    files = ec_names(base)
+    named = {s for s, _ in SINGLES + NEIGHBOURS} | set(triple)
+    assert {2, 13} <= named
+    untouched = [i for i in range(14) if i not in named]
+    assert untouched
+    for i in untouched:
+        good[i].tofile(files[i])
+        os.utime(files[i], ns=(10**18, 10**18 + i))
+
+    def damage():
+        for i in sorted(named):
+            bad[i].tofile(files[i])
+
+    def on_disk():
+        return [np.fromfile(name, np.uint8) for name in files]
+
+    def same(got, expect):
+        return all(np.array_equal(g, e) for g, e in zip(got, expect))
+
+    after_pairs = [g.copy() for g in good]
+    for c in triple:
+        after_pairs[c][TRIPLE_AT] = bad[c][TRIPLE_AT]
+    after_single = [a.copy() for a in after_pairs]
+    pair_cols = np.array([o for o in range(*RUN) if o not in (EDGE - 1, EDGE)])
+    for c in (2, 13):
+        after_single[c][pair_cols] = bad[c][pair_cols]
+    for block in BIG_BLOCKS:
+        width = block or 1 << 20  # HEC_SMALL_BLOCK_SIZE
+        n_blocks = -(-BIG_SIZE // width)
+        # ---- pairs
+        damage()
+        want = big_entries(PM, bad, cols, width)
+        assert H.locate_corrupt_pairs_ec_files(base, block) == (n_blocks, len(want), want), hex(block)
+        assert H.correct_ec_files(base, block, pairs=True) == (n_blocks, len(want), want), hex(block)
+        assert same(on_disk(), after_pairs), hex(block)
+        left = big_entries(PM, after_pairs, cols, width)
+        assert len(left) == 1 and left[0][3] == UNEXPLAINED and left[0][0] == TRIPLE_AT // width * width
+        assert H.correct_ec_files(base, block, pairs=True) == (n_blocks, 1, left), hex(block)
+        assert H.locate_corrupt_pairs_ec_files(base, block) == (n_blocks, 1, left), hex(block)
+        assert same(on_disk(), after_pairs), hex(block)
+        # ---- single, and once the cap
+        damage()
+        single = big_entries(M, bad, cols, width)
+        assert all(w[3] & UNEXPLAINED for w in single if w[0] <= RUN[1] and RUN[0] < w[0] + w[1])
+        if block == 65536:
+            assert [(w[0], w[3]) for w in single] == [
+                (0, bits(11)), (EDGE - 65536, bits(2) | UNEXPLAINED), (EDGE, bits(13) | UNEXPLAINED),
+                (6 << 20, bits(6, 9)), ((8 << 20) - 65536, bits(0)), (8 << 20, bits(10)),
+                (TRIPLE_AT // 65536 * 65536, UNEXPLAINED), (BIG_SIZE // 65536 * 65536, bits(4))]
+            assert H.correct_ec_files(base, block, cap=2) == (n_blocks, len(single), single[:2])
+        else:
+            assert H.correct_ec_files(base, block) == (n_blocks, len(single), single), hex(block)
+        assert same(on_disk(), after_single), hex(block)
+    assert [os.stat(files[i]).st_mtime_ns for i in untouched] == [10**18 + i for i in untouched]

@@ -629,7 +629,9 @@ def test_files_longer_than_the_two_slots(gpu, tmp_path):
     for i in present:
         bufs[i].tofile(base + ".ec%02d" % i)
     good = read_files(base, present)
-    for block in (65536, 0):
+    # 5 MiB blocks are larger than a chunk's 4 MiB: one block per chunk, and the
+    # last chunk is a short block alone, whose words are the slot's first
+    for block in (65536, 0, 5 << 20):
         width = block or 1 << 20  # HEC_SMALL_BLOCK_SIZE
         n_blocks = -(-size // width)
         for shard, off in hits:

@@ -7,7 +7,9 @@ and the verify launches ahead of it go in several ranges.
 One child process (`python -m pytest tests/test_gpu_correct.py -m gpu`
 with HEC_LIB_PATH set); tests/small_grid_probe.py runs first in the child and
 ends it unless the limits are live. Nothing is deselected: the file's largest
-batch is 2053 stripes of 4 KiB. The child has a time limit of its own, and is
+device batch is 2053 stripes of 4 KiB, and its largest file scrub fourteen
+shard files of 8 MiB + 300007 bytes in blocks of up to 5 MiB (one stripe per
+block, about 120 MB in all). The child has a time limit of its own, and is
 not started when an earlier small-grid child died of a signal or ran out of
 time."""
 import os

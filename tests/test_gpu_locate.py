@@ -602,14 +602,20 @@ def test_files_longer_than_the_two_slots(gpu, tmp_path):
     for shard, off in hits:
         bufs[shard][off] ^= 0x33
     syn = M.syndromes(np.stack(bufs))
-    want = []
-    for lo in sorted({off // block * block for _, off in hits}):
-        hi = min(lo + block, size)
-        s = syn[:, lo:hi]
-        want.append((lo, hi - lo, sum(1 << j for j in range(4) if s[j].any()), M.syndrome_word(s)))
-    assert [w[3] for w in want] == [1 << 11, 1 << 2, 1 << 13, UNEXPLAINED, 1 << 10, 1 << 4]
-    assert want[-1][:2] == (size // block * block, size % block)
     base = str(tmp_path / "big")
     for i in range(14):
         bufs[i].tofile(base + ".ec%02d" % i)
-    assert H.locate_corrupt_ec_files(base, block) == (-(-size // block), len(want), want)
+    # 5 MiB blocks are larger than a chunk's 4 MiB: one block per chunk, and the
+    # last chunk is a short block alone, whose words are the slot's first
+    for block in (65536, 5 << 20):
+        want = []
+        for lo in sorted({off // block * block for _, off in hits}):
+            hi = min(lo + block, size)
+            s = syn[:, lo:hi]
+            want.append((lo, hi - lo, sum(1 << j for j in range(4) if s[j].any()), M.syndrome_word(s)))
+        if block == 65536:
+            assert [w[3] for w in want] == [1 << 11, 1 << 2, 1 << 13, UNEXPLAINED, 1 << 10, 1 << 4]
+        else:
+            assert [w[3] for w in want] == [1 << 11 | 1 << 2 | 1 << 13, UNEXPLAINED | 1 << 10 | 1 << 4]
+        assert want[-1][:2] == (size // block * block, size % block)
+        assert H.locate_corrupt_ec_files(base, block) == (-(-size // block), len(want), want), block

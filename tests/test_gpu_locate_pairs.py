@@ -452,3 +452,96 @@ def test_files(gpu, tmp_path):
         os.remove(base + ".ec%02d" % shard)
     assert H.rebuild_ec_files(base) == [3, 5, 11]
     assert H.locate_corrupt_pairs_ec_files(base, BLOCK) == (n_blocks, 0, [])
+
+
+# ---- shard files longer than the two slots -----------------------------------------
+BIG_SIZE = (8 << 20) + 300_007
+# 64 KiB: three chunks of 64 blocks, slot 0 used twice; 0: the 1 MiB default,
+# four blocks per chunk; 5 MiB: larger than a chunk's 4 MiB, so one block per
+# chunk, and the last chunk is a short block alone (3 MiB + 300007)
+BIG_BLOCKS = (65536, 0, 5 << 20)
+EDGE = 4 << 20  # the first chunk edge at 64 KiB and 1 MiB blocks
+RUN = (EDGE - 2048, EDGE + 2048)
+SINGLES = [(11, 5), (2, EDGE - 1), (13, EDGE), (0, (8 << 20) - 1), (10, 8 << 20), (4, BIG_SIZE - 1)]
+NEIGHBOURS = [(6, (6 << 20) + 99), (9, (6 << 20) + 100)]
+TRIPLE_AT = (8 << 20) + 200_009  # the last chunk at every block size; alone in its 64 KiB block
+
+
+def big_volume(seed):
+    """-> (good, bad, cols, triple): fourteen streams of BIG_SIZE bytes, ten of
+    seeded random bytes and the oracle's parity of them (one encode call:
+    parity is bytewise, no block geometry), and a damaged copy. Single flips
+    in six different files, data and parity, at the first and the last byte
+    and on both sides of 4 MiB and 8 MiB; two different files wrong in
+    neighbouring columns; files 2 and 13 wrong in the same columns over a run
+    of 4096 that straddles 4 MiB -- except that of the two columns at the edge
+    itself each is wrong in one of the two files only (file 2 at 4 MiB - 1,
+    file 13 at 4 MiB: the single flips there; a third wrong file in a column
+    of the run would leave it unexplained for good); and one column with
+    three wrong files the pair model calls unexplained. cols: every damaged
+    column, ascending."""
+    from oracle import corc
+    rng = np.random.default_rng(seed)
+    good = [rng.integers(0, 256, BIG_SIZE, dtype=np.uint8) for _ in range(10)] + \
+           [np.zeros(BIG_SIZE, np.uint8) for _ in range(4)]
+    corc.CReedSolomon(10, 4).encode(good)
+    bad = [g.copy() for g in good]
+    for shard, o in SINGLES + NEIGHBOURS:
+        bad[shard][o] ^= 0x33
+    lo, hi = RUN
+    for shard in (2, 13):
+        x = rng.integers(1, 256, hi - lo, dtype=np.uint8)
+        x[EDGE - 1 - lo] = x[EDGE - lo] = 0
+        bad[shard][lo:hi] ^= x
+    triple = unexplained_triple(rng)
+    for c, v in triple.items():
+        bad[c][TRIPLE_AT] ^= v
+    cols = np.array(sorted({o for _, o in SINGLES + NEIGHBOURS} | set(range(lo, hi)) | {TRIPLE_AT}))
+    assert all((bad[i] != good[i]).sum() == sum(1 for o in cols if bad[i][o] != good[i][o]) for i in range(14))
+    return good, bad, cols, triple
+
+
+def big_entries(model, files, cols, width):
+    """The entries of a scrub of `files` at blocks of `width` bytes, from the
+    model on the damaged columns of each block: a column the oracle encoded
+    and nobody touched has a zero syndrome."""
+    want = []
+    for lo in sorted({int(o) // width * width for o in cols}):
+        hi = min(lo + width, BIG_SIZE)
+        sel = cols[(cols >= lo) & (cols < hi)]
+        block = np.stack([f[sel] for f in files])[None]
+        mis, sus = M.mismatch_words(block)[0], model.suspect_words(block)[0]
+        if mis:
+            want.append((lo, hi - lo, mis, sus))
+    return want
+
+
+def ec_names(base):
+    return [base + ".ec%02d" % i for i in range(14)]
+
+
+def test_files_longer_than_the_two_slots(gpu, tmp_path):
+    """hec_locate_corrupt_pairs_ec_files over three chunks (64 KiB and 1 MiB
+    blocks: slot 0 is used twice, its words collected while later chunks are
+    in flight) and with a block larger than a chunk: the entries equal the
+    model's at every block size, and no file is written."""
+    import helyim_amd as H
+    good, bad, cols, triple = big_volume(2028)
+    base = str(tmp_path / "big")
+    for i, name in enumerate(ec_names(base)):
+        bad[i].tofile(name)
+        os.utime(name, ns=(10**18, 10**18 + i))
+    for block in BIG_BLOCKS:
+        width = block or 1 << 20  # HEC_SMALL_BLOCK_SIZE
+        want = big_entries(PM, bad, cols, width)
+        if block == 65536:
+            assert [(w[0], w[3]) for w in want] == [
+                (0, bits(11)), (EDGE - 65536, bits(2, 13)), (EDGE, bits(2, 13)), (6 << 20, bits(6, 9)),
+                ((8 << 20) - 65536, bits(0)), (8 << 20, bits(10)), (TRIPLE_AT // 65536 * 65536, UNEXPLAINED),
+                (BIG_SIZE // 65536 * 65536, bits(4))]
+            assert want[-1][1] == BIG_SIZE % 65536
+        if block == 5 << 20:
+            assert [w[:2] for w in want] == [(0, 5 << 20), (5 << 20, BIG_SIZE - (5 << 20))]
+        assert H.locate_corrupt_pairs_ec_files(base, block) == (-(-BIG_SIZE // width), len(want), want), hex(block)
+    assert [os.stat(name).st_mtime_ns for name in ec_names(base)] == [10**18 + i for i in range(14)]
+    assert all(np.array_equal(np.fromfile(name, np.uint8), bad[i]) for i, name in enumerate(ec_names(base)))

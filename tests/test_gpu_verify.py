@@ -10,6 +10,7 @@ past a shard's end are garbage: a verify that compares a byte at or past
 shard_len reports a false mismatch here. Every device call is also a footprint
 check: the arenas must come back byte for byte, the result word at index S
 untouched."""
+import contextlib
 import ctypes
 import functools
 import os
@@ -408,6 +409,283 @@ def test_host_batch_three_paths_agree(gpu, L):
         pinned.close()
 
 
+# ---- host batches past one chunk ---------------------------------------------------
+CHUNK_BYTES = 96 << 20  # kChunkBytes of host_pipeline.cpp: a constant with no knob
+# (k, m, L, shard pitch of the caller's image, stripes of a chunk, stripes): the
+# smallest batches of four chunks with a short last one
+CHUNKED = [(10, 4, 17, 64, 28086, 3 * 28086 + 13),
+           (10, 4, 65541, F.r16(65541) + 48, 109, 3 * 109 + 13),
+           (4, 32, 17, 32, 10922, 3 * 10922 + 7)]
+
+
+def oracle_parity(k, m, data):
+    """data [S, k, L] (any strides) -> the oracle's parity [m, S, L]. RS parity
+    is bytewise, so the batch is one stripe of S * L columns: one encode call."""
+    S, _, L = data.shape
+    bufs = [np.ascontiguousarray(data[:, i]).reshape(S * L) for i in range(k)] + \
+           [np.zeros(S * L, np.uint8) for _ in range(m)]
+    corc.CReedSolomon(k, m).encode(bufs)
+    return np.stack(bufs[k:]).reshape(m, S, L)
+
+
+def batch_words(k, m, data, stored):
+    """The expected words [S] (uint32) of data [S, k, L] with the stored parity
+    [S, m, L]: bit j = the oracle's parity shard j differs somewhere."""
+    par = oracle_parity(k, m, data)
+    words = np.zeros(data.shape[0], np.uint32)
+    for j in range(m):
+        words |= (par[j] != stored[:, j]).any(axis=1).astype(np.uint32) << np.uint32(j)
+    return words
+
+
+@functools.lru_cache(maxsize=1)
+def chunked_image(k, m, L, pitch, S, seed=0):
+    """[S, k + m, pitch] of seeded random bytes, the shard gaps too, with the
+    oracle's parity in place (never modified: tests damage copies). Only the
+    last one is kept: the largest is 312 MB."""
+    rng = np.random.default_rng([k, m, L, S, seed])
+    image = np.frombuffer(bytearray(rng.bytes(S * (k + m) * pitch)), np.uint8).reshape(S, k + m, pitch)
+    image[:, k:, :L] = oracle_parity(k, m, image[:, :k, :L]).transpose(1, 0, 2)
+    image.setflags(write=False)
+    return image
+
+
+def random_image(nbytes):
+    return np.frombuffer(np.random.default_rng(nbytes).bytes(nbytes), np.uint8)
+
+
+def chunk_damage(image, k, m, L, C, seed=None):
+    """A damaged copy of a clean image and its reference words. Dirty are the
+    stripes on both sides of every chunk edge, the first, the last and one in
+    the middle of each chunk (seeded: a random one); all others stay clean.
+    Of the twelve dirty stripes (in a seeded order) four get one flip in a
+    data shard, whose word is read from the reference, and the i-th of the
+    other eight gets the parity rows j = i mod 8 (and row i mod m): every
+    parity row is flipped in a stripe whose word is also asserted by
+    construction -- one row per stripe at m = 4, rows 7, 15, 23 and 31 in
+    one stripe at m = 32. The flips alternate between byte 0 and byte L - 1,
+    in data and in parity."""
+    S = image.shape[0]
+    rng = np.random.default_rng(seed)
+    last = S - 3 * C
+    mids = [C // 2, C + C // 3, 2 * C + C // 5, 3 * C + last // 2] if seed is None else \
+        [c * C + int(rng.integers(1, (C if c < 3 else last) - 1)) for c in range(4)]
+    stripes = [0, C - 1, C, 2 * C - 1, 2 * C, 3 * C - 1, 3 * C, S - 1] + mids
+    assert len(set(stripes)) == 12 and max(stripes) == S - 1
+    order = list(range(12)) if seed is None else [int(t) for t in rng.permutation(12)]
+    dirty = image.copy()
+    alone = {}
+    for s, t in zip(stripes, order):
+        if t % 3 == 2:
+            dirty[s, (7 * t) % k, L - 1 if t % 2 else 0] ^= 0x80 >> (t % 8)
+            continue
+        i = t - t // 3  # 0..7 over the stripes without a data flip
+        rows = {j for j in range(m) if j % 8 == i} | {i % m}
+        for j in rows:
+            dirty[s, k + j, 0 if (i + j // 8) % 2 == 0 else L - 1] ^= 0x01 << (j % 8)
+        alone[s] = sum(1 << j for j in rows)
+    want = batch_words(k, m, dirty[:, :k, :L], dirty[:, k:, :L])
+    assert sorted(np.flatnonzero(want).tolist()) == sorted(stripes)  # the reference calls every other stripe clean
+    assert all(int(want[s]) == w for s, w in alone.items())          # parity flips alone: exactly their bits
+    return dirty, want, stripes
+
+
+def host_verify(rs, data, par, L, S):
+    """hec_host_verify_batch on data / par = (address, stripe stride, shard
+    stride) -> (words [S] uint32, n_bad_stripes). Words are prefilled with
+    0xFFFFFFFF (a chunk that is never handed back shows), word S is a sentinel,
+    and n_bad_stripes is preset: it is set, not accumulated."""
+    import helyim_amd as H
+    words = np.full(S + 1, 0xFFFFFFFF, np.uint32)
+    words[S] = SENTINEL
+    n_bad = ctypes.c_uint32(1234)
+    rc = H.lib.hec_host_verify_batch(rs.handle, *data, *par, L, S, words.ctypes.data, ctypes.byref(n_bad))
+    assert rc == 0, (rc, H._lib.last_detail())
+    assert int(words[S]) == SENTINEL
+    return words[:S].copy(), int(n_bad.value)
+
+
+def in_place(ptr, k, n, pitch):
+    return (ptr, n * pitch, pitch), (ptr + k * pitch, n * pitch, pitch)
+
+
+def check_words(got, want, note):
+    words, n_bad = got
+    differ = np.flatnonzero(words != want)
+    assert differ.size == 0, (note, differ[:8].tolist(), [hex(w) for w in words[differ[:8]]],
+                              [hex(w) for w in want[differ[:8]]])
+    assert n_bad == int(np.count_nonzero(want)), (note, n_bad)
+
+
+def chunk_bytes_of_slot(n, L, C):
+    return C * n * (-(-L // 256) * 256)
+
+
+PAGEABLE = ("pageable", "copies")
+
+
+@contextlib.contextmanager
+def host_path(path):
+    """Pageable batches go through the two pinned slots ("pageable": zero copy
+    on, the default) or through the three device slots ("copies": zero copy
+    off, restored on the way out)."""
+    import helyim_amd as H
+    assert path in PAGEABLE
+    assert H.lib.hec_set_host_zero_copy(int(path == "pageable")) == 0
+    try:
+        yield path
+    finally:
+        assert H.lib.hec_set_host_zero_copy(1) == 0
+
+
+@pytest.mark.parametrize("k,m,L,pitch,C,S", CHUNKED)
+def test_host_verify_across_chunks(gpu, k, m, L, pitch, C, S):
+    """Four chunks, the last one short, through every host path: pinned memory
+    read in place, pageable memory through the two recycled pinned slots, and
+    through the three recycled device slots with zero copy off. Every path must
+    return exactly the reference words of a batch whose dirty stripes sit on
+    both sides of every chunk edge, and all-zero words for the clean batch; the
+    caller's bytes stay as they were. RS(4,32) uses all 32 bits of a word.
+
+    At RS(10,4), L = 17 each pageable path first sizes its slots with the dirty
+    batch, then verifies 340 random stripes of 65541 bytes -- every one
+    mismatches -- so that the recycled slots hold garbage in bytes 17..255 of
+    every 256-byte shard pitch when the clean batch follows: a launch that
+    compares a byte past shard_len reports a clean stripe as bad."""
+    import time
+    import torch
+    import helyim_amd as H
+    from helyim_amd import batch
+    n = k + m
+    assert C == max(1, CHUNK_BYTES // (n * -(-L // 256) * 256)) and 3 * C < S < 4 * C  # else kChunkBytes changed
+    rs = H.ReedSolomon(k, m)
+    image = chunked_image(k, m, L, pitch, S)
+    dirty, want, _ = chunk_damage(image, k, m, L, C)
+    zeros = np.zeros(S, np.uint32)
+    stale_pads = (k, m, L) == (10, 4, 17)
+    if stale_pads:
+        bS, bL, bpitch = CHUNKED[1][5], CHUNKED[1][2], CHUNKED[1][3]
+        big = random_image(bS * 14 * bpitch)
+        assert chunk_bytes_of_slot(14, bL, CHUNKED[1][4]) <= chunk_bytes_of_slot(n, L, C)  # no slot grows after `big`
+    pinned = H.HostBuffer(image.nbytes)
+    page = np.empty_like(image)
+    try:
+        for label, img, expect in (("dirty", dirty, want), ("clean", image, zeros)):
+            pinned.array[:] = img.reshape(-1)
+            assert batch.host_zero_copy(pinned.tensor((S, n, pitch)))
+            t0 = time.perf_counter()
+            got = host_verify(rs, *in_place(pinned.ptr, k, n, pitch), L, S)
+            print(f"host verify RS({k},{m}) L={L} S={S} {label} pinned: {time.perf_counter() - t0:.3f} s")
+            check_words(got, expect, (label, "pinned"))
+            assert np.array_equal(pinned.array, img.reshape(-1)), label
+        # with zero copy off a batch goes up in two 2-D copies per stripe: 1.7 s a
+        # call at 84271 stripes, so of the two L = 17 codecs RS(10,4) alone takes that path
+        for path in PAGEABLE if (m, L) != (32, 17) else PAGEABLE[:1]:
+            for label, img, expect in (("dirty", dirty, want), ("clean", image, zeros)):
+                page[...] = img
+                with host_path(path):
+                    if stale_pads and label == "clean":
+                        words, n_bad = host_verify(rs, *in_place(big.ctypes.data, 10, 14, bpitch), bL, bS)
+                        assert words.all() and n_bad == bS, path
+                    t0 = time.perf_counter()
+                    got = host_verify(rs, *in_place(page.ctypes.data, k, n, pitch), L, S)
+                print(f"host verify RS({k},{m}) L={L} S={S} {label} {path}: {time.perf_counter() - t0:.3f} s")
+                check_words(got, expect, (label, path))
+                assert np.array_equal(page, img), (label, path)
+        if L == 65541:  # the Python mirror on the same batch
+            t = torch.from_numpy(dirty)[:, :, :L]
+            assert np.array_equal(batch.host_verify_batch(rs, t), want)
+    finally:
+        H.lib.hec_set_host_zero_copy(1)
+        pinned.close()
+
+
+@pytest.mark.parametrize("path", PAGEABLE)
+def test_host_verify_across_chunks_shard_major(gpu, path):
+    """The four chunks of the RS(10,4), L = 17 batch with data and parity in
+    arrays of their own, shard-major: [10][S][64] and [4][S][64], so a stripe
+    is 64 bytes from the next and a shard S * 64."""
+    import time
+    import helyim_amd as H
+    k, m, L, pitch, C, S = CHUNKED[0]
+    rs = H.ReedSolomon(k, m)
+    dirty, want, _ = chunk_damage(chunked_image(k, m, L, pitch, S), k, m, L, C)
+    data = np.ascontiguousarray(dirty[:, :k].transpose(1, 0, 2))
+    par = np.ascontiguousarray(dirty[:, k:].transpose(1, 0, 2))
+    d0, p0 = data.copy(), par.copy()
+    with host_path(path):
+        t0 = time.perf_counter()
+        got = host_verify(rs, (data.ctypes.data, pitch, S * pitch), (par.ctypes.data, pitch, S * pitch), L, S)
+    print(f"host verify RS({k},{m}) L={L} S={S} dirty shard-major {path}: {time.perf_counter() - t0:.3f} s")
+    check_words(got, want, (path, "shard-major"))
+    assert np.array_equal(data, d0) and np.array_equal(par, p0), path
+
+
+@pytest.fixture(scope="module")
+def thread_batches():
+    """Four batches (dirty, its copy, reference words), each built by a thread
+    of its own: the clean RS(10,4), L = 17 image with its stripes in a seeded
+    order (which keeps every stripe's parity right) and a seeded dirty set."""
+    import threading
+    T = 4
+    k, m, L, pitch, C, S = CHUNKED[0]
+    image = chunked_image(k, m, L, pitch, S)
+    batches = [None] * T
+
+    def prepare(t):
+        own = image[np.random.default_rng(100 + t).permutation(S)]
+        dirty, want, _ = chunk_damage(own, k, m, L, C, seed=200 + t)
+        batches[t] = (dirty, dirty.copy(), want)
+
+    workers = [threading.Thread(target=prepare, args=(t,)) for t in range(T)]
+    for th in workers:
+        th.start()
+    for th in workers:
+        th.join()
+    assert all(batches), "a thread failed to build its batch"
+    assert len({tuple(np.flatnonzero(b[2]).tolist()) for b in batches}) == T  # T different dirty sets
+    return batches
+
+
+@pytest.mark.parametrize("path", PAGEABLE)
+def test_host_verify_four_threads(gpu, thread_batches, path):
+    """Four threads, each with its own four-chunk RS(10,4) batch of 17-byte
+    shards and its own dirty stripes, the chunk edges among them. Each calls
+    hec_host_verify_batch twice while the others do: a pipeline and its result
+    words are leased per call, so every result is the thread's own reference."""
+    import threading
+    import time
+    import helyim_amd as H
+    k, m, L, pitch, C, S = CHUNKED[0]
+    rs = H.ReedSolomon(k, m)
+    batches = thread_batches
+    T = len(batches)
+    gate = threading.Barrier(T)
+    results, errors = [None] * T, []
+
+    def run(t):
+        try:
+            gate.wait(timeout=60)
+            results[t] = [host_verify(rs, *in_place(batches[t][0].ctypes.data, k, 14, pitch), L, S) for _ in range(2)]
+        except BaseException as e:  # an assertion in a thread fails the test, not the thread alone
+            errors.append((t, repr(e)))
+            gate.abort()
+
+    threads = [threading.Thread(target=run, args=(t,)) for t in range(T)]
+    with host_path(path):
+        t0 = time.perf_counter()
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+    print(f"host verify four threads x two calls, {path}: {time.perf_counter() - t0:.3f} s")
+    assert not errors, (path, errors)
+    for t, (dirty, before, want) in enumerate(batches):
+        for call in range(2):
+            check_words(results[t][call], want, (path, "thread", t, "call", call))
+        assert np.array_equal(dirty, before), (path, t)
+
+
 # ---- shard files -----------------------------------------------------------------
 BLOCK = 4096
 
@@ -506,17 +784,22 @@ def test_files_longer_than_the_two_slots(gpu, tmp_path):
     bufs = [rng.integers(0, 256, size, dtype=np.uint8) for _ in range(10)] + [np.zeros(size, np.uint8) for _ in range(4)]
     corc.CReedSolomon(10, 4).encode(bufs)
     hits = [(11, 5), (2, (4 << 20) - 1), (13, (4 << 20)), (10, (8 << 20) + 12345), (12, size - 1)]
-    want = {}
     for shard, off in hits:
         bufs[shard][off] ^= 0x33
-    for shard, off in hits:
-        lo = off // block * block
-        want[lo] = (lo, min(block, size - lo), file_oracle_mask(bufs, lo, min(lo + block, size)))
     base = str(tmp_path / "big")
     for i in range(14):
         bufs[i].tofile(base + ".ec%02d" % i)
-    assert want[0][2] == 1 << 1 and want[size // block * block] == (size // block * block, size % block, 1 << 2)
-    assert H.verify_ec_files(base, block) == (-(-size // block), len(want), [want[k] for k in sorted(want)])
+    # 5 MiB blocks are larger than a chunk's 4 MiB: one block per chunk, and the
+    # last chunk is a short block alone, whose word is the slot's first
+    for block in (65536, 5 << 20):
+        want = {}
+        for shard, off in hits:
+            lo = off // block * block
+            want[lo] = (lo, min(block, size - lo), file_oracle_mask(bufs, lo, min(lo + block, size)))
+        assert want[0][2] & 1 << 1 and want[size // block * block][:2] == (size // block * block, size % block)
+        if block == 65536:
+            assert want[0][2] == 1 << 1 and want[size // block * block][2] == 1 << 2
+        assert H.verify_ec_files(base, block) == (-(-size // block), len(want), [want[k] for k in sorted(want)]), block
     # 1 MiB blocks: four blocks per chunk; the same bytes, coarser
     n_blocks, n_bad, bad = H.verify_ec_files(base)
     assert (n_blocks, n_bad) == (9, 4) and [b[0] >> 20 for b in bad] == [0, 3, 4, 8]
