@@ -53,8 +53,11 @@ SIGNATURES = {
     "hec_rs_reconstruct": (_I, [_P, _P, _P, _P, _S]),
     "hec_rs_reconstruct_data": (_I, [_P, _P, _P, _P, _S]),
     "hec_rs_reconstruct_batch": (_I, [_P, _P, _P, _P, _S, _I, ctypes.POINTER(_S)]),
+    "hec_rs_reconstruct_some": (_I, [_P, _P, _P, _P, _P, _S]),
+    "hec_rs_reconstruct_some_batch": (_I, [_P, _P, _P, _P, _P, _S, ctypes.POINTER(_S)]),
     "hec_gpu_encode_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P]),
     "hec_gpu_reconstruct_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P]),
+    "hec_gpu_reconstruct_some_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P]),
     "hec_gpu_verify_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P, _P, _P]),
     "hec_host_verify_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P, ctypes.POINTER(_U32)]),
     "hec_verify_ec_files": (_I, [ctypes.c_char_p, _U64, _P, _S, ctypes.POINTER(_S), ctypes.POINTER(_U64)]),
@@ -83,10 +86,12 @@ SIGNATURES = {
                                           ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
     "hec_host_encode_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32]),
     "hec_host_reconstruct_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P]),
+    "hec_host_reconstruct_some_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P]),
     "hec_host_encode_batch_multi": (_I, [_P, _P, _S, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32]),
     "hec_host_reconstruct_batch_multi": (_I, [_P, _P, _S, _P, _U64, _U64, _U64, _U32, _P, _P]),
     "hec_gpu_encode_ragged": (_I, [_P, _P, _P, _U32, _P]),
     "hec_gpu_reconstruct_ragged": (_I, [_P, _P, _P, _U32, _P, _P]),
+    "hec_gpu_reconstruct_some_ragged": (_I, [_P, _P, _P, _P, _U32, _P, _P]),
     "hec_gpu_verify_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P]),
     "hec_gpu_locate_corrupt_ragged": (_I, [_P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "hec_gpu_correct_ragged": (_I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
@@ -136,6 +141,8 @@ SIGNATURES = {
     "hec_host_numa_node": (_I, [_P, ctypes.POINTER(_I)]),
     "hec_encode_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
     "hec_decode_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
+    "hec_reconstruct_some_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
+    "hec_reconstruct_some_batch_kernel_name": (ctypes.c_char_p, [_P, _U64, _U64, _U64, _U32]),
     "hec_ragged_kernel_name": (ctypes.c_char_p, [_P, _U32, _I]),
     "hec_ragged_scrub_kernel_name": (ctypes.c_char_p, [_P, _U32]),
 }

@@ -84,6 +84,28 @@ def reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: tor
                                         _stream_ptr(stream)))
 
 
+def reconstruct_some_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
+                           want_masks: torch.Tensor, bad_stripes: torch.Tensor = None, stream=None) -> None:
+    """Rebuild, in place, only the erased shards named in want_masks (int32
+    [S], bit i = shard i is worth rebuilding); the other erased shards are
+    neither computed nor written, and a stripe that wants none of its erased
+    shards is not read (hec_gpu_reconstruct_some_batch, RS(10,4))."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    for name, t in (("present_masks", present_masks), ("want_masks", want_masks)):
+        if not (t.is_cuda and t.dtype in (torch.int32, torch.uint32) and t.numel() == S and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous 32-bit CUDA tensor with one word per stripe")
+        _check_device(t)
+    check(lib.hec_gpu_reconstruct_some_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1),
+                                             L, S, present_masks.data_ptr(), want_masks.data_ptr(),
+                                             _counter_arg(bad_stripes, "bad_stripes"), _stream_ptr(stream)))
+
+
+def reconstruct_some_kernel_name(L: int) -> str:
+    """Kernel an aligned reconstruct_some_batch of shard length L runs."""
+    return lib.hec_reconstruct_some_kernel_name(L).decode()
+
+
 def _words_arg(S: int, t: torch.Tensor, name: str) -> torch.Tensor:
     """A per-stripe result tensor (mismatch, suspects, present_masks): allocated when not given."""
     if t is None:
@@ -507,6 +529,25 @@ def host_reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks
     return int(bad.value)
 
 
+def host_reconstruct_some_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks, want_masks) -> int:
+    """host_reconstruct_batch of the erased shards named in want_masks only
+    (hec_host_reconstruct_some_batch, RS(10,4)): only those come back over
+    PCIe. Returns the number of skipped stripes (fewer than 10 shards present
+    and an erased shard wanted)."""
+    import ctypes
+    import numpy as np
+    _check_host(stripes, rs)
+    S, n, L = stripes.shape
+    m = np.ascontiguousarray(np.asarray(present_masks, dtype=np.uint32))
+    w = np.ascontiguousarray(np.asarray(want_masks, dtype=np.uint32))
+    if m.size != S or w.size != S:
+        raise ValueError(f"{m.size} present masks and {w.size} want masks for {S} stripes")
+    bad = ctypes.c_uint32(0)
+    check(lib.hec_host_reconstruct_some_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1),
+                                              L, S, m.ctypes.data, w.ctypes.data, ctypes.byref(bad)))
+    return int(bad.value)
+
+
 def host_verify_batch(rs: ReedSolomon, stripes: torch.Tensor):
     """Scrub host-memory stripes[S, total, L] on the GPU (hec_host_verify_batch):
     returns the uint32 ``[S]`` numpy array of mismatch words (verify_batch's
@@ -579,6 +620,21 @@ def reconstruct_ragged(rs: ReedSolomon, base: torch.Tensor, descs, bad_stripes: 
     bad = bad_stripes.data_ptr() if bad_stripes is not None else None
     check(lib.hec_gpu_reconstruct_ragged(rs.handle, base.data_ptr(), d.ctypes.data, len(d), bad,
                                          _stream_ptr(stream)))
+
+
+def reconstruct_some_ragged(rs: ReedSolomon, base: torch.Tensor, descs, want_masks,
+                            bad_stripes: torch.Tensor = None, stream=None) -> None:
+    """reconstruct_ragged of the erased shards named in want_masks only (one
+    host word per stripe, bit i = shard i is worth rebuilding); a stripe that
+    wants none of its erased shards launches nothing
+    (hec_gpu_reconstruct_some_ragged)."""
+    import numpy as np
+    d = _desc_array(descs, base, rs.total_shard_count())
+    w = np.ascontiguousarray(np.asarray(want_masks, dtype=np.uint32))
+    if w.size != len(d):
+        raise ValueError(f"{w.size} want masks for {len(d)} stripes")
+    check(lib.hec_gpu_reconstruct_some_ragged(rs.handle, base.data_ptr(), d.ctypes.data, w.ctypes.data, len(d),
+                                              _counter_arg(bad_stripes, "bad_stripes"), _stream_ptr(stream)))
 
 
 def verify_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: torch.Tensor = None,

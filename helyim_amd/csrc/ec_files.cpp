@@ -603,7 +603,7 @@ static int rebuild_ec_files_impl(const std::string& base, uint32_t* ids, size_t*
         Mat coefs;
         std::vector<uint32_t> in_ids, out_ids;
         bool noop = false;
-        if ((rc = decode_plan(rs.rs, present, false, coefs, in_ids, out_ids, &noop))) return rc;
+        if ((rc = decode_plan(rs.rs, present, nullptr, coefs, in_ids, out_ids, &noop))) return rc;
         HostPlans hp;
         hp.add(coefs, in_ids, out_ids);
         DevicePlanSet ps;

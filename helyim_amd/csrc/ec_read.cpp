@@ -227,15 +227,15 @@ int read_ranges(const std::string& base, const Shards& sh, uint64_t large, uint6
                                                                     std::to_string(__builtin_popcount(mask)) +
                                                                     " shards present");
                 lost.push_back({id, off, iv.size, dst});
-                jobs.push_back(CompactJob{iv.size, mask});
+                jobs.push_back(CompactJob{iv.size, mask, 1u << id});  // of the shards gone, only the interval's
             }
             dst += iv.size;
         }
     }
     if (lost.empty()) return HEC_OK;
     // The decode reads the first 10 present shards of each lost interval,
-    // pread straight into pinned staging; the rebuilt interval is copied to its
-    // place in out.
+    // pread straight into pinned staging; only the interval's own shard is
+    // rebuilt, and copied to its place in out.
     return compact_reconstruct_104(
         rs104(), jobs,
         [&](size_t j, int, int shard, uint8_t* dst) {
@@ -244,9 +244,7 @@ int read_ranges(const std::string& base, const Shards& sh, uint64_t large, uint6
             return got < 0 ? io("read " + shard_name(base, shard))
                            : fail(HEC_ERR_IO, "read " + shard_name(base, shard) + ": shard shrank during the read");
         },
-        [&](size_t j, int shard, const uint8_t* src) {
-            if (shard == lost[j].shard) std::memcpy(lost[j].dst, src, lost[j].size);
-        },
+        [&](size_t j, int, const uint8_t* src) { std::memcpy(lost[j].dst, src, lost[j].size); },
         /*io_bound_fill=*/true);
 }
 

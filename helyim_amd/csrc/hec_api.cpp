@@ -94,6 +94,28 @@ int hec_gpu_reconstruct_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t st
                      stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks, d_bad_stripes, s);
 }
 
+int hec_gpu_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                   uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                   const uint32_t* d_present_masks, const uint32_t* d_want_masks,
+                                   uint32_t* d_bad_stripes, void* stream) {
+    HEC_TRY(check_some_args(rs, d_shards, d_present_masks, d_want_masks, stripe_stride, shard_stride, shard_len,
+                            n_stripes));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HEC_TRY(ensure_dense_decode(rs, gd, s));
+    return run_some(gd->decode_dense, 10, d_shards, stripe_stride, shard_stride, shard_len, n_stripes, d_present_masks,
+                    d_want_masks, d_bad_stripes, s);
+}
+
+const char* hec_reconstruct_some_kernel_name(uint64_t shard_len) { return some_kernel_name(shard_len); }
+const char* hec_reconstruct_some_batch_kernel_name(const uint8_t* d_shards, uint64_t stripe_stride,
+                                                   uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes) {
+    const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(d_shards)) | stripe_stride | shard_stride;
+    return some_batch_kernel_name(shard_len, n_stripes, align % 16 == 0);
+}
+
 int hec_gpu_verify_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,
                          uint64_t data_shard_stride, const uint8_t* d_parity, uint64_t parity_stripe_stride,
                          uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes, uint32_t* d_mismatch,

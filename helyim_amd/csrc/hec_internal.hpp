@@ -209,9 +209,10 @@ struct DevicePlanSet {
 };
 
 // Decode plan of one erasure pattern (upstream reconstruct semantics).
-// present: n flags. data_only: skip missing parity. Returns HEC_OK or
-// TOO_FEW_SHARDS_PRESENT; *noop = true when every shard is present.
-int decode_plan(const hec_rs* rs, const uint8_t* present, bool data_only, Mat& coefs,
+// present: n flags. required: n flags, the missing shards worth a row
+// (nullptr = all of them; reconstruct_data passes the data shards). Returns
+// HEC_OK or TOO_FEW_SHARDS_PRESENT; *noop = true when no row is left.
+int decode_plan(const hec_rs* rs, const uint8_t* present, const uint8_t* required, Mat& coefs,
                 std::vector<uint32_t>& in_ids, std::vector<uint32_t>& out_ids, bool* noop);
 
 // Per-device state shared by all contexts of one geometry.
@@ -392,11 +393,16 @@ std::atomic<uint64_t>& host_staging_max();
 // length len and present mask; the decode reads its first 10 present shards,
 // which fill(j, slot, shard, dst) writes (len bytes) straight into staging
 // (non-zero return = that status aborts the call); take(j, shard, src) then
-// receives every erased shard. fill / take run on up to 16 threads
-// (io_bound_fill: fill does preads, worth threads at smaller sizes).
+// receives every erased shard named in want (bits of present shards mean
+// nothing; a job that wants none of its erased shards takes part in nothing).
+// Only those are laid out, computed and stored: when some job wants fewer than
+// it lost, the launch is the ragged reconstruct-some kernel, else today's
+// decode. fill / take run on up to 16 threads (io_bound_fill: fill does
+// preads, worth threads at smaller sizes).
 struct CompactJob {
     uint64_t len;
     uint32_t mask;
+    uint32_t want = 0xFFFFFFFFu;
 };
 using CompactFill = std::function<int(size_t job, int slot, int shard, uint8_t* dst)>;
 using CompactTake = std::function<void(size_t job, int shard, const uint8_t* src)>;
@@ -441,6 +447,24 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
               uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
               uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
               hipStream_t s, Completion* done = nullptr, bool over_pcie = false);
+
+// Reconstruct some over a strided in-place RS(10,4) batch (hec.h
+// hec_gpu_reconstruct_some_batch is the contract), asynchronously on s. ps:
+// the dense decode set (ensure_dense_decode first). wants == nullptr means
+// "all": run_apply's decode of any codec (nin inputs), launch for launch.
+int run_some(const DevicePlanSet& ps, uint32_t nin, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+             uint64_t len, uint32_t n_stripes, const uint32_t* masks, const uint32_t* wants, uint32_t* bad,
+             hipStream_t s);
+// Prologue of the reconstruct-some batch entry points: nulls, the empty shard,
+// the codec, the layout. All before device work.
+inline int check_some_args(const hec_rs* rs, const void* shards, const void* masks, const void* wants,
+                           uint64_t stripe_stride, uint64_t shard_stride, uint64_t len, uint32_t n_stripes) {
+    if (!rs || !shards || !masks || !wants) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    if (rs->k != 10 || rs->m != 4)
+        return fail(HEC_ERR_INVALID_ARGUMENT, "batched reconstruct some is RS(10,4) only");
+    return check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, len, n_stripes);
+}
 
 // Verify the stored parity of a strided batch against ps's encode plan (plan
 // 0), asynchronously on s: mismatch[0, n_stripes) (device words) are cleared

@@ -149,8 +149,9 @@ static int encode_host(const hec_rs* rs, const uint8_t* const* data, uint8_t* co
     return HEC_OK;
 }
 
+// required: n flags, the missing shards to rebuild (nullptr = all of them).
 static int reconstruct_host(const hec_rs* rs, uint8_t* const* shards, const size_t* lens,
-                            const uint8_t* present, size_t n_shards, bool data_only) {
+                            const uint8_t* present, size_t n_shards, const uint8_t* required) {
     if (!shards || !lens || !present) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     if (n_shards < size_t(rs->n)) return fail(HEC_ERR_TOO_FEW_SHARDS, "");
     if (n_shards > size_t(rs->n)) return fail(HEC_ERR_TOO_MANY_SHARDS, "");
@@ -167,11 +168,12 @@ static int reconstruct_host(const hec_rs* rs, uint8_t* const* shards, const size
     if (npresent < rs->k) return fail(HEC_ERR_TOO_FEW_SHARDS_PRESENT, "");
     if (rs->k == 10 && rs->m == 4 && uint64_t(rs->k) * L <= host_staging_max())
         // one-stripe degraded read: pinned compact staging + the dense-LUT kernel
-        return hec_rs_reconstruct_batch(rs, shards, lens, present, 1, data_only ? 1 : 0, nullptr);
+        return required ? hec_rs_reconstruct_some_batch(rs, shards, lens, present, required, 1, nullptr)
+                        : hec_rs_reconstruct_batch(rs, shards, lens, present, 1, 0, nullptr);
     Mat coefs;
     std::vector<uint32_t> in_ids, out_ids;
     bool noop = false;
-    int rc = decode_plan(rs, present, data_only, coefs, in_ids, out_ids, &noop);
+    int rc = decode_plan(rs, present, required, coefs, in_ids, out_ids, &noop);
     if (rc) return rc;
     for (uint32_t id : out_ids)
         if (!shards[id]) return fail(HEC_ERR_INVALID_ARGUMENT, "missing shard without a buffer");
@@ -253,13 +255,22 @@ int hec_rs_verify(const hec_rs_t* rs, const uint8_t* const* shards, const size_t
 int hec_rs_reconstruct(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
                        const uint8_t* present, size_t n_shards) {
     if (!rs) return fail(HEC_ERR_INVALID_ARGUMENT, "null codec");
-    return reconstruct_host(rs, shards, shard_lens, present, n_shards, false);
+    return reconstruct_host(rs, shards, shard_lens, present, n_shards, nullptr);
 }
 
 int hec_rs_reconstruct_data(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
                             const uint8_t* present, size_t n_shards) {
     if (!rs) return fail(HEC_ERR_INVALID_ARGUMENT, "null codec");
-    return reconstruct_host(rs, shards, shard_lens, present, n_shards, true);
+    std::vector<uint8_t> data_flags(size_t(rs->n), 0);  // reconstruct some of the data shards
+    std::fill(data_flags.begin(), data_flags.begin() + rs->k, uint8_t(1));
+    return reconstruct_host(rs, shards, shard_lens, present, n_shards, data_flags.data());
+}
+
+int hec_rs_reconstruct_some(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
+                            const uint8_t* present, const uint8_t* required, size_t n_shards) {
+    if (!rs) return fail(HEC_ERR_INVALID_ARGUMENT, "null codec");
+    if (!required) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    return reconstruct_host(rs, shards, shard_lens, present, n_shards, required);
 }
 
 }  // extern "C"

@@ -29,6 +29,8 @@ struct Pipeline {
     DeviceBuf<> slot[kDepth];               // exact bytes, all reallocated together
     DeviceBuf<uint32_t> mask_dev[kDepth];
     PinnedBuf<uint32_t> mask_host[kDepth];  // pinned staging for per-chunk masks
+    DeviceBuf<uint32_t> want_dev[kDepth];   // reconstruct some: per-chunk want words, reserved by
+    PinnedBuf<uint32_t> want_host[kDepth];  // reserve_wants on that call's first use
     // pinned staging for pageable callers: two slots the kernels code in place
     PinnedBuf<> hslot[2];
     hipEvent_t hdone[2] = {};
@@ -41,6 +43,10 @@ struct Pipeline {
         HEC_TRY(reserve_all(mask_dev, n_masks * 4));
         return reserve_all(mask_host, n_masks * 4);
     }
+    int reserve_wants(size_t n_masks) {
+        HEC_TRY(reserve_all(want_dev, n_masks * 4));
+        return reserve_all(want_host, n_masks * 4);
+    }
     int reserve_host(size_t bytes) {
         if (!hdone[0])
             for (auto& e : hdone) HEC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -50,11 +56,12 @@ struct Pipeline {
     uint64_t pinned_bytes() const {
         uint64_t b = hslot[0].cap + hslot[1].cap;
         for (auto& m : mask_host) b += m.cap;
+        for (auto& m : want_host) b += m.cap;
         return b;
     }
     uint64_t device_bytes() const {
         uint64_t b = 0;
-        for (int i = 0; i < kDepth; ++i) b += slot[i].cap + mask_dev[i].cap;
+        for (int i = 0; i < kDepth; ++i) b += slot[i].cap + mask_dev[i].cap + want_dev[i].cap;
         return b;
     }
     // Host batches code caller memory in place (zero copy) or copy into it: an
@@ -135,12 +142,16 @@ uint32_t chunk_stripes(uint64_t shard_len, int n, uint32_t n_stripes) {
 }
 
 // A chunk's present masks, normalised (& full) into dst; returns how many of
-// its stripes have fewer than k shards present.
-uint32_t load_masks(uint32_t* dst, const uint32_t* src, uint32_t c, uint32_t full, int k) {
+// its stripes have fewer than k shards present. wsrc (a reconstruct some):
+// wdst gets the erased shards each stripe wants, and a stripe that wants none
+// is not counted.
+uint32_t load_masks(uint32_t* dst, const uint32_t* src, uint32_t c, uint32_t full, int k, uint32_t* wdst = nullptr,
+                    const uint32_t* wsrc = nullptr) {
     uint32_t bad = 0;
     for (uint32_t s = 0; s < c; ++s) {
         dst[s] = src[s] & full;
-        bad += __builtin_popcount(dst[s]) < k ? 1u : 0u;
+        if (wsrc) wdst[s] = wsrc[s] & ~dst[s] & full;
+        bad += __builtin_popcount(dst[s]) < k && (!wsrc || wdst[s]) ? 1u : 0u;
     }
     return bad;
 }
@@ -271,6 +282,14 @@ int run_device_ranges(const int* devices, size_t n_devices, uint32_t n_stripes,
     return HEC_OK;
 }
 
+// hec_host_reconstruct_batch (h_want_masks == nullptr: every erased shard,
+// today's launches) and hec_host_reconstruct_some_batch: one body. With want
+// words a stripe takes part only where it wants an erased shard, and only the
+// wanted shards are computed, stored and brought back.
+int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
+                     uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
+                     const uint32_t* h_want_masks, uint32_t* n_bad_stripes);
+
 }  // namespace
 }  // namespace hec
 
@@ -370,6 +389,31 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
     HEC_TRY(check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes));
+    return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks, nullptr,
+                            n_bad_stripes);
+}
+
+int hec_host_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride,
+                                    uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                    const uint32_t* h_present_masks, const uint32_t* h_want_masks,
+                                    uint32_t* n_bad_stripes) {
+    HEC_TRY(check_some_args(rs, h_shards, h_present_masks, h_want_masks, stripe_stride, shard_stride, shard_len,
+                            n_stripes));
+    if (n_bad_stripes) *n_bad_stripes = 0;
+    if (n_stripes == 0) return HEC_OK;
+    return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks,
+                            h_want_masks, n_bad_stripes);
+}
+
+}  // extern "C"
+
+namespace hec {
+namespace {
+
+int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
+                     uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
+                     const uint32_t* h_want_masks, uint32_t* n_bad_stripes) {
+    const uint32_t* const wants = h_want_masks;
     GeomDevice* gd;
     HEC_TRY(geom_device(rs, &gd));
     Lease<Pipeline> p;
@@ -377,17 +421,23 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
     const int k = rs->k, n = rs->n;
     const uint32_t full = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1);
     uint32_t bad = 0;
+    // the erased shards stripe s of slot q's chunk rebuilds (0: it takes no part)
+    auto wanted = [&](int q, uint32_t s) { return wants ? p->want_host[q][s] : ~p->mask_host[q][s] & full; };
     uint8_t* zs;
     if (host_device_view(h_shards, batch_span(stripe_stride, shard_stride, n, shard_len, n_stripes), &zs)) {
         // masks to the device (the caller's array may be pageable), then one
         // decode over the pinned host shards in place
         HEC_TRY(p->reserve(0, n_stripes));
+        if (wants) HEC_TRY(p->reserve_wants(n_stripes));
         HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
-        bad = load_masks(p->mask_host[0], h_present_masks, n_stripes, full, k);
+        bad = load_masks(p->mask_host[0], h_present_masks, n_stripes, full, k, p->want_host[0], wants);
         HEC_HIP(hipMemcpyAsync(p->mask_dev[0], p->mask_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
                                p->streams[0]));
-        HEC_TRY(run_apply(gd->decode_dense, uint32_t(k), zs, stripe_stride, shard_stride, zs, stripe_stride,
-                          shard_stride, shard_len, n_stripes, p->mask_dev[0], nullptr, p->streams[0]));
+        if (wants)
+            HEC_HIP(hipMemcpyAsync(p->want_dev[0], p->want_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
+                                   p->streams[0]));
+        HEC_TRY(run_some(gd->decode_dense, uint32_t(k), zs, stripe_stride, shard_stride, shard_len, n_stripes, p->mask_dev[0],
+                         wants ? p->want_dev[0].p : nullptr, nullptr, p->streams[0]));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
         if (n_bad_stripes) *n_bad_stripes = bad;
         return HEC_OK;
@@ -405,41 +455,46 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
         // into two pinned slots on the host pool, decoded in place there by the
         // zero-copy kernel, and only the erased shards are copied back.
         HEC_TRY(p->reserve(0, C));
+        if (wants) HEC_TRY(p->reserve_wants(C));
         HEC_TRY(p->reserve_host(size_t(C) * dstripe));
         HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
         uint8_t* hz[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
         uint32_t* zm[2] = {reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[0])),
                            reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[1]))};
-        if (hz[0] && hz[1] && zm[0] && zm[1])
+        uint32_t* zw[2] = {nullptr, nullptr};
+        if (wants)
+            for (int q = 0; q < 2; ++q) zw[q] = reinterpret_cast<uint32_t*>(pinned_device_ptr(p->want_host[q]));
+        if (hz[0] && hz[1] && zm[0] && zm[1] && (!wants || (zw[0] && zw[1])))
             return finish(two_slot_loop(
                 p.sc, n_stripes, C,
                 [&](uint32_t s0, uint32_t c, int q) {
-                    bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k);
+                    bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k, p->want_host[q],
+                                      wants ? wants + s0 : nullptr);
                     parallel_for(size_t(c) * n, uint64_t(c) * k * shard_len, [&](size_t t) {
                         const uint32_t s = uint32_t(t / n);
                         const int i = int(t % n);
                         const uint32_t mask = p->mask_host[q][s];
-                        if (__builtin_popcount(mask) < k || __builtin_popcount(mask) == n || !((mask >> i) & 1))
-                            return;
+                        if (__builtin_popcount(mask) < k || !wanted(q, s) || !((mask >> i) & 1)) return;
                         if (__builtin_popcount(mask & ((1u << i) - 1)) >= k) return;  // only the first k present
                         std::memcpy(p->hslot[q] + s * dstripe + uint64_t(i) * Lp, host_shard(s0 + s, i), shard_len);
                     });
                 },
                 [&](uint32_t c, int q) {
-                    return run_apply(gd->decode_dense, uint32_t(k), hz[q], dstripe, Lp, hz[q], dstripe, Lp, L16, c,
-                                     zm[q], nullptr, p->streams[0]);
+                    return run_some(gd->decode_dense, uint32_t(k), hz[q], dstripe, Lp, L16, c, zm[q], zw[q], nullptr,
+                                    p->streams[0]);
                 },
                 [&](uint32_t s0, uint32_t c, int q) {
                     parallel_for(size_t(c) * n, uint64_t(c) * 4 * shard_len, [&](size_t t) {
                         const uint32_t s = uint32_t(t / n);
                         const int i = int(t % n);
                         const uint32_t mask = p->mask_host[q][s];
-                        if (__builtin_popcount(mask) < k || ((mask >> i) & 1)) return;
+                        if (__builtin_popcount(mask) < k || !((wanted(q, s) >> i) & 1)) return;
                         std::memcpy(host_shard(s0 + s, i), p->hslot[q] + s * dstripe + uint64_t(i) * Lp, shard_len);
                     });
                 }));
     }
     HEC_TRY(p->reserve(size_t(C) * n * Lp, C));
+    if (wants) HEC_TRY(p->reserve_wants(C));
     HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
     auto dev_shard = [&](int q, uint32_t s, int i) { return p->slot[q] + s * dstripe + uint64_t(i) * Lp; };
     return finish(copy_loop(
@@ -447,11 +502,11 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
         [&](uint32_t s0, uint32_t c, int q) -> int {
             // the staging of this slot was last read by the copy issued kDepth chunks ago
             HEC_HIP(hipStreamSynchronize(p->streams[q]));
-            bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k);
+            bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k, p->want_host[q],
+                              wants ? wants + s0 : nullptr);
             for (uint32_t s = 0; s < c; ++s) {
                 const uint32_t mask = p->mask_host[q][s];
-                const int present = __builtin_popcount(mask);
-                if (present < k || present == n) continue;
+                if (__builtin_popcount(mask) < k || !wanted(q, s)) continue;
                 // H2D only the first k present shards (the ones the decode reads),
                 // merged into runs of adjacent shard ids
                 HEC_TRY(for_bit_runs(mask, n, k, [&](int i, int count) -> int {
@@ -461,19 +516,20 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
                 }));
             }
             HEC_HIP(hipMemcpyAsync(p->mask_dev[q], p->mask_host[q], c * 4, hipMemcpyHostToDevice, p->streams[q]));
+            if (wants)
+                HEC_HIP(hipMemcpyAsync(p->want_dev[q], p->want_host[q], c * 4, hipMemcpyHostToDevice, p->streams[q]));
             return HEC_OK;
         },
         [&](uint32_t c, int q, uint32_t) {
-            uint8_t* d = p->slot[q];
-            return run_apply(gd->decode_dense, uint32_t(k), d, dstripe, Lp, d, dstripe, Lp, L16, c, p->mask_dev[q],
-                             nullptr, p->streams[q]);
+            return run_some(gd->decode_dense, uint32_t(k), p->slot[q], dstripe, Lp, L16, c, p->mask_dev[q],
+                            wants ? p->want_dev[q].p : nullptr, nullptr, p->streams[q]);
         },
         [&](uint32_t s0, uint32_t c, int q) -> int {
             for (uint32_t s = 0; s < c; ++s) {
                 const uint32_t mask = p->mask_host[q][s];
                 if (__builtin_popcount(mask) < k) continue;
-                // D2H the erased shards, merged into runs
-                HEC_TRY(for_bit_runs(~mask & full, n, n, [&](int i, int count) -> int {
+                // D2H the erased shards that were rebuilt, merged into runs
+                HEC_TRY(for_bit_runs(wanted(q, s), n, n, [&](int i, int count) -> int {
                     HEC_HIP(copy2d(host_shard(s0 + s, i), shard_stride, dev_shard(q, s, i), Lp, shard_len,
                                    uint64_t(count), hipMemcpyDeviceToHost, p->streams[q]));
                     return HEC_OK;
@@ -482,6 +538,11 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
             return HEC_OK;
         }));
 }
+
+}  // namespace
+}  // namespace hec
+
+extern "C" {
 
 int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t data_stripe_stride,
                           uint64_t data_shard_stride, const uint8_t* h_parity, uint64_t parity_stripe_stride,

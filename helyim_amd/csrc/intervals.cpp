@@ -69,21 +69,27 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     const int k = rs->k, n = rs->n;
     struct Lay {
         uint64_t Lp, off, out_off;
+        uint32_t w;  // the erased shards the job wants; 0: the job is left out of everything below
     };
     std::vector<Lay> lay(jobs.size());
     uint64_t total = 0;
+    bool some = false, any = false;  // some: a job wants fewer shards than it lost
     for (size_t j = 0; j < jobs.size(); ++j) {
         if (__builtin_popcount(jobs[j].mask) < k || jobs[j].len == 0 || jobs[j].len > 0xFFFFFFFFull)
             return fail(HEC_ERR_INVALID_ARGUMENT, "compact job without k survivors");
+        const uint32_t erased = ~jobs[j].mask & ((1u << n) - 1);
+        lay[j].w = jobs[j].want & erased;
+        some |= lay[j].w != erased;
+        any |= lay[j].w != 0;
         lay[j].Lp = round_up(jobs[j].len, 16);
         lay[j].off = total;
-        total += round_up(uint64_t(k) * lay[j].Lp, 256);  // compact inputs: the first k present shards
+        if (lay[j].w) total += round_up(uint64_t(k) * lay[j].Lp, 256);  // compact inputs: the first k present shards
     }
-    if (jobs.empty()) return HEC_OK;
+    if (!any) return HEC_OK;
     const uint64_t in_total = total;
-    for (size_t j = 0; j < jobs.size(); ++j) {  // compact outputs: the erased shards, ascending
+    for (size_t j = 0; j < jobs.size(); ++j) {  // compact outputs: the wanted erased shards, ascending
         lay[j].out_off = total;
-        total += round_up(uint64_t(n - __builtin_popcount(jobs[j].mask)) * lay[j].Lp, 256);
+        total += round_up(uint64_t(__builtin_popcount(lay[j].w)) * lay[j].Lp, 256);
     }
     GeomDevice* gd;
     int rc = geom_device(rs, &gd);
@@ -94,9 +100,9 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     std::vector<RaggedItem> items(jobs.size());
     std::vector<uint32_t> block_item;
     for (size_t j = 0; j < jobs.size(); ++j) {
-        const uint32_t chunks = uint32_t((jobs[j].len + 4095) / 4096);
+        const uint32_t chunks = lay[j].w ? uint32_t((jobs[j].len + 4095) / 4096) : 0;
         items[j] = RaggedItem{lay[j].off, lay[j].Lp, uint32_t(jobs[j].len), jobs[j].mask,
-                              uint32_t(block_item.size()), 0, lay[j].out_off};
+                              uint32_t(block_item.size()), lay[j].w, lay[j].out_off};
         block_item.insert(block_item.end(), chunks, uint32_t(j));
     }
     const size_t items_bytes = items.size() * sizeof(RaggedItem);
@@ -114,6 +120,7 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     auto fill_one = [&](size_t t) {
         const size_t j = t / size_t(k);
         const int want = int(t % size_t(k));
+        if (!lay[j].w) return;
         int used = 0;
         for (int i = 0; i < n; ++i)
             if ((jobs[j].mask >> i) & 1) {
@@ -153,7 +160,10 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     // small zero-copy calls: completion from the kernel's own signal
     const bool signal = zh && in_total <= completion_flag_max();
     if (signal && (rc = sc->done.arm(sc->stream, &ra.done_count, &ra.done_flag, &ra.done_seq))) return rc;
-    HEC_HIP(launch_rs104_ragged(ra, true, sc->stream));
+    if (some)
+        HEC_HIP(launch_rs104_ragged_some(ra, sc->stream));
+    else
+        HEC_HIP(launch_rs104_ragged(ra, true, sc->stream));
     if (!zh)
         HEC_HIP(hipMemcpyAsync(sc->host + in_total, sc->dev + in_total, total - in_total, hipMemcpyDeviceToHost,
                                sc->stream));
@@ -162,11 +172,11 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
     } else {
         HEC_HIP(hipStreamSynchronize(sc->stream));
     }
-    // hand back the erased shards
+    // hand back the wanted erased shards
     parallel_for(jobs.size(), total - in_total, [&](size_t j) {
         int r = 0;
         for (int i = 0; i < n; ++i)
-            if (!((jobs[j].mask >> i) & 1)) take(j, i, sc->host + lay[j].out_off + uint64_t(r++) * lay[j].Lp);
+            if ((lay[j].w >> i) & 1) take(j, i, sc->host + lay[j].out_off + uint64_t(r++) * lay[j].Lp);
     });
     return HEC_OK;
 }
@@ -175,26 +185,28 @@ int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& job
 
 using namespace hec;
 
-extern "C" {
-
-int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens, const uint8_t* present,
-                             size_t n_stripes, int data_only, size_t* bad_index) {
-    if (!rs || (n_stripes && (!shards || !lens || !present))) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+// hec_rs_reconstruct_batch (required == nullptr: every missing shard, or with
+// data_only the data shards) and hec_rs_reconstruct_some_batch (required: n
+// flags per stripe, the missing shards to rebuild): one body.
+static int reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens, const uint8_t* present,
+                             const uint8_t* required, size_t n_stripes, int data_only, size_t* bad_index) {
     const int k = rs->k, n = rs->n;
     if (bad_index) *bad_index = n_stripes;
+    auto need = [&](size_t s, int i) { return required ? required[s * n + i] != 0 : !(data_only && i >= k); };
     // 1. validate every stripe first (upstream reconstruct checks, per stripe)
     struct Active {
         size_t s;
         uint64_t L;
-        uint32_t mask;
+        uint32_t mask, want;
     };
     std::vector<Active> act;
     for (size_t s = 0; s < n_stripes; ++s) {
         const uint8_t* pr = present + s * n;
         uint64_t L = 0;
         int np = 0, err = HEC_OK;
-        uint32_t mask = 0;
+        uint32_t mask = 0, want = 0;
         for (int i = 0; i < n && !err; ++i) {
+            if (i < 32 && need(s, i)) want |= 1u << i;
             if (!pr[i]) continue;
             const size_t li = lens[s * n + i];
             if (li == 0) err = HEC_ERR_EMPTY_SHARD;
@@ -206,22 +218,25 @@ int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const s
         if (!err && np < n && np < k) err = HEC_ERR_TOO_FEW_SHARDS_PRESENT;
         if (!err && np < n)
             for (int i = 0; i < n; ++i)
-                if (!pr[i] && !(data_only && i >= k) && !shards[s * n + i])
+                if (!pr[i] && need(s, i) && !shards[s * n + i])
                     err = fail(HEC_ERR_INVALID_ARGUMENT, "missing shard without a buffer");
         if (err) {
             if (bad_index) *bad_index = s;
             return err == HEC_ERR_INVALID_ARGUMENT ? err : fail(err, "stripe " + std::to_string(s));
         }
         if (np == n) continue;  // upstream no-op
-        act.push_back({s, L, mask});
+        act.push_back({s, L, mask, want});
     }
     if (act.empty()) return HEC_OK;
 
     // Other geometries: one host-API reconstruct per stripe (same kernels, generic path).
     if (!(k == 10 && rs->m == 4)) {
         for (const Active& a : act) {
-            int rc = data_only ? hec_rs_reconstruct_data(rs, shards + a.s * n, lens + a.s * n, present + a.s * n, n)
-                               : hec_rs_reconstruct(rs, shards + a.s * n, lens + a.s * n, present + a.s * n, n);
+            int rc = required ? hec_rs_reconstruct_some(rs, shards + a.s * n, lens + a.s * n, present + a.s * n,
+                                                        required + a.s * n, n)
+                     : data_only
+                         ? hec_rs_reconstruct_data(rs, shards + a.s * n, lens + a.s * n, present + a.s * n, n)
+                         : hec_rs_reconstruct(rs, shards + a.s * n, lens + a.s * n, present + a.s * n, n);
             if (rc) {
                 if (bad_index) *bad_index = a.s;
                 return rc;
@@ -231,7 +246,7 @@ int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const s
     }
 
     std::vector<CompactJob> jobs(act.size());
-    for (size_t j = 0; j < act.size(); ++j) jobs[j] = CompactJob{act[j].L, act[j].mask};
+    for (size_t j = 0; j < act.size(); ++j) jobs[j] = CompactJob{act[j].L, act[j].mask, act[j].want};
     return compact_reconstruct_104(
         rs, jobs,
         [&](size_t j, int, int shard, uint8_t* dst) {
@@ -239,8 +254,24 @@ int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const s
             return HEC_OK;
         },
         [&](size_t j, int shard, const uint8_t* src) {
-            if (!(data_only && shard >= k)) std::memcpy(shards[act[j].s * n + shard], src, act[j].L);
+            std::memcpy(shards[act[j].s * n + shard], src, act[j].L);
         });
+}
+
+extern "C" {
+
+int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens, const uint8_t* present,
+                             size_t n_stripes, int data_only, size_t* bad_index) {
+    if (!rs || (n_stripes && (!shards || !lens || !present))) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    return reconstruct_batch(rs, shards, lens, present, nullptr, n_stripes, data_only, bad_index);
+}
+
+int hec_rs_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens,
+                                  const uint8_t* present, const uint8_t* required, size_t n_stripes,
+                                  size_t* bad_index) {
+    if (!rs || (n_stripes && (!shards || !lens || !present || !required)))
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    return reconstruct_batch(rs, shards, lens, present, required, n_stripes, 0, bad_index);
 }
 
 }  // extern "C"
@@ -254,10 +285,11 @@ enum class RaggedOp { Encode, Decode, Scrub };
 // Workgroups of one ragged stripe: none for a decode of a stripe whose 14
 // shards are all present (upstream's no-op), none for a scrub of a stripe
 // with no spare shard (nothing to compare: it is not read), so those launch
-// nothing.
-uint64_t ragged_chunks(const hec_stripe_desc& d, RaggedOp op, uint32_t chunk_bytes) {
+// nothing. want: a reconstruct some's word for the stripe (a decode of a
+// stripe that wants none of its erased shards is a no-op too).
+uint64_t ragged_chunks(const hec_stripe_desc& d, RaggedOp op, uint32_t chunk_bytes, uint32_t want = 0xFFFFFFFFu) {
     const uint32_t m = d.present_mask & 0x3FFFu;
-    if (op == RaggedOp::Decode && m == 0x3FFFu) return 0;
+    if (op == RaggedOp::Decode && (want & ~m & 0x3FFFu) == 0) return 0;
     if (op == RaggedOp::Scrub && __builtin_popcount(m) <= 10) return 0;
     return (uint64_t(d.shard_len) + chunk_bytes - 1) / chunk_bytes;
 }
@@ -298,7 +330,7 @@ RaggedPick ragged_scrub_pick(const hec_stripe_desc* descs, uint32_t n) {
 // The argument and descriptor checks of every device-resident ragged call,
 // all before device work; *n_blocks = the workgroup map's entries.
 int ragged_check_args(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, RaggedOp op,
-                      uint32_t chunk_bytes, uint64_t* n_blocks) {
+                      uint32_t chunk_bytes, uint64_t* n_blocks, const uint32_t* wants = nullptr) {
     if (!rs || !d_base || (n && !descs)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     if (!(rs->k == 10 && rs->m == 4))
         return fail(HEC_ERR_INVALID_ARGUMENT, "ragged device batches are RS(10,4) only");
@@ -311,7 +343,7 @@ int ragged_check_args(const hec_rs_t* rs, const uint8_t* d_base, const hec_strip
             return fail(HEC_ERR_INVALID_ARGUMENT, "stripe " + std::to_string(j) +
                                                       ": offset/stride must be 16-byte aligned, stride >= len");
         // 64-bit: a shard_len near 2^32 must not wrap to 0 or 1 chunks
-        *n_blocks += ragged_chunks(d, op, chunk_bytes);
+        *n_blocks += ragged_chunks(d, op, chunk_bytes, wants ? wants[j] : 0xFFFFFFFFu);
         if (*n_blocks > UINT32_MAX) return fail(HEC_ERR_INVALID_ARGUMENT, "ragged batch above 2^32 workgroups");
     }
     return HEC_OK;
@@ -342,15 +374,16 @@ struct RaggedMeta {
         return slot->reserve(bytes);
     }
     // items and workgroup map of one pair written straight into the pinned slot
+    // wants (a reconstruct some): each item's want word, and no map entry for a stripe that wants nothing
     void fill(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, size_t items_at,
-              size_t map_at, uint8_t* d_base, uint64_t n_blocks, RaggedArgs& ra) {
+              size_t map_at, uint8_t* d_base, uint64_t n_blocks, RaggedArgs& ra, const uint32_t* wants = nullptr) {
         RaggedItem* items = reinterpret_cast<RaggedItem*>(slot->h + items_at);
         uint32_t* block_item = reinterpret_cast<uint32_t*>(slot->h + map_at);
         uint32_t first = 0;
         for (uint32_t j = 0; j < n; ++j) {
             const hec_stripe_desc& d = descs[j];
-            const uint32_t chunks = uint32_t(ragged_chunks(d, op, chunk_bytes));
-            items[j] = RaggedItem{d.offset, d.shard_stride, d.shard_len, d.present_mask, first, 0, 0};
+            const uint32_t chunks = uint32_t(ragged_chunks(d, op, chunk_bytes, wants ? wants[j] : 0xFFFFFFFFu));
+            items[j] = RaggedItem{d.offset, d.shard_stride, d.shard_len, d.present_mask, first, wants ? wants[j] : 0, 0};
             std::fill(block_item + first, block_item + first + chunks, j);
             first += chunks;
         }
@@ -362,8 +395,8 @@ struct RaggedMeta {
     // decode2: the arguments of the second pair, a 4 KiB decode map of n_blocks2 entries
     int upload(const hec_stripe_desc* descs, uint32_t n, RaggedOp op, uint32_t chunk_bytes, uint8_t* d_base,
                uint64_t n_blocks, hipStream_t stream, RaggedArgs& ra, RaggedArgs* decode2 = nullptr,
-               uint64_t n_blocks2 = 0) {
-        fill(descs, n, op, chunk_bytes, 0, map_off, d_base, n_blocks, ra);
+               uint64_t n_blocks2 = 0, const uint32_t* wants = nullptr) {
+        fill(descs, n, op, chunk_bytes, 0, map_off, d_base, n_blocks, ra, wants);
         if (decode2) fill(descs, n, RaggedOp::Decode, 4096, items2_off, map2_off, d_base, n_blocks2, *decode2);
         HEC_HIP(hipMemcpyAsync(slot->d, slot->h, bytes, hipMemcpyHostToDevice, stream));
         return HEC_OK;
@@ -371,14 +404,15 @@ struct RaggedMeta {
 };
 
 // Device-resident ragged batches: stripe descriptors come from the host, data
-// stays in HBM.
+// stays in HBM. wants (a decode only): hec_gpu_reconstruct_some_ragged's want
+// words, nullptr for the other calls.
 int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool decode,
-               uint32_t* d_bad, hipStream_t stream) {
+               uint32_t* d_bad, hipStream_t stream, const uint32_t* wants = nullptr) {
     const RaggedOp op = decode ? RaggedOp::Decode : RaggedOp::Encode;
     const bool bitslice = (n == 0 || descs) && ragged_pick(descs, n, decode).bitslice;  // a null list fails below
     const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
     uint64_t n_blocks;
-    HEC_TRY(ragged_check_args(rs, d_base, descs, n, op, chunk_bytes, &n_blocks));
+    HEC_TRY(ragged_check_args(rs, d_base, descs, n, op, chunk_bytes, &n_blocks, wants));
     if (n == 0) return HEC_OK;
     GeomDevice* gd;
     int rc = geom_device(rs, &gd);
@@ -387,7 +421,7 @@ int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs
     if ((rc = meta.reserve(n, n_blocks))) return rc;
     if (decode && (rc = ensure_dense_decode(rs, gd, meta.lease.sc->stream))) return rc;
     RaggedArgs ra{};
-    if ((rc = meta.upload(descs, n, op, chunk_bytes, d_base, n_blocks, stream, ra))) return rc;
+    if ((rc = meta.upload(descs, n, op, chunk_bytes, d_base, n_blocks, stream, ra, nullptr, 0, wants))) return rc;
     ra.tabs = decode ? gd->decode_dense.tabs : gd->encode.tabs;
     ra.lut = decode ? gd->decode_dense.lut : nullptr;
     ra.bad_count = d_bad;
@@ -397,6 +431,8 @@ int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs
     }
     if (bitslice)
         HEC_HIP(launch_rs104_bs_ragged(ra, stream));
+    else if (wants)
+        HEC_HIP(launch_rs104_ragged_some(ra, stream));
     else
         HEC_HIP(launch_rs104_ragged(ra, decode, stream));
     HEC_HIP(hipEventRecord(meta.slot->free, stream));
@@ -536,6 +572,15 @@ int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_
 int hec_gpu_reconstruct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
                                uint32_t n_stripes, uint32_t* d_bad_stripes, void* stream) {
     return hec::gpu_ragged(rs, d_base, descs, n_stripes, true, d_bad_stripes, static_cast<hipStream_t>(stream));
+}
+
+int hec_gpu_reconstruct_some_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
+                                    const uint32_t* h_want_masks, uint32_t n_stripes, uint32_t* d_bad_stripes,
+                                    void* stream) {
+    // the ragged reconstruct's checks, in its order: a null want list fails with its null descriptor list
+    if (rs && d_base && n_stripes && !h_want_masks) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    return hec::gpu_ragged(rs, d_base, descs, n_stripes, true, d_bad_stripes, static_cast<hipStream_t>(stream),
+                           n_stripes ? h_want_masks : nullptr);
 }
 
 int hec_gpu_verify_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,

@@ -67,7 +67,7 @@ void DevicePlanSet::release() {
 // inverse; missing data rows = inverse rows; missing parity rows = parity
 // row x inverse (composed, bit-identical to upstream's second pass since the
 // reconstructed data bytes are unique).
-int decode_plan(const hec_rs* rs, const uint8_t* present, bool data_only, Mat& coefs,
+int decode_plan(const hec_rs* rs, const uint8_t* present, const uint8_t* required, Mat& coefs,
                 std::vector<uint32_t>& in_ids, std::vector<uint32_t>& out_ids, bool* noop) {
     const int k = rs->k, n = rs->n;
     int npresent = 0;
@@ -94,7 +94,7 @@ int decode_plan(const hec_rs* rs, const uint8_t* present, bool data_only, Mat& c
     Mat inv;
     if (!mat_invert(sub, inv)) return fail(HEC_ERR_INVALID_ARGUMENT, "singular decode matrix");
     for (uint32_t i : miss)
-        if (!(data_only && int(i) >= k)) out_ids.push_back(i);
+        if (!required || required[i]) out_ids.push_back(i);
     coefs = Mat(int(out_ids.size()), k);
     const Gf& g = gf();
     for (size_t r = 0; r < out_ids.size(); ++r) {
@@ -234,7 +234,7 @@ int ensure_dense_decode(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
         }
         for (int i = 0; i < n; ++i) present[i] = (mask >> i) & 1;
         bool is_noop = false;
-        int rc = decode_plan(rs, present, false, coefs, in_ids, out_ids, &is_noop);
+        int rc = decode_plan(rs, present, nullptr, coefs, in_ids, out_ids, &is_noop);
         if (rc) return rc;
         lut[mask] = hp.add(coefs, in_ids, out_ids);
     }
@@ -357,6 +357,24 @@ int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uin
     a.mask_limit = ps.lut_bits ? ((1u << ps.lut_bits) - 1u) : 0u;
     if (masks && !ps.lut) return fail(HEC_ERR_INVALID_ARGUMENT, "per-stripe masks need a decode LUT");
     HEC_HIP(launch_apply(a, int(nin), aligned, over_pcie && !masks, s));
+    return HEC_OK;
+}
+
+int run_some(const DevicePlanSet& ps, uint32_t nin, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
+             uint64_t len, uint32_t n_stripes, const uint32_t* masks, const uint32_t* wants, uint32_t* bad,
+             hipStream_t s) {
+    if (!wants)  // "all": the decode's own launches
+        return run_apply(ps, nin, shards, stripe_stride, shard_stride, shards, stripe_stride, shard_stride, len,
+                         n_stripes, masks, bad, s);
+    SomeArgs v{};
+    const bool aligned =
+        fill_args(v.a, ps, shards, stripe_stride, shard_stride, shards, stripe_stride, shard_stride, len, n_stripes, bad);
+    v.a.masks = masks;
+    v.a.lut = ps.lut;
+    v.a.mask_limit = (1u << ps.lut_bits) - 1u;
+    v.wants = wants;
+    if (!ps.lut || !ps.fast104) return fail(HEC_ERR_INVALID_ARGUMENT, "reconstruct some needs the RS(10,4) decode LUT");
+    HEC_HIP(launch_some(v, aligned, s));
     return HEC_OK;
 }
 

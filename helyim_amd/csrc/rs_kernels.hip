@@ -37,6 +37,10 @@
 //    and the masked locate's RAGGED walk) is that scrub over stripes of mixed
 //    lengths and masks: the ragged workgroup map in front of the same bodies;
 //    with CORRECT too (rs104_ragged_correct_kernel) the walk fixes in place.
+//  * Reconstruct some (rs104_some_kernel and siblings) is the decode with a
+//    want word per stripe: a compile-time SOME form of the decode bodies picks
+//    the wanted rows of the mask's plan with scalar work, so only those rows
+//    are computed and stored.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -143,13 +147,49 @@ __device__ __forceinline__ void gf_mac(u32x4 (&acc)[R], const u32x4 d, cu32p tab
     }
 }
 
+// gf_mac with accumulator r taking table row `row[r]` (reconstruct some, the
+// byte-wise tail of a shard).
+template <int R>
+__device__ __forceinline__ void gf_mac_rows(u32x4 (&acc)[R], const u32x4 d, cu32p tab, const uint32_t (&row)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        u32x4 one[1] = {acc[r]};
+        gf_mac<1>(one, d, tab + row[r] * 5);
+        acc[r] = one[0];
+    }
+}
+
+// The rows a reconstruct-some decode computes, all wave-uniform scalar work:
+// w = want & erased, out[q] = the q-th set bit of w (ascending), row[q] = that
+// shard's row in the mask's plan (its rank among the erased shards). Entries
+// at or past nout = popcount(w) are 0, a valid row that is computed by nobody
+// (gf_mac2's prefix break) and never stored.
+struct SomeRows {
+    uint32_t nout;
+    uint32_t out[4], row[4];
+};
+__device__ __forceinline__ SomeRows some_rows(uint32_t erased, uint32_t want) {
+    SomeRows s;
+    uint32_t w = want & erased;
+    s.nout = __builtin_popcount(w);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        s.out[q] = w ? __builtin_ctz(w) : 0;
+        s.row[q] = w ? __builtin_popcount(erased & ((1u << s.out[q]) - 1)) : 0;
+        w &= w - 1;
+    }
+    return s;
+}
+
 // Two inputs at once: the six lookups of a row are folded into the
 // accumulator by three 3-input XORs (v_bitop3) instead of four ops.
 // nrows (wave-uniform, <= R): rows at or past it skip their math (a decode
 // with e < 4 erasures; scalar branches, the tables keep their 4-row stride).
-template <int R, typename V = u32x4>
+// ROWS (reconstruct some): accumulator r takes table row `row[r]` of the set
+// instead of row r; the prefix break at nrows stays.
+template <int R, typename V = u32x4, bool ROWS = false>
 __device__ __forceinline__ void gf_mac2(V (&acc)[R], const V d0, const V d1, cu32p tab0, cu32p tab1,
-                                        uint32_t nrows = R) {
+                                        uint32_t nrows = R, const uint32_t* row = nullptr) {
     constexpr int W = int(sizeof(V) / 4);  // dwords per lane vector
     uint32_t s[2][3][W];
 #pragma unroll
@@ -168,8 +208,9 @@ __device__ __forceinline__ void gf_mac2(V (&acc)[R], const V d0, const V d1, cu3
     uint32_t ta[R * 5], tbw[R * 5];
 #pragma unroll
     for (int j = 0; j < R * 5; ++j) {
-        ta[j] = tab0[j];
-        tbw[j] = tab1[j];
+        const uint32_t at = ROWS ? row[j / 5] * 5 + uint32_t(j % 5) : uint32_t(j);
+        ta[j] = tab0[at];
+        tbw[j] = tab1[at];
     }
     if (R < 4 || nrows < uint32_t(R)) {
 #pragma unroll
@@ -378,17 +419,27 @@ __device__ __forceinline__ void fast_item(const ApplyArgs& a, uint32_t per_strip
 // stripe, and strided batches of shards below 4 GiB) lets each load address
 // be a scalar shard base plus a 32-bit lane offset (global_load saddr form:
 // no per-load 64-bit VALU address math).
-template <bool DEC, bool COMPACT = false, typename OffT = uint64_t>
+// SOME (a decode, hec.h hec_gpu_reconstruct_some_batch): only the erased
+// shards named in `want` are computed and stored (some_rows); a stripe that
+// wants none of its erased shards leaves before the mask is judged, so it is
+// neither read nor counted. COMPACT then holds the wanted outputs only, slot q
+// = the q-th wanted erased shard.
+template <bool DEC, bool COMPACT = false, typename OffT = uint64_t, bool SOME = false>
 __device__ __forceinline__ void rs104_chunk(const uint8_t* in_b, uint8_t* out_b, uint64_t in_shard,
                                             uint64_t out_shard, uint64_t len, uint32_t chunk, uint32_t mask_in,
-                                            cu32p tab, cu32p lut, uint32_t* bad_count) {
+                                            cu32p tab, cu32p lut, uint32_t* bad_count, uint32_t want = 0) {
+    static_assert(DEC || !SOME, "reconstruct some is a decode");
     constexpr int K = 10, N = 14, R = 4;
     uint32_t in_id[K], out_id[R];
+    [[maybe_unused]] uint32_t row[R] = {0, 0, 0, 0};
     uint32_t nout = R;
     uint32_t mask = 0, plan = 0;
     if constexpr (DEC) {
         mask = mask_in & ((1u << N) - 1);
         const uint32_t present = __builtin_popcount(mask);
+        if constexpr (SOME) {
+            if ((want & ~mask & ((1u << N) - 1)) == 0) return;
+        }
         if (present < K) {
             if (chunk == 0 && threadIdx.x == 0 && bad_count) atomicAdd(bad_count, 1u);
             return;
@@ -402,10 +453,20 @@ __device__ __forceinline__ void rs104_chunk(const uint8_t* in_b, uint8_t* out_b,
             m &= m - 1;
         }
         uint32_t e = ~mask & ((1u << N) - 1);
+        if constexpr (SOME) {  // the wanted erased shards, ascending, and their plan rows
+            const SomeRows sr = some_rows(e, want);
+            nout = sr.nout;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {  // erased shards, ascending
-            out_id[r] = COMPACT ? r : (e ? __builtin_ctz(e) : 0);
-            e &= e - 1;
+            for (int r = 0; r < R; ++r) {
+                out_id[r] = COMPACT ? r : sr.out[r];
+                row[r] = sr.row[r];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {  // erased shards, ascending
+                out_id[r] = COMPACT ? r : (e ? __builtin_ctz(e) : 0);
+                e &= e - 1;
+            }
         }
         // plan lookup issued now; its value is first needed after the data
         // loads, so the scalar round trip overlaps them
@@ -439,7 +500,7 @@ __device__ __forceinline__ void rs104_chunk(const uint8_t* in_b, uint8_t* out_b,
         }
 #pragma unroll
         for (int i = 0; i < K; i += 2)
-            gf_mac2<R>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), nout);
+            gf_mac2<R, u32x4, SOME>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), nout, row);
         // Materialise every row before the uniform `r < nout` store branches:
         // otherwise the compiler sinks each row's math into its branch, keeps
         // all 200 table words live and spills SGPRs (154 VGPRs, 3 waves/SIMD).
@@ -455,7 +516,10 @@ __device__ __forceinline__ void rs104_chunk(const uint8_t* in_b, uint8_t* out_b,
         }
         for (int i = 0; i < K; ++i) {
             const u32x4 d = load_tail(in_b + uint64_t(in_id[i]) * in_shard + o, avail);
-            gf_mac<R>(acc, d, tab + i * (R * 5));
+            if constexpr (SOME)
+                gf_mac_rows<R>(acc, d, tab + i * (R * 5), row);
+            else
+                gf_mac<R>(acc, d, tab + i * (R * 5));
         }
         for (int r = 0; r < R; ++r)
             if (r < int(nout)) store_tail(out_b + uint64_t(out_id[r]) * out_shard + o, acc[r], avail);
@@ -484,18 +548,25 @@ __global__ __launch_bounds__(kThreads) void rs104_kernel(ApplyArgs a) {
 // ab_decode_bytes_per_lane.jsonl), and the zero-copy host encode over PCIe
 // (DEC=false: inputs 0..9, outputs 0..3; profiles/r04/e2e_encode_kernels_*).
 // Shards below 4 GiB (32-bit lane offsets).
-template <bool DEC>
+// SOME: rs104_chunk's, the rows of `want` only.
+template <bool DEC, bool SOME = false>
 __device__ __forceinline__ void rs104_narrow_chunk(const uint8_t* in_b, uint8_t* out_b, uint64_t in_shard,
                                                    uint64_t out_shard, uint32_t chunk, uint32_t mask_in, cu32p tabs,
-                                                   cu32p lut, uint32_t* bad_count) {
+                                                   cu32p lut, uint32_t* bad_count, uint32_t want = 0) {
+    static_assert(DEC || !SOME, "reconstruct some is a decode");
     typedef u32x2 V;
     constexpr int K = 10, N = 14, R = 4, VB = int(sizeof(V));
     uint32_t in_id[K], out_id[R];
+    [[maybe_unused]] uint32_t row[R] = {0, 0, 0, 0};
     uint32_t nout = R, plan = 0;
     bool work = true;
     if constexpr (DEC) {
         const uint32_t mask = mask_in & ((1u << N) - 1);
         const uint32_t present = __builtin_popcount(mask);
+        uint32_t e = ~mask & ((1u << N) - 1);
+        if constexpr (SOME) {
+            if ((want & e) == 0) return;  // nothing wanted: not read, not counted
+        }
         if (present < K && chunk == 0 && threadIdx.x == 0 && bad_count) atomicAdd(bad_count, 1u);
         work = present >= K && present < N;  // too few: skipped + counted; all present: upstream no-op
         nout = N - present;
@@ -505,11 +576,20 @@ __device__ __forceinline__ void rs104_narrow_chunk(const uint8_t* in_b, uint8_t*
             in_id[i] = m ? __builtin_ctz(m) : 0;
             m &= m - 1;
         }
-        uint32_t e = ~mask & ((1u << N) - 1);
+        if constexpr (SOME) {  // the wanted erased shards, ascending, and their plan rows
+            const SomeRows sr = some_rows(e, want);
+            nout = sr.nout;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {  // erased shards, ascending
-            out_id[r] = e ? __builtin_ctz(e) : 0;
-            e &= e - 1;
+            for (int r = 0; r < R; ++r) {
+                out_id[r] = sr.out[r];
+                row[r] = sr.row[r];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {  // erased shards, ascending
+                out_id[r] = e ? __builtin_ctz(e) : 0;
+                e &= e - 1;
+            }
         }
         if (work) plan = lut[mask];  // first used after the data loads
     } else {
@@ -533,7 +613,7 @@ __device__ __forceinline__ void rs104_narrow_chunk(const uint8_t* in_b, uint8_t*
         for (int r = 0; r < R; ++r) acc[r] = V(0u);
 #pragma unroll
         for (int i = 0; i < K; i += 2)
-            gf_mac2<R, V>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), nout);
+            gf_mac2<R, V, SOME>(acc, d[i], d[i + 1], tab + i * (R * 5), tab + (i + 1) * (R * 5), nout, row);
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -553,6 +633,70 @@ __global__ __launch_bounds__(kThreads) void rs104_narrow_kernel(ApplyArgs a) {
     const uint32_t mask = DEC ? as_const(a.masks)[stripe] : 0u;
     rs104_narrow_chunk<DEC>(a.in_base + uint64_t(stripe) * a.in_stripe, a.out_base + uint64_t(stripe) * a.out_stripe,
                             a.in_shard, a.out_shard, chunk, mask, as_const(a.tabs), as_const(a.lut), a.bad_count);
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+// Reconstruct some (hec.h hec_gpu_reconstruct_some_batch): the two in-place
+// decodes above with a want word per stripe beside its mask, the SOME form of
+// their chunk bodies. The want word rides the mask's scalar round trip.
+template <typename OffT>
+__global__ __launch_bounds__(kThreads) void rs104_some_kernel(SomeArgs v) {
+    const ApplyArgs& a = v.a;
+    uint32_t stripe, chunk;
+    fast_item(a, a.chunks_per_stripe, stripe, chunk);
+    const uint32_t mask = as_const(a.masks)[stripe], want = as_const(v.wants)[stripe];
+    uint8_t* b = a.out_base + uint64_t(stripe) * a.out_stripe;
+    rs104_chunk<true, false, OffT, true>(b, b, a.in_shard, a.out_shard, a.len, chunk, mask, as_const(a.tabs),
+                                         as_const(a.lut), a.bad_count, want);
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+__global__ __launch_bounds__(kThreads) void rs104_narrow_some_kernel(SomeArgs v) {
+    const ApplyArgs& a = v.a;
+    uint32_t stripe, chunk;
+    fast_item(a, a.chunks_per_stripe, stripe, chunk);
+    const uint32_t mask = as_const(a.masks)[stripe], want = as_const(v.wants)[stripe];
+    uint8_t* b = a.out_base + uint64_t(stripe) * a.out_stripe;
+    rs104_narrow_chunk<true, true>(b, b, a.in_shard, a.out_shard, chunk, mask, as_const(a.tabs), as_const(a.lut),
+                                   a.bad_count, want);
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+// Reconstruct some on layouts the two kernels above do not take (unaligned
+// bases or strides, batches rs104_pick sends to rs_apply_kernel): grid-stride
+// over (stripe, 4 KiB chunk) items of the dense decode plan set, one
+// apply_group of one row per wanted erased shard. The ten inputs are read once
+// per wanted row, again from cache after the first: the traffic saving of the
+// aligned kernels does not hold here, the footprint does.
+template <bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void rs_some_kernel(SomeArgs v) {
+    const ApplyArgs& a = v.a;
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        const uint32_t mask = as_const(a.masks)[stripe] & a.mask_limit;
+        const uint32_t erased = ~mask & a.mask_limit;
+        uint32_t w = as_const(v.wants)[stripe] & erased;
+        if (w == 0) continue;  // nothing wanted: not read, not counted
+        const uint32_t pid = as_const(a.lut)[mask];
+        if (pid == kNoPlan) {
+            if (chunk == 0 && threadIdx.x == 0 && a.bad_count) atomicAdd(a.bad_count, 1u);
+            continue;
+        }
+        const __attribute__((address_space(4))) DevPlan* pp = as_const(a.plans) + pid;
+        const uint32_t nin = pp->nin, row_stride = pp->tab_rows * 5;
+        const uint8_t* in_b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        uint8_t* out_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+        cu32p in_ids = as_const(a.idx) + pp->idx_off;
+        cu32p out_ids = in_ids + nin;  // the erased shards, ascending: entry `row` is the shard of that rank
+        cu32p tab = as_const(a.tabs) + pp->tab_off;
+        const uint64_t chunk_off = uint64_t(chunk) * (kThreads * kVecBytes);
+        for (; w; w &= w - 1) {
+            const uint32_t row = __builtin_popcount(erased & ((1u << __builtin_ctz(w)) - 1));
+            apply_group<10, 1, ALIGNED>(a, in_b, out_b, in_ids, out_ids + row, tab + row * 5, nin, row_stride,
+                                        chunk_off);
+        }
+    }
     if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
 }
 
@@ -659,10 +803,13 @@ __device__ __forceinline__ uint32_t ragged_block(const RaggedArgs& a) {
 
 // Descriptor of the stripe workgroup blk works on: the kernel-argument copy
 // for a one-stripe launch, else the workgroup map and item table (scalar loads).
+// WANT: also the want word of a reconstruct-some item (RaggedItem::pad); the
+// other kernels never load it.
+template <bool WANT = false>
 __device__ __forceinline__ RaggedItem ragged_item(const RaggedArgs& a, uint32_t blk) {
     if (a.inline_one) return a.one;
     const __attribute__((address_space(4))) RaggedItem* p = as_const(a.items) + as_const(a.block_item)[blk];
-    return RaggedItem{p->off, p->shard_stride, p->len, p->mask, p->first_block, 0, p->out_off};
+    return RaggedItem{p->off, p->shard_stride, p->len, p->mask, p->first_block, WANT ? p->want : 0, p->out_off};
 }
 
 // Ragged encode with every stripe length a multiple of 8 KiB: workgroup ->
@@ -727,6 +874,24 @@ hipError_t launch_rs104_ragged(const RaggedArgs& a, bool decode, hipStream_t str
     return launch_ragged(a.compact ? rs104_ragged_kernel<true, true> : rs104_ragged_kernel<true, false>, a, stream);
 }
 
+// Ragged reconstruct some: the ragged decode with each item's want word
+// (RaggedItem::pad) through rs104_chunk's SOME form. COMPACT: the outputs at
+// out_off are the wanted erased shards only, slot q = the q-th of them.
+template <bool COMPACT>
+__global__ __launch_bounds__(kThreads) void rs104_ragged_some_kernel(RaggedArgs a) {
+    const uint32_t blk = ragged_block(a);
+    const RaggedItem it = ragged_item<true>(a, blk);
+    uint8_t* b = a.base + it.off;
+    uint8_t* o = COMPACT ? a.base + it.out_off : b;
+    rs104_chunk<true, COMPACT, uint32_t, true>(b, o, it.shard_stride, it.shard_stride, it.len, blk - it.first_block,
+                                               it.mask, as_const(a.tabs), as_const(a.lut), a.bad_count, it.want);
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+hipError_t launch_rs104_ragged_some(const RaggedArgs& a, hipStream_t stream) {
+    return launch_ragged(a.compact ? rs104_ragged_some_kernel<true> : rs104_ragged_some_kernel<false>, a, stream);
+}
+
 // The kernel an aligned RS(10,4) batch with the fast plan layout runs, shared
 // by launch_apply and the name functions so a reported name is the kernel
 // that runs.
@@ -784,6 +949,7 @@ static void set_fast_map(ApplyArgs& a, uint32_t chunk_bytes, bool round_up) {
 static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
 static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
+static ApplyArgs& apply_args(SomeArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CorrectArgs& c) { return c.a; }
 static ApplyArgs& apply_args(CorrectPresentArgs& c) { return c.a; }
 
@@ -838,6 +1004,11 @@ static ApplyArgs stripe_range(ApplyArgs a, Range r) {
     if (!r.last) a.done_flag = nullptr;
     return a;
 }
+static SomeArgs stripe_range(SomeArgs v, Range r) {
+    v.a = stripe_range(v.a, r);
+    v.wants += r.first;
+    return v;
+}
 
 hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pcie, hipStream_t stream) {
     // RS(10,4) fast path: fixed 4-row table stride, one chunk of >= 2 KiB per
@@ -859,6 +1030,54 @@ hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pci
         return a.masks ? launch_rs104<true>(a, kind, stream) : launch_rs104<false>(a, kind, stream);
     if (nin == 10) return launch_stride(aligned ? rs_apply_kernel<10, true> : rs_apply_kernel<10, false>, a, stream);
     return launch_stride(aligned ? rs_apply_kernel<0, true> : rs_apply_kernel<0, false>, a, stream);
+}
+
+// Reconstruct some over a strided in-place batch: launch_apply's decode, its
+// stripe ranges and rs104_pick's choice, with the SOME kernels.
+static const char* some_name(Rs104Kind k) {
+    switch (k) {
+        case Rs104Kind::Apply: return "rs_some_kernel (table lookup, one pass per wanted row)";
+        case Rs104Kind::Narrow: return "rs104_narrow_some_kernel<8 B per lane> (table lookup)";
+        default: return "rs104_some_kernel (table lookup)";
+    }
+}
+
+const char* some_kernel_name(uint64_t len) {
+    if (len == 0) return kNoLaunch;
+    return some_name(rs104_pick(len, 1, true, false));
+}
+const char* some_batch_kernel_name(uint64_t len, uint64_t n_stripes, bool aligned) {
+    if (len == 0 || n_stripes == 0) return kNoLaunch;
+    if (!aligned) return some_name(Rs104Kind::Apply);
+    const uint64_t per_stripe = (len + 4095) / 4096;  // launch_some's stripe ranges
+    if (per_stripe * n_stripes > kMaxLaunchBlocks && n_stripes > 1 && per_stripe <= kMaxLaunchBlocks)
+        n_stripes = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
+    return some_name(rs104_pick(len, n_stripes, true, false));
+}
+
+hipError_t launch_some(const SomeArgs& v, bool aligned, hipStream_t stream) {
+    const ApplyArgs& a = v.a;
+    const uint64_t per_stripe = (a.len + 4095) / 4096;
+    const uint64_t items = per_stripe * a.n_stripes;
+    if (items > kMaxLaunchBlocks && a.n_stripes > 1 && per_stripe <= kMaxLaunchBlocks) {
+        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
+        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
+            hipError_t e = launch_some(stripe_range(v, range_at(a.n_stripes, step, i)), aligned, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    SomeArgs w = v;
+    switch (aligned ? rs104_pick(a.len, a.n_stripes, true, false) : Rs104Kind::Apply) {
+        case Rs104Kind::Apply:
+            return launch_stride(aligned ? rs_some_kernel<true> : rs_some_kernel<false>, w, stream);
+        case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
+            set_fast_map(w.a, kNarrowChunk, false);
+            return launch_items(rs104_narrow_some_kernel, rs104_narrow_some_kernel, w, stream);
+        default:
+            set_fast_map(w.a, kThreads * kVecBytes, true);
+            return launch_items(rs104_some_kernel<uint32_t>, rs104_some_kernel<uint64_t>, w, stream);
+    }
 }
 
 // ---------------------------------------------------------------------------

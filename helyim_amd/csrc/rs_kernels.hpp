@@ -80,7 +80,7 @@ struct RaggedItem {
     uint32_t len;
     uint32_t mask;         // present mask (decode); ignored by encode
     uint32_t first_block;
-    uint32_t pad;
+    uint32_t want;         // reconstruct some: erased shards worth rebuilding (bit i = shard i); else 0
     uint64_t out_off;      // compact decode: output slot 0 (erased shards, ascending)
 };
 
@@ -93,7 +93,8 @@ struct RaggedArgs {
     const uint32_t* lut;         // decode: mask -> plan id
     uint32_t* bad_count;
     uint32_t compact;            // decode: inputs = slots 0..9 at off (the first 10 present
-                                 // shards), outputs = slots 0..e-1 at out_off (erased shards)
+                                 // shards), outputs = slots 0..e-1 at out_off (erased shards;
+                                 // reconstruct some: the wanted ones of them only)
     uint32_t block_base;         // launcher-internal: first map entry of this launch
     uint32_t map_q8, map_r8;     // launcher-internal: that launch's workgroups / 8 and % 8
     uint32_t inline_one;         // 1: a single stripe, described by `one` (no items / map in memory)
@@ -104,6 +105,13 @@ struct RaggedArgs {
 };
 
 hipError_t launch_rs104_ragged(const RaggedArgs& a, bool decode, hipStream_t stream);
+// Ragged reconstruct some (hec.h hec_gpu_reconstruct_some_ragged): the decode
+// with every item's want word; of a stripe's erased shards only the wanted
+// ones are computed and stored. a.compact: the outputs at out_off are those
+// shards alone, ascending, slot q at out_off + q * shard_stride. A stripe that
+// wants none of its erased shards should own no map entry (its workgroups
+// would leave at once).
+hipError_t launch_rs104_ragged_some(const RaggedArgs& a, hipStream_t stream);
 // Bit-sliced ragged encode: every stripe's length a multiple of kBsChunk bytes;
 // the workgroup map has len / kBsChunk entries per stripe.
 constexpr uint32_t kBsChunk = 2 * kThreads * kVecBytes;  // 8 KiB
@@ -127,6 +135,23 @@ hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pci
 const char* encode_kernel_name(uint64_t len, bool over_pcie);
 // Same for an aligned in-place RS(10,4) device batch reconstruct.
 const char* decode_kernel_name(uint64_t len);
+
+// Reconstruct some (hec.h hec_gpu_reconstruct_some_batch) of a strided
+// in-place RS(10,4) batch. a: a mask-driven decode's arguments over the dense
+// decode plan set (in_* == out_*, masks, lut, bad_count); wants[s] bit i =
+// shard i of stripe s is worth rebuilding. Of each stripe's erased shards only
+// the wanted ones are computed and stored; a stripe that wants none is not
+// read and not counted.
+struct SomeArgs {
+    ApplyArgs a;
+    const uint32_t* wants;
+};
+hipError_t launch_some(const SomeArgs& v, bool aligned, hipStream_t stream);
+// Name of the kernel an aligned reconstruct some of one stripe of this shard
+// length runs, and of the kernel launch_some runs on a whole batch (its first
+// stripe range where it goes in several).
+const char* some_kernel_name(uint64_t len);
+const char* some_batch_kernel_name(uint64_t len, uint64_t n_stripes, bool aligned);
 
 // Parity verify (scrub) of a strided batch: the encode plan's parity is
 // recomputed in registers and compared with the stored parity; nothing but

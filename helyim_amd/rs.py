@@ -95,7 +95,16 @@ class ReedSolomon:
     def reconstruct_data(self, shards: MutableSequence[Optional[object]]) -> None:
         self._reconstruct(shards, data_only=True)
 
-    def _reconstruct(self, shards, data_only: bool) -> None:
+    def reconstruct_some(self, shards: MutableSequence[Optional[object]], required: Sequence) -> None:
+        """reconstruct() of the missing shards flagged in ``required`` (one
+        flag per shard; flags of present shards mean nothing). The other
+        missing slots stay None: they are neither computed nor copied back
+        (hec_rs_reconstruct_some)."""
+        if len(required) != len(shards):
+            raise ValueError(f"{len(required)} required flags for {len(shards)} shards")
+        self._reconstruct(shards, data_only=False, required=[bool(r) for r in required])
+
+    def _reconstruct(self, shards, data_only: bool, required=None) -> None:
         arrs: List[Optional[np.ndarray]] = [None if s is None else _as_u8(s) for s in shards]
         present = (ctypes.c_uint8 * len(arrs))(*[0 if a is None else 1 for a in arrs])
         # Allocate missing slots of the common length (upstream get_or_initialize);
@@ -106,11 +115,15 @@ class ReedSolomon:
         new: List[int] = []
         if len(arrs) == n and L and all(x == L for x in lens) and len(lens) >= self._k and len(lens) < n:
             for i, a in enumerate(arrs):
-                if a is None and not (data_only and i >= self._k):
+                if a is None and not (data_only and i >= self._k) and (required is None or required[i]):
                     arrs[i] = np.zeros(L, dtype=np.uint8)
                     new.append(i)
-        rc = lib.hec_rs_reconstruct_data if data_only else lib.hec_rs_reconstruct
-        check(rc(self._h, _ptr_array(arrs), _len_array(arrs), present, len(arrs)))
+        if required is not None:
+            flags = (ctypes.c_uint8 * len(arrs))(*[1 if r else 0 for r in required])
+            check(lib.hec_rs_reconstruct_some(self._h, _ptr_array(arrs), _len_array(arrs), present, flags, len(arrs)))
+        else:
+            rc = lib.hec_rs_reconstruct_data if data_only else lib.hec_rs_reconstruct
+            check(rc(self._h, _ptr_array(arrs), _len_array(arrs), present, len(arrs)))
         for i in new:
             shards[i] = arrs[i]
 

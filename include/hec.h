@@ -181,6 +181,24 @@ int hec_rs_reconstruct_data(const hec_rs_t* rs, uint8_t* const* shards, const si
 int hec_rs_reconstruct_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens,
                              const uint8_t* present, size_t n_stripes, int data_only, size_t* bad_index);
 
+/* Reconstruct some (klauspost's ReconstructSome; upstream's reconstruct_data
+ * is the case "the data shards"): hec_rs_reconstruct with required[i] != 0
+ * marking the absent shards worth rebuilding (n_shards flags; flags of
+ * present shards mean nothing). Validation and errors are hec_rs_reconstruct's,
+ * in its order. An absent slot that is not required may be NULL and is left
+ * alone; an absent required slot that is NULL returns
+ * HEC_ERR_INVALID_ARGUMENT. Only the required absent shards are computed,
+ * stored and copied back. All flags set is hec_rs_reconstruct; the data flags
+ * only is hec_rs_reconstruct_data. Any codec. */
+int hec_rs_reconstruct_some(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
+                            const uint8_t* present, const uint8_t* required, size_t n_shards);
+/* hec_rs_reconstruct_batch with required flags (n_stripes * total entries,
+ * stripe-major) in the place of data_only; per stripe the semantics are
+ * hec_rs_reconstruct_some's. */
+int hec_rs_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens,
+                                  const uint8_t* present, const uint8_t* required, size_t n_stripes,
+                                  size_t* bad_index);
+
 /* ---- device-resident batches (no reference counterpart: the GPU form of the
  * encode_data_one_batch loop, encoder.rs:158-198, over many stripes) -------
  * Shard (stripe s, shard i) lives at base + s*stripe_stride + i*shard_stride.
@@ -217,6 +235,36 @@ int hec_gpu_reconstruct_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t st
                               uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
                               const uint32_t* d_present_masks, uint32_t* d_bad_stripes,
                               void* stream);
+
+/* Reconstruct only the wanted shards. A want mask has bit i set when shard i
+ * is worth rebuilding. Per stripe, let E be the erased shards (clear bits of
+ * the present mask below 14) and W = want & E:
+ *  - want bits of present shards, and bits 14 to 31, mean nothing;
+ *  - W empty: the stripe is a no-op: not read, not written, not counted,
+ *    however few of its shards are present;
+ *  - fewer than 10 shards present and W non-empty: the stripe is skipped and
+ *    counted into *d_bad_stripes (device word, optional, accumulated);
+ *  - otherwise exactly the shards of W get the bytes
+ *    hec_gpu_reconstruct_batch would give them, decoded from the first 10
+ *    present shards in index order;
+ *  - nothing else is written: not an erased shard outside W, not a survivor,
+ *    not a gap;
+ *  - with every want bit set the call gives hec_gpu_reconstruct_batch's bytes
+ *    and counter.
+ * d_want_masks: device, n_stripes words. Layouts, strides and lengths as
+ * hec_gpu_reconstruct_batch; its argument errors in its order, plus a null
+ * d_want_masks (HEC_ERR_INVALID_ARGUMENT, with the other nulls) and, after
+ * HEC_ERR_EMPTY_SHARD, any codec but RS(10,4) (HEC_ERR_INVALID_ARGUMENT, as
+ * the scrub calls), all before any device work.
+ * Cost: on 16-byte aligned layouts a stripe moves (10 + |W|) shard lengths
+ * and does |W| rows of GF math, where the full decode moves (10 + |E|) and
+ * does |E| rows. Unaligned bases or strides take a generic kernel that makes
+ * one pass over the ten inputs per wanted shard (again from cache after the
+ * first): the footprint holds there, the traffic claim does not. */
+int hec_gpu_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64_t stripe_stride,
+                                   uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                   const uint32_t* d_present_masks, const uint32_t* d_want_masks,
+                                   uint32_t* d_bad_stripes, void* stream);
 
 /* Verify (scrub) n_stripes stripes: the batched, on-device form of
  * ReedSolomon::verify. Reads the data shards from d_data and the STORED parity
@@ -685,6 +733,18 @@ int hec_host_reconstruct_batch_multi(const hec_rs_t* rs, const int* devices, siz
                                      uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
                                      uint32_t* n_bad_stripes);
 
+/* hec_gpu_reconstruct_some_batch's contract on host memory (h_want_masks:
+ * host, n_stripes words), over the three paths of hec_host_reconstruct_batch:
+ * pinned memory in place, pageable memory through the pinned slots, and H2D /
+ * D2H copies with zero copy off. Only the shards of W come back over PCIe; a
+ * stripe with W empty sends nothing either way. RS(10,4) only. Argument
+ * errors as the device call's. *n_bad_stripes (optional) = stripes with fewer
+ * than 10 shards present and W non-empty. Synchronous. */
+int hec_host_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride,
+                                    uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                                    const uint32_t* h_present_masks, const uint32_t* h_want_masks,
+                                    uint32_t* n_bad_stripes);
+
 /* Ragged device batches (RS(10,4)): every stripe has its own length, shard
  * stride and erasure pattern -- BASELINE config 5's mixed 64 KiB-4 MiB
  * stripes in ONE launch. Stripe j's shard i is at d_base + offset + i *
@@ -702,6 +762,13 @@ int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_
                           uint32_t n_stripes, void* stream);
 int hec_gpu_reconstruct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
                                uint32_t n_stripes, uint32_t* d_bad_stripes, void* stream);
+/* hec_gpu_reconstruct_ragged with hec_gpu_reconstruct_some_batch's contract
+ * per stripe. h_want_masks: HOST memory beside descs, n_stripes words (NULL
+ * with n_stripes > 0: HEC_ERR_INVALID_ARGUMENT). A stripe with W empty gets no
+ * workgroups at all. */
+int hec_gpu_reconstruct_some_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
+                                    const uint32_t* h_want_masks, uint32_t n_stripes,
+                                    uint32_t* d_bad_stripes, void* stream);
 
 /* Ragged scrub (RS(10,4)): the masked verify and the masked locate over a
  * ragged batch, stripes of mixed lengths and mixed present masks in one pass
@@ -1111,6 +1178,13 @@ const char* hec_version(void);
 const char* hec_encode_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned in-place RS(10,4) device batch reconstruct. */
 const char* hec_decode_kernel_name(uint64_t shard_len);
+/* Kernel an aligned hec_gpu_reconstruct_some_batch of one stripe of this shard
+ * length runs, and the kernel the call runs on a whole batch with this base,
+ * strides and stripe count (odd bases or strides: the generic one). */
+const char* hec_reconstruct_some_kernel_name(uint64_t shard_len);
+const char* hec_reconstruct_some_batch_kernel_name(const uint8_t* d_shards, uint64_t stripe_stride,
+                                                   uint64_t shard_stride, uint64_t shard_len,
+                                                   uint32_t n_stripes);
 /* Same for a 16-byte-aligned RS(10,4) device batch verify. */
 const char* hec_verify_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned hec_gpu_verify_present_batch (masked verify). */

@@ -134,6 +134,11 @@ extern "C" {
     pub fn hec_rs_reconstruct_batch(rs: *const hec_rs_t, shards: *const *mut u8, lens: *const usize,
                                     present: *const u8, n_stripes: usize, data_only: c_int,
                                     bad_index: *mut usize) -> c_int;
+    pub fn hec_rs_reconstruct_some(rs: *const hec_rs_t, shards: *const *mut u8, shard_lens: *const usize,
+                                   present: *const u8, required: *const u8, n_shards: usize) -> c_int;
+    pub fn hec_rs_reconstruct_some_batch(rs: *const hec_rs_t, shards: *const *mut u8, lens: *const usize,
+                                         present: *const u8, required: *const u8, n_stripes: usize,
+                                         bad_index: *mut usize) -> c_int;
 
     // device-resident and host-memory stripe batches
     pub fn hec_gpu_encode_batch(rs: *const hec_rs_t, d_data: *const u8, data_stripe_stride: u64,
@@ -144,6 +149,10 @@ extern "C" {
                                      shard_stride: u64, shard_len: u64, n_stripes: u32,
                                      d_present_masks: *const u32, d_bad_stripes: *mut u32,
                                      stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_reconstruct_some_batch(rs: *const hec_rs_t, d_shards: *mut u8, stripe_stride: u64,
+                                          shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                          d_present_masks: *const u32, d_want_masks: *const u32,
+                                          d_bad_stripes: *mut u32, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_verify_batch(rs: *const hec_rs_t, d_data: *const u8, data_stripe_stride: u64,
                                 data_shard_stride: u64, d_parity: *const u8, parity_stripe_stride: u64,
                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
@@ -212,6 +221,10 @@ extern "C" {
     pub fn hec_host_reconstruct_batch(rs: *const hec_rs_t, h_shards: *mut u8, stripe_stride: u64,
                                       shard_stride: u64, shard_len: u64, n_stripes: u32,
                                       h_present_masks: *const u32, n_bad_stripes: *mut u32) -> c_int;
+    pub fn hec_host_reconstruct_some_batch(rs: *const hec_rs_t, h_shards: *mut u8, stripe_stride: u64,
+                                           shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                           h_present_masks: *const u32, h_want_masks: *const u32,
+                                           n_bad_stripes: *mut u32) -> c_int;
     pub fn hec_host_encode_batch_multi(rs: *const hec_rs_t, devices: *const c_int, n_devices: usize,
                                        h_data: *const u8, data_stripe_stride: u64, data_shard_stride: u64,
                                        h_parity: *mut u8, parity_stripe_stride: u64, parity_shard_stride: u64,
@@ -224,6 +237,9 @@ extern "C" {
                                  n_stripes: u32, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_reconstruct_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
                                       n_stripes: u32, d_bad_stripes: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hec_gpu_reconstruct_some_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
+                                           h_want_masks: *const u32, n_stripes: u32, d_bad_stripes: *mut u32,
+                                           stream: *mut c_void) -> c_int;
     pub fn hec_gpu_verify_ragged(rs: *const hec_rs_t, d_base: *const u8, descs: *const hec_stripe_desc,
                                  n_stripes: u32, d_check: *mut u32, d_bad_stripes: *mut u32,
                                  d_unchecked: *mut u32, stream: *mut c_void) -> c_int;
@@ -316,6 +332,9 @@ extern "C" {
     pub fn hec_version() -> *const c_char;
     pub fn hec_encode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_decode_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_reconstruct_some_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_reconstruct_some_batch_kernel_name(d_shards: *const u8, stripe_stride: u64, shard_stride: u64,
+                                                  shard_len: u64, n_stripes: u32) -> *const c_char;
     pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_check_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_ragged_kernel_name(descs: *const hec_stripe_desc, n_stripes: u32, decode: c_int) -> *const c_char;
