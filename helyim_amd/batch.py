@@ -41,27 +41,40 @@ def _check_stripes(t: torch.Tensor, rs: ReedSolomon, shards: int = None):
     _check_device(t)
 
 
-def encode_batch(rs: ReedSolomon, stripes: torch.Tensor, stream=None) -> None:
-    """Parity of every stripe of ``stripes[S, total, L]`` into shards data..total."""
+def _layout(rs: ReedSolomon, stripes: torch.Tensor):
+    """In-place ``stripes[S, total, L]``, checked -> (the six data / parity
+    layout arguments of the C calls, S, L): the parity is shards data..total."""
     _check_stripes(stripes, rs)
-    k = rs.data_shard_count()
     S, n, L = stripes.shape
     st, sh = stripes.stride(0), stripes.stride(1)
     base = stripes.data_ptr()
-    check(lib.hec_gpu_encode_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S,
-                                   _stream_ptr(stream)))
+    return (base, st, sh, base + rs.data_shard_count() * sh, st, sh), S, L
 
 
-def encode_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, stream=None) -> None:
-    """data[S, k, L] -> parity[S, m, L] (separate buffers)."""
+def _layout_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor):
+    """_layout of data[S, k, L] and parity[S, m, L] in separate buffers."""
     _check_stripes(data, rs, rs.data_shard_count())
     _check_stripes(parity, rs, rs.parity_shard_count())
     S, k, L = data.shape
     if parity.shape[0] != S or parity.shape[2] != L:
         raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
-    check(lib.hec_gpu_encode_batch(rs.handle, data.data_ptr(), data.stride(0), data.stride(1),
-                                   parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
-                                   _stream_ptr(stream)))
+    return (data.data_ptr(), data.stride(0), data.stride(1), parity.data_ptr(), parity.stride(0),
+            parity.stride(1)), S, L
+
+
+def _encode(rs, layout, stream):
+    lay, S, L = layout
+    check(lib.hec_gpu_encode_batch(rs.handle, *lay, L, S, _stream_ptr(stream)))
+
+
+def encode_batch(rs: ReedSolomon, stripes: torch.Tensor, stream=None) -> None:
+    """Parity of every stripe of ``stripes[S, total, L]`` into shards data..total."""
+    _encode(rs, _layout(rs, stripes), stream)
+
+
+def encode_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, stream=None) -> None:
+    """data[S, k, L] -> parity[S, m, L] (separate buffers)."""
+    _encode(rs, _layout_sep(rs, data, parity), stream)
 
 
 def reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
@@ -131,6 +144,13 @@ def _verify_args(S: int, mismatch: torch.Tensor, bad_stripes: torch.Tensor):
     return _words_arg(S, mismatch, "mismatch"), _counter_arg(bad_stripes, "bad_stripes")
 
 
+def _verify(rs, layout, mismatch, bad_stripes, stream):
+    lay, S, L = layout
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    check(lib.hec_gpu_verify_batch(rs.handle, *lay, L, S, mismatch.data_ptr(), bad, _stream_ptr(stream)))
+    return mismatch
+
+
 def verify_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
                  bad_stripes: torch.Tensor = None, stream=None) -> torch.Tensor:
     """Scrub ``stripes[S, total, L]`` on the device (hec_gpu_verify_batch): word s
@@ -139,55 +159,20 @@ def verify_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor 
     parity of its data shards; 0 = clean. bad_stripes (32-bit CUDA word,
     accumulated): plus one per stripe with a non-zero word. Nothing else is
     written. Asynchronous on the stream."""
-    _check_stripes(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    check(lib.hec_gpu_verify_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), bad,
-                                   _stream_ptr(stream)))
-    return mismatch
+    return _verify(rs, _layout(rs, stripes), mismatch, bad_stripes, stream)
 
 
 def verify_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, mismatch: torch.Tensor = None,
                      bad_stripes: torch.Tensor = None, stream=None) -> torch.Tensor:
     """verify_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
-    _check_stripes(data, rs, rs.data_shard_count())
-    _check_stripes(parity, rs, rs.parity_shard_count())
-    S, k, L = data.shape
-    if parity.shape[0] != S or parity.shape[2] != L:
-        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    check(lib.hec_gpu_verify_batch(rs.handle, data.data_ptr(), data.stride(0), data.stride(1),
-                                   parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
-                                   mismatch.data_ptr(), bad, _stream_ptr(stream)))
-    return mismatch
+    return _verify(rs, _layout_sep(rs, data, parity), mismatch, bad_stripes, stream)
 
 
-def _locate(call, rs, stripes, mismatch, suspects, bad_stripes, stream):
-    _check_stripes(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
+def _locate(call, rs, layout, mismatch, suspects, bad_stripes, stream):
+    lay, S, L = layout
     mismatch, bad = _verify_args(S, mismatch, bad_stripes)
     suspects = _words_arg(S, suspects, "suspects")
-    check(call(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
-               _stream_ptr(stream)))
-    return mismatch, suspects
-
-
-def _locate_sep(call, rs, data, parity, mismatch, suspects, bad_stripes, stream):
-    _check_stripes(data, rs, rs.data_shard_count())
-    _check_stripes(parity, rs, rs.parity_shard_count())
-    S, k, L = data.shape
-    if parity.shape[0] != S or parity.shape[2] != L:
-        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    suspects = _words_arg(S, suspects, "suspects")
-    check(call(rs.handle, data.data_ptr(), data.stride(0), data.stride(1), parity.data_ptr(), parity.stride(0),
-               parity.stride(1), L, S, mismatch.data_ptr(), suspects.data_ptr(), bad, _stream_ptr(stream)))
+    check(call(rs.handle, *lay, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad, _stream_ptr(stream)))
     return mismatch, suspects
 
 
@@ -213,14 +198,16 @@ def locate_corrupt_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch
     31) = a column no single shard explains; 0 = clean. With at most 3 wrong
     shards in a column no intact shard is ever named. Nothing else is written.
     Asynchronous on the stream."""
-    return _locate(lib.hec_gpu_locate_corrupt_batch, rs, stripes, mismatch, suspects, bad_stripes, stream)
+    return _locate(lib.hec_gpu_locate_corrupt_batch, rs, _layout(rs, stripes), mismatch, suspects, bad_stripes,
+                   stream)
 
 
 def locate_corrupt_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
                              mismatch: torch.Tensor = None, suspects: torch.Tensor = None,
                              bad_stripes: torch.Tensor = None, stream=None):
     """locate_corrupt_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
-    return _locate_sep(lib.hec_gpu_locate_corrupt_batch, rs, data, parity, mismatch, suspects, bad_stripes, stream)
+    return _locate(lib.hec_gpu_locate_corrupt_batch, rs, _layout_sep(rs, data, parity), mismatch, suspects,
+                   bad_stripes, stream)
 
 
 def locate_corrupt_pairs_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
@@ -233,15 +220,16 @@ def locate_corrupt_pairs_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch:
     are named exactly; 3 wrong shards never name a single intact shard but
     may name an intact pair (include/hec.h) -- locate_corrupt_batch keeps the
     stricter promise. Asynchronous on the stream."""
-    return _locate(lib.hec_gpu_locate_corrupt_pairs_batch, rs, stripes, mismatch, suspects, bad_stripes, stream)
+    return _locate(lib.hec_gpu_locate_corrupt_pairs_batch, rs, _layout(rs, stripes), mismatch, suspects, bad_stripes,
+                   stream)
 
 
 def locate_corrupt_pairs_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
                                    mismatch: torch.Tensor = None, suspects: torch.Tensor = None,
                                    bad_stripes: torch.Tensor = None, stream=None):
     """locate_corrupt_pairs_batch of data[S, k, L] against the stored parity[S, m, L] (separate buffers)."""
-    return _locate_sep(lib.hec_gpu_locate_corrupt_pairs_batch, rs, data, parity, mismatch, suspects, bad_stripes,
-                       stream)
+    return _locate(lib.hec_gpu_locate_corrupt_pairs_batch, rs, _layout_sep(rs, data, parity), mismatch, suspects,
+                   bad_stripes, stream)
 
 
 def repair_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
@@ -279,6 +267,17 @@ def _bytes_counter_arg(t: torch.Tensor, name: str):
     return t.data_ptr()
 
 
+def _correct(rs, layout, mismatch, suspects, bad_stripes, uncorrected, corrected_bytes, pairs, stream):
+    lay, S, L = layout
+    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
+    suspects = _words_arg(S, suspects, "suspects")
+    call = lib.hec_gpu_correct_pairs_batch if pairs else lib.hec_gpu_correct_batch
+    check(call(rs.handle, *lay, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
+               _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
+               _stream_ptr(stream)))
+    return mismatch, suspects
+
+
 def correct_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor = None,
                   suspects: torch.Tensor = None, bad_stripes: torch.Tensor = None, uncorrected: torch.Tensor = None,
                   corrected_bytes: torch.Tensor = None, pairs: bool = False, stream=None):
@@ -293,18 +292,8 @@ def correct_batch(rs: ReedSolomon, stripes: torch.Tensor, mismatch: torch.Tensor
     accumulated): the bytes changed. Unlike repair_batch this also restores a
     stripe whose columns name five or more shards. Asynchronous on the
     stream."""
-    _check_stripes(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    suspects = _words_arg(S, suspects, "suspects")
-    call = lib.hec_gpu_correct_pairs_batch if pairs else lib.hec_gpu_correct_batch
-    check(call(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
-               _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
-               _stream_ptr(stream)))
-    return mismatch, suspects
+    return _correct(rs, _layout(rs, stripes), mismatch, suspects, bad_stripes, uncorrected, corrected_bytes, pairs,
+                    stream)
 
 
 def correct_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor, mismatch: torch.Tensor = None,
@@ -312,19 +301,8 @@ def correct_batch_sep(rs: ReedSolomon, data: torch.Tensor, parity: torch.Tensor,
                       uncorrected: torch.Tensor = None, corrected_bytes: torch.Tensor = None, pairs: bool = False,
                       stream=None):
     """correct_batch of data[S, k, L] and the stored parity[S, m, L] (separate buffers, both fixed in place)."""
-    _check_stripes(data, rs, rs.data_shard_count())
-    _check_stripes(parity, rs, rs.parity_shard_count())
-    S, k, L = data.shape
-    if parity.shape[0] != S or parity.shape[2] != L:
-        raise ValueError(f"parity {tuple(parity.shape)} does not match data {tuple(data.shape)}")
-    mismatch, bad = _verify_args(S, mismatch, bad_stripes)
-    suspects = _words_arg(S, suspects, "suspects")
-    call = lib.hec_gpu_correct_pairs_batch if pairs else lib.hec_gpu_correct_batch
-    check(call(rs.handle, data.data_ptr(), data.stride(0), data.stride(1), parity.data_ptr(), parity.stride(0),
-               parity.stride(1), L, S, mismatch.data_ptr(), suspects.data_ptr(), bad,
-               _counter_arg(uncorrected, "uncorrected"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
-               _stream_ptr(stream)))
-    return mismatch, suspects
+    return _correct(rs, _layout_sep(rs, data, parity), mismatch, suspects, bad_stripes, uncorrected, corrected_bytes,
+                    pairs, stream)
 
 
 def _masks_arg(S: int, present_masks: torch.Tensor) -> torch.Tensor:
@@ -333,6 +311,16 @@ def _masks_arg(S: int, present_masks: torch.Tensor) -> torch.Tensor:
         raise ValueError("present_masks must be a contiguous 32-bit CUDA tensor with one word per stripe")
     _check_device(present_masks)
     return present_masks
+
+
+def _present_args(rs, stripes, present_masks, **words):
+    """The masked calls' shared preparation -> (the C arguments up to the
+    masks, the per-stripe result tensors named in words, allocated when None)."""
+    _check_stripes(stripes, rs)
+    S, n, L = stripes.shape
+    masks = _masks_arg(S, present_masks)
+    lead = (rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr())
+    return lead, [_words_arg(S, t, name) for name, t in words.items()]
 
 
 def verify_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: torch.Tensor,
@@ -347,13 +335,9 @@ def verify_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks: 
     not read and are counted into unchecked; bad_stripes counts the non-zero
     words (32-bit CUDA words, accumulated). Absent shards are never read and
     nothing but the words is written. Asynchronous on the stream."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    masks = _masks_arg(S, present_masks)
-    check = _words_arg(S, check, "check")
+    lead, (check,) = _present_args(rs, stripes, present_masks, check=check)
     check_status(lib.hec_gpu_verify_present_batch(
-        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
-        check.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"),
+        *lead, check.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"),
         _stream_ptr(stream)))
     return check
 
@@ -369,14 +353,9 @@ def locate_corrupt_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present
     detected (bit 31); with 2 lost, two wrong shards in one column may name an
     intact shard (include/hec.h has the table). With the full mask the words
     are locate_corrupt_batch's (check = mismatch << 10)."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    masks = _masks_arg(S, present_masks)
-    check = _words_arg(S, check, "check")
-    suspects = _words_arg(S, suspects, "suspects")
+    lead, (check, suspects) = _present_args(rs, stripes, present_masks, check=check, suspects=suspects)
     check_status(lib.hec_gpu_locate_corrupt_present_batch(
-        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
-        check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        *lead, check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
         _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
     return check, suspects
 
@@ -394,15 +373,10 @@ def reconstruct_checked_batch(rs: ReedSolomon, stripes: torch.Tensor, present_ma
     included (use mask 0x3FFF), and counted into unrepaired. bad_stripes is
     reconstruct_batch's count. Only shards outside a stripe's use mask are
     written. Run verify_batch afterwards for proof."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    masks = _masks_arg(S, present_masks)
-    check = _words_arg(S, check, "check")
-    suspects = _words_arg(S, suspects, "suspects")
-    use_masks = _words_arg(S, use_masks, "use_masks")
+    lead, (check, suspects, use_masks) = _present_args(rs, stripes, present_masks, check=check, suspects=suspects,
+                                                       use_masks=use_masks)
     check_status(lib.hec_gpu_reconstruct_checked_batch(
-        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(),
-        check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        *lead, check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
         _counter_arg(unrepaired, "unrepaired"), _stream_ptr(stream)))
     return check, suspects, use_masks
 
@@ -422,14 +396,9 @@ def correct_present_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks:
     uncorrected (32-bit CUDA word, accumulated): plus one per stripe left
     inconsistent (bit 31, or dirty with fewer spares); corrected_bytes (64-bit
     CUDA word, accumulated): the bytes changed. Asynchronous on the stream."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    masks = _masks_arg(S, present_masks)
-    check = _words_arg(S, check, "check")
-    suspects = _words_arg(S, suspects, "suspects")
+    lead, (check, suspects) = _present_args(rs, stripes, present_masks, check=check, suspects=suspects)
     check_status(lib.hec_gpu_correct_present_batch(
-        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(), int(min_spares),
-        check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
+        *lead, int(min_spares), check.data_ptr(), suspects.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
         _counter_arg(unchecked, "unchecked"), _counter_arg(uncorrected, "uncorrected"),
         _bytes_counter_arg(corrected_bytes, "corrected_bytes"), _stream_ptr(stream)))
     return check, suspects
@@ -449,17 +418,12 @@ def reconstruct_corrected_batch(rs: ReedSolomon, stripes: torch.Tensor, present_
     reconstruct_checked_batch this also restores a stripe whose columns name
     many different shards; a survivor that is wrong throughout is cheaper as
     an erasure there. Run verify_batch afterwards for proof."""
-    _check_stripes(stripes, rs)
-    S, n, L = stripes.shape
-    masks = _masks_arg(S, present_masks)
-    check = _words_arg(S, check, "check")
-    suspects = _words_arg(S, suspects, "suspects")
-    use_masks = _words_arg(S, use_masks, "use_masks")
+    lead, (check, suspects, use_masks) = _present_args(rs, stripes, present_masks, check=check, suspects=suspects,
+                                                       use_masks=use_masks)
     check_status(lib.hec_gpu_reconstruct_corrected_batch(
-        rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1), L, S, masks.data_ptr(), int(min_spares),
-        check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
-        _counter_arg(unrepaired, "unrepaired"), _bytes_counter_arg(corrected_bytes, "corrected_bytes"),
-        _stream_ptr(stream)))
+        *lead, int(min_spares), check.data_ptr(), suspects.data_ptr(), use_masks.data_ptr(),
+        _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unrepaired, "unrepaired"),
+        _bytes_counter_arg(corrected_bytes, "corrected_bytes"), _stream_ptr(stream)))
     return check, suspects, use_masks
 
 
@@ -637,6 +601,13 @@ def reconstruct_some_ragged(rs: ReedSolomon, base: torch.Tensor, descs, want_mas
                                               _counter_arg(bad_stripes, "bad_stripes"), _stream_ptr(stream)))
 
 
+def _ragged_args(rs, base, descs, **words):
+    """The ragged scrub calls' shared preparation -> (the descriptor array,
+    the per-stripe result tensors named in words, allocated when None)."""
+    d = _desc_array(descs, base, rs.total_shard_count())
+    return d, [_words_arg(len(d), t, name) for name, t in words.items()]
+
+
 def verify_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: torch.Tensor = None,
                   bad_stripes: torch.Tensor = None, unchecked: torch.Tensor = None, stream=None) -> torch.Tensor:
     """Scrub stripes of mixed lengths and present masks in one pass
@@ -649,8 +620,7 @@ def verify_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: torch.Tenso
     unchecked; bad_stripes counts the non-zero words (32-bit CUDA words,
     accumulated). Nothing but the words is written. Asynchronous on the
     stream."""
-    d = _desc_array(descs, base, rs.total_shard_count())
-    check = _words_arg(len(d), check, "check")
+    d, (check,) = _ragged_args(rs, base, descs, check=check)
     check_status(lib.hec_gpu_verify_ragged(
         rs.handle, base.data_ptr(), d.ctypes.data, len(d), check.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"),
         _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
@@ -668,9 +638,7 @@ def locate_corrupt_ragged(rs: ReedSolomon, base: torch.Tensor, descs, check: tor
     dirty column of a stripe with one spare shard). To repair, clear the named
     bits in the stripe's present mask and call reconstruct_ragged; verify_ragged
     with the original masks is the proof."""
-    d = _desc_array(descs, base, rs.total_shard_count())
-    check = _words_arg(len(d), check, "check")
-    suspects = _words_arg(len(d), suspects, "suspects")
+    d, (check, suspects) = _ragged_args(rs, base, descs, check=check, suspects=suspects)
     check_status(lib.hec_gpu_locate_corrupt_ragged(
         rs.handle, base.data_ptr(), d.ctypes.data, len(d), check.data_ptr(), suspects.data_ptr(),
         _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"), _stream_ptr(stream)))
@@ -689,9 +657,7 @@ def correct_ragged(rs: ReedSolomon, base: torch.Tensor, descs, min_spares: int =
     at or past a stripe's length and the gaps between stripes are never
     touched. uncorrected, corrected_bytes: as correct_present_batch's.
     Asynchronous on the stream."""
-    d = _desc_array(descs, base, rs.total_shard_count())
-    check = _words_arg(len(d), check, "check")
-    suspects = _words_arg(len(d), suspects, "suspects")
+    d, (check, suspects) = _ragged_args(rs, base, descs, check=check, suspects=suspects)
     check_status(lib.hec_gpu_correct_ragged(
         rs.handle, base.data_ptr(), d.ctypes.data, len(d), int(min_spares), check.data_ptr(), suspects.data_ptr(),
         _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unchecked, "unchecked"),
@@ -713,10 +679,8 @@ def reconstruct_corrected_ragged(rs: ReedSolomon, base: torch.Tensor, descs, min
     stripe keeps its holes (use mask 0x3FFF) and is counted into unrepaired.
     bad_stripes counts the stripes with fewer than ten shards. Run
     verify_ragged with full masks afterwards for proof."""
-    d = _desc_array(descs, base, rs.total_shard_count())
-    check = _words_arg(len(d), check, "check")
-    suspects = _words_arg(len(d), suspects, "suspects")
-    use_masks = _words_arg(len(d), use_masks, "use_masks")
+    d, (check, suspects, use_masks) = _ragged_args(rs, base, descs, check=check, suspects=suspects,
+                                                   use_masks=use_masks)
     check_status(lib.hec_gpu_reconstruct_corrected_ragged(
         rs.handle, base.data_ptr(), d.ctypes.data, len(d), int(min_spares), check.data_ptr(), suspects.data_ptr(),
         use_masks.data_ptr(), _counter_arg(bad_stripes, "bad_stripes"), _counter_arg(unrepaired, "unrepaired"),

@@ -417,8 +417,9 @@ Job small_rows_job(int dat_fd, const Fd* out, const DevicePlanSet* enc, uint64_t
     job.h2d.push_back({0, 0, b * small_row});
     // parity device/host layout [4][b][small]: each parity file gets one contiguous piece
     job.kernel = [=](uint8_t* d, hipStream_t s) {
-        return run_apply(*enc, K, d, small_row, small, d + data_cap, small, b * small, small, uint32_t(b),
-                         nullptr, nullptr, s);
+        const Batch rows = Batch::split(arena(d, small_row, small), arena(d + data_cap, small, b * small), small,
+                                        uint32_t(b));
+        return run_apply(*enc, K, rows, nullptr, nullptr, s);
     };
     job.d2h.push_back({data_cap, data_cap, b * small * M});
     for (int j = 0; j < K; ++j) {
@@ -494,7 +495,8 @@ static int write_ec_files_impl(const std::string& base, uint64_t buf_size, uint6
                 add_reads(job.reads, dat.fd, j * n, n, processed + j * large + t, 1 << 20, 2);
             job.h2d.push_back({0, 0, n * K});
             job.kernel = [=](uint8_t* d, hipStream_t s) {
-                return run_apply(*enc, K, d, 0, n, d + data_cap, 0, n, n, 1, nullptr, nullptr, s);
+                return run_apply(*enc, K, Batch::split(arena(d, 0, n), arena(d + data_cap, 0, n), n, 1), nullptr,
+                                 nullptr, s);
             };
             job.d2h.push_back({data_cap, data_cap, n * M});
             for (int j = 0; j < K; ++j) job.writes.push_back({out[j].fd, out_off + t, {{j * n, n}}});
@@ -633,7 +635,7 @@ static int rebuild_ec_files_impl(const std::string& base, uint32_t* ids, size_t*
                 job.h2d.push_back({id * slot, id * slot, nr * row_size});
             }
             job.kernel = [=](uint8_t* d, hipStream_t s) {
-                return run_apply(*psp, K, d, row_size, slot, d, row_size, slot, row_size, uint32_t(nr), nullptr,
+                return run_apply(*psp, K, Batch::in_place(arena(d, row_size, slot), row_size, uint32_t(nr)), nullptr,
                                  nullptr, s);
             };
             for (uint32_t id : out_ids) {

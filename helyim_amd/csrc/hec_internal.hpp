@@ -1,7 +1,9 @@
 // Internal declarations of libhec, shared by every csrc/*.cpp: the error
-// record (errors.cpp), staging buffers, the per-device registry and slot
-// leases, the host worker pool (host_pool.cpp), plans and per-geometry device
-// state (plans.cpp) and the per-call host paths' scratch (host_calls.cpp).
+// record (errors.cpp), the strided batch view (Strided, Batch), staging
+// buffers, the per-device registry and slot leases, the host worker pool
+// (host_pool.cpp), plans, per-geometry device state and the launches of a
+// plan set or a scrub over a batch (plans.cpp: run_apply, run_some, run_scrub)
+// and the per-call host paths' scratch (host_calls.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -80,19 +82,48 @@ struct ErrorSlot {
 
 constexpr uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
+// One [stripe][shard] arena of a strided batch: shard i of stripe st starts at
+// base + st * stripe + i * shard.
+struct Strided {
+    uint8_t* base = nullptr;
+    uint64_t stripe = 0, shard = 0;
+    Strided from(uint64_t i) const { return Strided{base + i * shard, stripe, shard}; }  // the arena from shard i on
+    uint64_t low_bits() const { return uint64_t(reinterpret_cast<uintptr_t>(base)) | stripe | shard; }
+};
+// An arena the call only reads is viewed through the same struct.
+inline Strided arena(const void* base, uint64_t stripe, uint64_t shard) {
+    return Strided{static_cast<uint8_t*>(const_cast<void*>(base)), stripe, shard};
+}
+// A strided batch as the launches see it: n_stripes stripes of len-byte shards,
+// read from `in`, written to (a verify: compared with) `out`.
+struct Batch {
+    Strided in, out;
+    uint64_t len = 0;
+    uint32_t n_stripes = 0;
+    static Batch in_place(const Strided& a, uint64_t len, uint32_t n) { return Batch{a, a, len, n}; }
+    static Batch split(const Strided& data, const Strided& parity, uint64_t len, uint32_t n) {
+        return Batch{data, parity, len, n};
+    }
+    // an in-place arena as data shards [0, k) and the parity shards behind them
+    static Batch split_at(const Strided& a, int k, uint64_t len, uint32_t n) {
+        return Batch{a, a.from(uint64_t(k)), len, n};
+    }
+    // every base and stride 16-byte aligned: the launches' vector-access kernels
+    bool aligned() const { return ((in.low_bits() | out.low_bits()) % 16) == 0; }
+};
+
 // Strided-batch geometry sanity (the C ABI sees only pointers, so sizes cannot
 // be checked): shards of a stripe and stripes of a shard must not overlap,
 // and the batch's byte extent must not wrap the address space.
-inline int check_strided(const char* what, uint32_t shards, uint64_t stripe_stride, uint64_t shard_stride,
-                         uint64_t len, uint32_t n_stripes) {
-    if (shards > 1 && shard_stride < len)
+inline int check_strided(const char* what, uint32_t shards, const Strided& a, uint64_t len, uint32_t n_stripes) {
+    if (shards > 1 && a.shard < len)
         return fail(HEC_ERR_INVALID_ARGUMENT, std::string(what) + ": shard stride below shard length");
-    if (n_stripes > 1 && stripe_stride < len)
+    if (n_stripes > 1 && a.stripe < len)
         return fail(HEC_ERR_INVALID_ARGUMENT, std::string(what) + ": stripe stride below shard length");
-    uint64_t a, b, e;
-    if (__builtin_mul_overflow(uint64_t(n_stripes ? n_stripes - 1 : 0), stripe_stride, &a) ||
-        __builtin_mul_overflow(uint64_t(shards ? shards - 1 : 0), shard_stride, &b) ||
-        __builtin_add_overflow(a, b, &e) || __builtin_add_overflow(e, len, &e))
+    uint64_t x, y, e;
+    if (__builtin_mul_overflow(uint64_t(n_stripes ? n_stripes - 1 : 0), a.stripe, &x) ||
+        __builtin_mul_overflow(uint64_t(shards ? shards - 1 : 0), a.shard, &y) ||
+        __builtin_add_overflow(x, y, &e) || __builtin_add_overflow(e, len, &e))
         return fail(HEC_ERR_INVALID_ARGUMENT, std::string(what) + ": batch extent overflows");
     return HEC_OK;
 }
@@ -104,10 +135,12 @@ inline int check_batch_args(const hec_rs* rs, const void* a, const void* b, uint
     if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
     return HEC_OK;
 }
-inline int check_encode_strides(const hec_rs* rs, uint64_t data_stripe, uint64_t data_shard, uint64_t parity_stripe,
-                                uint64_t parity_shard, uint64_t len, uint32_t n_stripes) {
-    if (int rc = check_strided("data", uint32_t(rs->k), data_stripe, data_shard, len, n_stripes)) return rc;
-    return check_strided("parity", uint32_t(rs->m), parity_stripe, parity_shard, len, n_stripes);
+inline int check_batch_args(const hec_rs* rs, const Batch& b) {
+    return check_batch_args(rs, b.in.base, b.out.base, b.len);
+}
+inline int check_encode_strides(const hec_rs* rs, const Batch& b) {
+    if (int rc = check_strided("data", uint32_t(rs->k), b.in, b.len, b.n_stripes)) return rc;
+    return check_strided("parity", uint32_t(rs->m), b.out, b.len, b.n_stripes);
 }
 int hip_fail(hipError_t e, const char* what);
 
@@ -217,11 +250,12 @@ int decode_plan(const hec_rs* rs, const uint8_t* present, const uint8_t* require
 
 // Per-device state shared by all contexts of one geometry.
 struct GeomDevice {
+    uint32_t k = 0;              // data shards, fixed per cached geometry (the cache key has k): run_scrub's verify nin
     DevicePlanSet encode;        // plan 0 = encode
     DevicePlanSet decode_dense;  // LUT over all 2^n present masks (n <= 16)
     bool decode_ready = false;
     // RS(10,4) only: the locate kernel's ratio constants as one 3 x 10 plan,
-    // row j - 1, input c = P[j][c] / P[0][c] (P = the parity rows; run_locate)
+    // row j - 1, input c = P[j][c] / P[0][c] (P = the parity rows; run_scrub)
     DevicePlanSet locate;
     // RS(10,4) only: the pair search's constants (rs_kernels.hpp
     // VerifyArgs::pair_tabs): plan 0 = T, 4 x 4, classical syndromes S = T *
@@ -443,38 +477,62 @@ void parallel_for(size_t n, uint64_t bytes, F fn) {
 // Run one plan set over a strided batch (plan 0 for every stripe unless masks).
 // done (optional): the launch signals it (Completion::arm) when it finishes.
 // over_pcie: an encode whose buffers are host memory (zero copy).
-int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uint64_t in_stripe,
-              uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
-              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
+int run_apply(const DevicePlanSet& ps, uint32_t nin, const Batch& b, const uint32_t* masks, uint32_t* bad,
               hipStream_t s, Completion* done = nullptr, bool over_pcie = false);
 
 // Reconstruct some over a strided in-place RS(10,4) batch (hec.h
 // hec_gpu_reconstruct_some_batch is the contract), asynchronously on s. ps:
 // the dense decode set (ensure_dense_decode first). wants == nullptr means
 // "all": run_apply's decode of any codec (nin inputs), launch for launch.
-int run_some(const DevicePlanSet& ps, uint32_t nin, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-             uint64_t len, uint32_t n_stripes, const uint32_t* masks, const uint32_t* wants, uint32_t* bad,
-             hipStream_t s);
+int run_some(const DevicePlanSet& ps, uint32_t nin, const Batch& b, const uint32_t* masks, const uint32_t* wants,
+             uint32_t* bad, hipStream_t s);
 // Prologue of the reconstruct-some batch entry points: nulls, the empty shard,
 // the codec, the layout. All before device work.
-inline int check_some_args(const hec_rs* rs, const void* shards, const void* masks, const void* wants,
-                           uint64_t stripe_stride, uint64_t shard_stride, uint64_t len, uint32_t n_stripes) {
-    if (!rs || !shards || !masks || !wants) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+inline int check_some_args(const hec_rs* rs, const Batch& b, const void* masks, const void* wants) {
+    if (!rs || !b.in.base || !masks || !wants) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (b.len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
     if (rs->k != 10 || rs->m != 4)
         return fail(HEC_ERR_INVALID_ARGUMENT, "batched reconstruct some is RS(10,4) only");
-    return check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, len, n_stripes);
+    return check_strided("shards", uint32_t(rs->n), b.in, b.len, b.n_stripes);
 }
 
-// Verify the stored parity of a strided batch against ps's encode plan (plan
-// 0), asynchronously on s: mismatch[0, n_stripes) (device words) are cleared
-// on s, then bit j of mismatch[st] is set when parity shard j of stripe st
-// differs within its len bytes; bad (optional device word) += stripes with a
-// non-zero word. len is the true shard length, never a rounded-up one: pad
-// bytes would be compared. At most 32 parity shards (the caller checks).
-int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint64_t data_stripe,
-               uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len,
-               uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s);
+// The scrub of a strided batch, asynchronously on s with no host
+// synchronisation and no allocation: pass 1 finds the bad stripes, pass 2
+// (optional) reads only those again.
+// Pass 1, masks == nullptr: the stored parity (b.out) is verified against gd's
+// encode plan over b.in, any codec with at most 32 parity shards (the caller
+// checks): bit j of words[st] is set when parity shard j of stripe st differs
+// within its len bytes. len is the true shard length, never a rounded-up one:
+// pad bytes would be compared. Pass 1 with masks: the masked check of an
+// in-place RS(10,4) batch over gd's check plans (ensure_check_plans first;
+// hec.h hec_gpu_verify_present_batch is the contract of words).
+// Pass 2 is RS(10,4) only (the caller checks the codec). Locate names the wrong
+// shards of each flagged stripe in suspects (hec.h hec_gpu_locate_corrupt_batch,
+// with masks hec_gpu_locate_corrupt_present_batch); pairs: two shards per
+// column (full masks only). Correct also fixes the columns it explains in
+// place (hec_gpu_correct_batch; with masks, in stripes with min_spares or more
+// spare shards: hec_gpu_correct_present_batch).
+enum class Pass2 { None, Locate, Correct };
+struct ScrubSpec {
+    const uint32_t* masks = nullptr;  // device words, one present mask per stripe
+    Pass2 pass2 = Pass2::None;
+    bool pairs = false;
+    uint32_t min_spares = 2;
+};
+// What a scrub writes, device memory all. words and (with a pass 2) suspects:
+// one word per stripe, cleared on s before the kernels OR bits in. The rest
+// are optional counters, accumulated: bad += stripes with a non-zero word,
+// unchecked += stripes without a spare shard (masked pass 1), left += stripes
+// pass 2 could not correct, corrected_bytes += bytes changed.
+struct ScrubOut {
+    uint32_t* words = nullptr;
+    uint32_t* suspects = nullptr;
+    uint32_t* bad = nullptr;
+    uint32_t* unchecked = nullptr;
+    uint32_t* left = nullptr;
+    unsigned long long* corrected_bytes = nullptr;
+};
+int run_scrub(const GeomDevice& gd, const Batch& b, const ScrubSpec& spec, const ScrubOut& out, hipStream_t s);
 // The verify entry points' extra argument checks, after check_batch_args.
 inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
     if (!mismatch) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
@@ -482,23 +540,6 @@ inline int check_verify_args(const hec_rs* rs, const void* mismatch) {
         return fail(HEC_ERR_INVALID_ARGUMENT, "verify needs at most 32 parity shards (one result bit each)");
     return HEC_OK;
 }
-
-// Locate, asynchronously on s with no host synchronisation and no allocation:
-// run_verify over gd's encode plan (mismatch[], bad: exactly its contract),
-// then suspects[0, n_stripes) are cleared on s and the locate kernel reads the
-// flagged stripes again (rs_kernels.hpp launch_locate; the result contract is
-// hec.h's). gd: the RS(10,4) geometry (the caller checks the codec). pairs:
-// pass 2 also names two shards per column (hec_gpu_locate_corrupt_pairs_batch).
-int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
-               const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
-               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s, bool pairs = false);
-// hec_gpu_correct_batch: run_locate with pass 2 fixing the columns it explains
-// in place (rs_kernels.hpp launch_correct). uncorrected, corrected_bytes:
-// optional device counters, accumulated.
-int run_correct(const GeomDevice& gd, uint8_t* data, uint64_t data_stripe, uint64_t data_shard, uint8_t* parity,
-                uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
-                uint32_t* suspects, uint32_t* bad, uint32_t* uncorrected, unsigned long long* corrected_bytes,
-                hipStream_t s, bool pairs);
 // The locate entry points' extra argument checks, after check_verify_args.
 inline int check_locate_args(const hec_rs* rs, const void* suspects) {
     if (!suspects) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
@@ -506,39 +547,18 @@ inline int check_locate_args(const hec_rs* rs, const void* suspects) {
         return fail(HEC_ERR_INVALID_ARGUMENT, "locate and repair are RS(10,4) only");
     return HEC_OK;
 }
-
-// Masked verify (degraded scrub; hec.h hec_gpu_verify_present_batch is the
-// contract), asynchronously on s: check[0, n_stripes) are cleared on s, then
-// the check kernels run over gd's check plans (ensure_check_plans first).
-int run_check(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* bad,
-              uint32_t* unchecked, hipStream_t s);
-// run_check, then suspects[0, n_stripes) are cleared on s and the masked
-// locate kernel reads the flagged stripes again.
-int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-                       uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* suspects,
-                       uint32_t* bad, uint32_t* unchecked, hipStream_t s);
-// hec_gpu_correct_present_batch: run_locate_present with pass 2 fixing, in
-// place, the columns it explains in stripes with min_spares or more spare
-// shards (rs_kernels.hpp launch_correct_present). uncorrected,
-// corrected_bytes: optional device counters, accumulated.
-int run_correct_present(const GeomDevice& gd, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-                        uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t min_spares, uint32_t* check,
-                        uint32_t* suspects, uint32_t* bad, uint32_t* unchecked, uint32_t* uncorrected,
-                        unsigned long long* corrected_bytes, hipStream_t s);
 inline int check_min_spares(uint32_t min_spares) {
     if (min_spares < 2 || min_spares > 4) return fail(HEC_ERR_INVALID_ARGUMENT, "min_spares must be 2, 3 or 4");
     return HEC_OK;
 }
 // Prologue of the masked entry points: nulls, the empty shard, the codec, the
 // layout. All before device work.
-inline int check_present_args(const hec_rs* rs, const void* shards, const void* masks, const void* check,
-                              uint64_t stripe_stride, uint64_t shard_stride, uint64_t len, uint32_t n_stripes) {
-    if (!rs || !shards || !masks || !check) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    if (len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+inline int check_present_args(const hec_rs* rs, const Batch& b, const void* masks, const void* check) {
+    if (!rs || !b.in.base || !masks || !check) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (b.len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
     if (rs->k != 10 || rs->m != 4)
         return fail(HEC_ERR_INVALID_ARGUMENT, "masked verify, locate and checked reconstruct are RS(10,4) only");
-    return check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, len, n_stripes);
+    return check_strided("shards", uint32_t(rs->n), b.in, b.len, b.n_stripes);
 }
 
 }  // namespace hec

@@ -103,6 +103,8 @@ static int encode_host(const hec_rs* rs, const uint8_t* const* data, uint8_t* co
     const uint64_t Lp = round_up(L, 256);
     if ((rc = sc->dbuf.reserve(size_t(Lp) * rs->n, kStagingFloor))) return rc;
     uint8_t* par = sc->dbuf + size_t(rs->k) * Lp;
+    // the stripe in device staging
+    const Batch dev = Batch::split_at(arena(sc->dbuf, 0, Lp), rs->k, round_up(L, 16), 1);
     auto dst_of = [&](int j) { return parity_out ? parity_out[j] : parity_vec->data() + size_t(j) * L; };
     if (uint64_t(rs->k) * L <= host_staging_max()) {
         // pinned staging: k shards packed -> one H2D, one D2H of the m parity
@@ -116,8 +118,8 @@ static int encode_host(const hec_rs* rs, const uint8_t* const* data, uint8_t* co
         uint8_t* zh = zero_copy_enabled() ? pinned_device_ptr(sc->hbuf) : nullptr;
         if (zh) {  // the kernel reads the packed shards and writes parity over PCIe
             Completion* done = uint64_t(rs->k) * L <= completion_flag_max() ? &sc->done : nullptr;
-            if ((rc = run_apply(gd->encode, uint32_t(rs->k), zh, 0, Lp, zh + size_t(rs->k) * Lp, 0, Lp,
-                                round_up(L, 16), 1, nullptr, nullptr, sc->stream, done)))
+            const Batch host = Batch::split_at(arena(zh, 0, Lp), rs->k, round_up(L, 16), 1);
+            if ((rc = run_apply(gd->encode, uint32_t(rs->k), host, nullptr, nullptr, sc->stream, done)))
                 return rc;
             if (done) {
                 if ((rc = done->wait(sc->stream))) return rc;
@@ -127,8 +129,7 @@ static int encode_host(const hec_rs* rs, const uint8_t* const* data, uint8_t* co
             }
         } else {
             HEC_HIP(hipMemcpyAsync(sc->dbuf, sc->hbuf, size_t(rs->k) * Lp, hipMemcpyHostToDevice, sc->stream));
-            if ((rc = run_apply(gd->encode, uint32_t(rs->k), sc->dbuf, 0, Lp, par, 0, Lp, round_up(L, 16), 1,
-                                nullptr, nullptr, sc->stream)))
+            if ((rc = run_apply(gd->encode, uint32_t(rs->k), dev, nullptr, nullptr, sc->stream)))
                 return rc;
             HEC_HIP(hipMemcpyAsync(hpar, par, size_t(rs->m - 1) * Lp + L, hipMemcpyDeviceToHost, sc->stream));
         }
@@ -140,8 +141,7 @@ static int encode_host(const hec_rs* rs, const uint8_t* const* data, uint8_t* co
     const StreamDrain drain{sc->stream};  // the D2H copies below write caller memory
     for (int i = 0; i < rs->k; ++i)
         HEC_HIP(hipMemcpyAsync(sc->dbuf + i * Lp, data[i], L, hipMemcpyHostToDevice, sc->stream));
-    if ((rc = run_apply(gd->encode, uint32_t(rs->k), sc->dbuf, 0, Lp, par, 0, Lp, round_up(L, 16), 1,
-                        nullptr, nullptr, sc->stream)))
+    if ((rc = run_apply(gd->encode, uint32_t(rs->k), dev, nullptr, nullptr, sc->stream)))
         return rc;
     for (int j = 0; j < rs->m; ++j)
         HEC_HIP(hipMemcpyAsync(dst_of(j), par + j * Lp, L, hipMemcpyDeviceToHost, sc->stream));
@@ -189,8 +189,8 @@ static int reconstruct_host(const hec_rs* rs, uint8_t* const* shards, const size
     const StreamDrain drain{sc->stream};  // the D2H copies below write caller memory
     for (uint32_t id : in_ids)
         HEC_HIP(hipMemcpyAsync(sc->dbuf + id * Lp, shards[id], L, hipMemcpyHostToDevice, sc->stream));
-    if ((rc = run_apply(sc->adhoc, uint32_t(rs->k), sc->dbuf, 0, Lp, sc->dbuf, 0, Lp, round_up(L, 16), 1,
-                        nullptr, nullptr, sc->stream)))
+    const Batch dev = Batch::in_place(arena(sc->dbuf, 0, Lp), round_up(L, 16), 1);
+    if ((rc = run_apply(sc->adhoc, uint32_t(rs->k), dev, nullptr, nullptr, sc->stream)))
         return rc;
     for (uint32_t id : out_ids)
         HEC_HIP(hipMemcpyAsync(shards[id], sc->dbuf + id * Lp, L, hipMemcpyDeviceToHost, sc->stream));

@@ -302,8 +302,9 @@ int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
                           uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes) {
     HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
-                                 parity_shard_stride, shard_len, n_stripes));
+    HEC_TRY(check_encode_strides(rs, Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
+                                                  arena(h_parity, parity_stripe_stride, parity_shard_stride),
+                                                  shard_len, n_stripes)));
     GeomDevice* gd;
     HEC_TRY(geom_device(rs, &gd));
     Lease<Pipeline> p;
@@ -314,9 +315,10 @@ int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
         host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
                          &zp)) {
         HEC_TRY(p->reserve(0, 1));
-        HEC_TRY(run_apply(gd->encode, uint32_t(k), zd, data_stripe_stride, data_shard_stride, zp,
-                          parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, nullptr, nullptr,
-                          p->streams[0], nullptr, /*over_pcie=*/true));
+        HEC_TRY(run_apply(gd->encode, uint32_t(k),
+                          Batch::split(arena(zd, data_stripe_stride, data_shard_stride),
+                                       arena(zp, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes),
+                          nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
         return HEC_OK;
     }
@@ -344,8 +346,8 @@ int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
                     });
                 },
                 [&](uint32_t c, int q) {
-                    return run_apply(gd->encode, uint32_t(k), zs[q], dstripe, Lp, zs[q] + uint64_t(k) * Lp, dstripe,
-                                     Lp, L16, c, nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true);
+                    return run_apply(gd->encode, uint32_t(k), Batch::split_at(arena(zs[q], dstripe, Lp), k, L16, c),
+                                     nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true);
                 },
                 [&](uint32_t s0, uint32_t c, int q) {
                     parallel_for(size_t(c) * m, uint64_t(c) * m * shard_len, [&](size_t t) {
@@ -367,8 +369,7 @@ int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
             return HEC_OK;
         },
         [&](uint32_t c, int q, uint32_t it) -> int {
-            uint8_t* d = p->slot[q];
-            HEC_TRY(run_apply(gd->encode, uint32_t(k), d, dstripe, Lp, d + uint64_t(k) * Lp, dstripe, Lp, L16, c,
+            HEC_TRY(run_apply(gd->encode, uint32_t(k), Batch::split_at(arena(p->slot[q], dstripe, Lp), k, L16, c),
                               nullptr, nullptr, p->streams[q]));
             if (int(it) == fail_at) return fail(HEC_ERR_HIP, "test hook: failure after chunk " + std::to_string(it));
             return HEC_OK;
@@ -388,7 +389,8 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
     HEC_TRY(check_batch_args(rs, h_shards, h_present_masks, shard_len));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes));
+    HEC_TRY(check_strided("shards", uint32_t(rs->n), arena(h_shards, stripe_stride, shard_stride), shard_len,
+                          n_stripes));
     return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks, nullptr,
                             n_bad_stripes);
 }
@@ -397,8 +399,8 @@ int hec_host_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* h_shards, uint6
                                     uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
                                     const uint32_t* h_present_masks, const uint32_t* h_want_masks,
                                     uint32_t* n_bad_stripes) {
-    HEC_TRY(check_some_args(rs, h_shards, h_present_masks, h_want_masks, stripe_stride, shard_stride, shard_len,
-                            n_stripes));
+    HEC_TRY(check_some_args(rs, Batch::in_place(arena(h_shards, stripe_stride, shard_stride), shard_len, n_stripes),
+                            h_present_masks, h_want_masks));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
     return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks,
@@ -436,7 +438,8 @@ int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stri
         if (wants)
             HEC_HIP(hipMemcpyAsync(p->want_dev[0], p->want_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
                                    p->streams[0]));
-        HEC_TRY(run_some(gd->decode_dense, uint32_t(k), zs, stripe_stride, shard_stride, shard_len, n_stripes, p->mask_dev[0],
+        HEC_TRY(run_some(gd->decode_dense, uint32_t(k),
+                         Batch::in_place(arena(zs, stripe_stride, shard_stride), shard_len, n_stripes), p->mask_dev[0],
                          wants ? p->want_dev[0].p : nullptr, nullptr, p->streams[0]));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
         if (n_bad_stripes) *n_bad_stripes = bad;
@@ -480,8 +483,8 @@ int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stri
                     });
                 },
                 [&](uint32_t c, int q) {
-                    return run_some(gd->decode_dense, uint32_t(k), hz[q], dstripe, Lp, L16, c, zm[q], zw[q], nullptr,
-                                    p->streams[0]);
+                    return run_some(gd->decode_dense, uint32_t(k), Batch::in_place(arena(hz[q], dstripe, Lp), L16, c),
+                                    zm[q], zw[q], nullptr, p->streams[0]);
                 },
                 [&](uint32_t s0, uint32_t c, int q) {
                     parallel_for(size_t(c) * n, uint64_t(c) * 4 * shard_len, [&](size_t t) {
@@ -521,8 +524,8 @@ int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stri
             return HEC_OK;
         },
         [&](uint32_t c, int q, uint32_t) {
-            return run_some(gd->decode_dense, uint32_t(k), p->slot[q], dstripe, Lp, L16, c, p->mask_dev[q],
-                            wants ? p->want_dev[q].p : nullptr, nullptr, p->streams[q]);
+            return run_some(gd->decode_dense, uint32_t(k), Batch::in_place(arena(p->slot[q], dstripe, Lp), L16, c),
+                            p->mask_dev[q], wants ? p->want_dev[q].p : nullptr, nullptr, p->streams[q]);
         },
         [&](uint32_t s0, uint32_t c, int q) -> int {
             for (uint32_t s = 0; s < c; ++s) {
@@ -552,13 +555,20 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
     HEC_TRY(check_verify_args(rs, h_mismatch));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
-                                 parity_shard_stride, shard_len, n_stripes));
+    HEC_TRY(check_encode_strides(rs, Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
+                                                  arena(h_parity, parity_stripe_stride, parity_shard_stride),
+                                                  shard_len, n_stripes)));
     GeomDevice* gd;
     HEC_TRY(geom_device(rs, &gd));
     Lease<Pipeline> p;
     HEC_TRY(lease_slot(p));
     const int k = rs->k, m = rs->m, n = rs->n;
+    // one verify launch into slot q's words: no count
+    auto verify = [&](const Batch& b, int q, hipStream_t s) {
+        ScrubOut out;
+        out.words = p->mask_dev[q];
+        return run_scrub(*gd, b, ScrubSpec{}, out, s);
+    };
     auto finish = [&](int rc) {
         if (!rc && n_bad_stripes)
             for (uint32_t s = 0; s < n_stripes; ++s) *n_bad_stripes += h_mismatch[s] ? 1u : 0u;
@@ -574,9 +584,9 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
         host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
                          &zp)) {
         HEC_TRY(p->reserve(0, n_stripes));
-        HEC_TRY(run_verify(gd->encode, uint32_t(k), zd, data_stripe_stride, data_shard_stride, zp,
-                           parity_stripe_stride, parity_shard_stride, shard_len, n_stripes, p->mask_dev[0], nullptr,
-                           p->streams[0]));
+        HEC_TRY(verify(Batch::split(arena(zd, data_stripe_stride, data_shard_stride),
+                                    arena(zp, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes),
+                       0, p->streams[0]));
         HEC_HIP(hipMemcpyAsync(p->mask_host[0], p->mask_dev[0], size_t(n_stripes) * 4, hipMemcpyDeviceToHost,
                                p->streams[0]));
         HEC_HIP(hipStreamSynchronize(p->streams[0]));
@@ -608,8 +618,7 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
                     });
                 },
                 [&](uint32_t c, int q) -> int {
-                    HEC_TRY(run_verify(gd->encode, uint32_t(k), zs[q], dstripe, Lp, zs[q] + uint64_t(k) * Lp, dstripe,
-                                       Lp, shard_len, c, p->mask_dev[q], nullptr, p->streams[0]));
+                    HEC_TRY(verify(Batch::split_at(arena(zs[q], dstripe, Lp), k, shard_len, c), q, p->streams[0]));
                     HEC_HIP(hipMemcpyAsync(p->mask_host[q], p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
                                            p->streams[0]));
                     return HEC_OK;
@@ -631,9 +640,7 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
             return HEC_OK;
         },
         [&](uint32_t c, int q, uint32_t) {
-            uint8_t* d = p->slot[q];
-            return run_verify(gd->encode, uint32_t(k), d, dstripe, Lp, d + uint64_t(k) * Lp, dstripe, Lp, shard_len, c,
-                              p->mask_dev[q], nullptr, p->streams[q]);
+            return verify(Batch::split_at(arena(p->slot[q], dstripe, Lp), k, shard_len, c), q, p->streams[q]);
         },
         [&](uint32_t s0, uint32_t c, int q) -> int {  // D2H of the words only
             HEC_HIP(hipMemcpyAsync(h_mismatch + s0, p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
@@ -647,8 +654,9 @@ int hec_host_encode_batch_multi(const hec_rs_t* rs, const int* devices, size_t n
                                 uint64_t parity_stripe_stride, uint64_t parity_shard_stride, uint64_t shard_len,
                                 uint32_t n_stripes) {
     HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
-    HEC_TRY(check_encode_strides(rs, data_stripe_stride, data_shard_stride, parity_stripe_stride,
-                                 parity_shard_stride, shard_len, n_stripes));
+    HEC_TRY(check_encode_strides(rs, Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
+                                                  arena(h_parity, parity_stripe_stride, parity_shard_stride),
+                                                  shard_len, n_stripes)));
     return run_device_ranges(devices, n_devices, n_stripes, [&](uint32_t s0, uint32_t c, size_t) {
         return hec_host_encode_batch(rs, h_data + s0 * data_stripe_stride, data_stripe_stride, data_shard_stride,
                                      h_parity + s0 * parity_stripe_stride, parity_stripe_stride, parity_shard_stride,
@@ -661,7 +669,8 @@ int hec_host_reconstruct_batch_multi(const hec_rs_t* rs, const int* devices, siz
                                      uint32_t n_stripes, const uint32_t* h_present_masks, uint32_t* n_bad_stripes) {
     HEC_TRY(check_batch_args(rs, h_shards, h_present_masks, shard_len));
     if (n_bad_stripes) *n_bad_stripes = 0;
-    HEC_TRY(check_strided("shards", uint32_t(rs->n), stripe_stride, shard_stride, shard_len, n_stripes));
+    HEC_TRY(check_strided("shards", uint32_t(rs->n), arena(h_shards, stripe_stride, shard_stride), shard_len,
+                          n_stripes));
     std::vector<uint32_t> bad(std::max<size_t>(n_devices, 1), 0);
     int rc = run_device_ranges(devices, n_devices, n_stripes, [&](uint32_t s0, uint32_t c, size_t r) {
         return hec_host_reconstruct_batch(rs, h_shards + s0 * stripe_stride, stripe_stride, shard_stride, shard_len, c,

@@ -403,142 +403,126 @@ struct RaggedMeta {
     }
 };
 
-// Device-resident ragged batches: stripe descriptors come from the host, data
-// stays in HBM. wants (a decode only): hec_gpu_reconstruct_some_ragged's want
-// words, nullptr for the other calls.
-int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool decode,
-               uint32_t* d_bad, hipStream_t stream, const uint32_t* wants = nullptr) {
-    const RaggedOp op = decode ? RaggedOp::Decode : RaggedOp::Encode;
-    const bool bitslice = (n == 0 || descs) && ragged_pick(descs, n, decode).bitslice;  // a null list fails below
-    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
-    uint64_t n_blocks;
-    HEC_TRY(ragged_check_args(rs, d_base, descs, n, op, chunk_bytes, &n_blocks, wants));
-    if (n == 0) return HEC_OK;
-    GeomDevice* gd;
-    int rc = geom_device(rs, &gd);
-    if (rc) return rc;
+// What every device-resident ragged call does before its first launch and
+// after its last: stripe descriptors come from the host, data stays in HBM.
+struct RaggedCall {
+    bool bitslice = false;
+    uint64_t n_blocks = 0, n_decode = 0;  // map entries of the call's own pair, and of a decode's second pair
+    GeomDevice* gd = nullptr;             // stays null for an empty batch: nothing to launch or record
     RaggedMeta meta;
-    if ((rc = meta.reserve(n, n_blocks))) return rc;
-    if (decode && (rc = ensure_dense_decode(rs, gd, meta.lease.sc->stream))) return rc;
-    RaggedArgs ra{};
-    if ((rc = meta.upload(descs, n, op, chunk_bytes, d_base, n_blocks, stream, ra, nullptr, 0, wants))) return rc;
-    ra.tabs = decode ? gd->decode_dense.tabs : gd->encode.tabs;
-    ra.lut = decode ? gd->decode_dense.lut : nullptr;
-    ra.bad_count = d_bad;
-    if (n_blocks == 0) {  // every stripe already complete (upstream no-op)
+    // The pick, the argument checks (all before device work; a null descriptor
+    // list fails inside ragged_check_args, after the caller's own null checks),
+    // the geometry's plan sets (every one before any launch: their first call
+    // uploads and waits) and the metadata upload; ra: the arguments of the
+    // call's own pair. wants: a reconstruct some's want words. decode2: the
+    // arguments of a second, decode pair (the corrected reconstruct).
+    int begin(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, RaggedOp op,
+              hipStream_t stream, RaggedArgs& ra, const uint32_t* wants = nullptr, RaggedArgs* decode2 = nullptr,
+              uint32_t min_spares = 2) {
+        const bool scrub = op == RaggedOp::Scrub;
+        bitslice = (n == 0 || descs) &&  // a null list fails below
+                   (scrub ? ragged_scrub_pick(descs, n) : ragged_pick(descs, n, op == RaggedOp::Decode)).bitslice;
+        const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
+        HEC_TRY(ragged_check_args(rs, d_base, descs, n, op, chunk_bytes, &n_blocks, wants));
+        if (decode2) HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Decode, 4096, &n_decode));
+        HEC_TRY(check_min_spares(min_spares));
+        if (n == 0) return HEC_OK;
+        GeomDevice* g;
+        HEC_TRY(geom_device(rs, &g));
+        // a scrub's plan sets upload on the caller's stream, before a metadata slot is taken
+        if (scrub) HEC_TRY(ensure_check_plans(rs, g, stream));
+        if (decode2) HEC_TRY(ensure_dense_decode(rs, g, stream));
+        HEC_TRY(meta.reserve(n, n_blocks, decode2 != nullptr, n_decode));
+        // a plain decode's on the slot's own stream
+        if (op == RaggedOp::Decode) HEC_TRY(ensure_dense_decode(rs, g, meta.lease.sc->stream));
+        HEC_TRY(meta.upload(descs, n, op, chunk_bytes, d_base, n_blocks, stream, ra, decode2, n_decode, wants));
+        gd = g;
+        return HEC_OK;
+    }
+    // After the last kernel that reads the slot, launched or not.
+    int end(hipStream_t stream) {
         HEC_HIP(hipEventRecord(meta.slot->free, stream));
         return HEC_OK;
     }
-    if (bitslice)
+};
+
+// The ragged encode, reconstruct and (wants) reconstruct some: one launch.
+int gpu_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool decode,
+               uint32_t* d_bad, hipStream_t stream, const uint32_t* wants = nullptr) {
+    RaggedCall c;
+    RaggedArgs ra{};
+    HEC_TRY(c.begin(rs, d_base, descs, n, decode ? RaggedOp::Decode : RaggedOp::Encode, stream, ra, wants));
+    if (!c.gd) return HEC_OK;
+    ra.tabs = decode ? c.gd->decode_dense.tabs : c.gd->encode.tabs;
+    ra.lut = decode ? c.gd->decode_dense.lut : nullptr;
+    ra.bad_count = d_bad;
+    if (c.n_blocks == 0) return c.end(stream);  // every stripe already complete (upstream no-op)
+    if (c.bitslice)
         HEC_HIP(launch_rs104_bs_ragged(ra, stream));
     else if (wants)
         HEC_HIP(launch_rs104_ragged_some(ra, stream));
     else
         HEC_HIP(launch_rs104_ragged(ra, decode, stream));
-    HEC_HIP(hipEventRecord(meta.slot->free, stream));
-    return HEC_OK;
+    return c.end(stream);
 }
 
-// hec_gpu_verify_ragged (d_suspects == nullptr, locate == false) and
-// hec_gpu_locate_corrupt_ragged: the masked verify, and its locate pass over
-// the flagged stripes, on a ragged batch. Pass 2 walks pass 1's map.
-int gpu_ragged_scrub(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, bool locate,
-                     uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad, uint32_t* d_unchecked,
-                     hipStream_t stream) {
-    if (!d_check || (locate && !d_suspects)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    const bool bitslice = (n == 0 || descs) && ragged_scrub_pick(descs, n).bitslice;  // a null list fails below
-    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
-    uint64_t n_blocks;
-    HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Scrub, chunk_bytes, &n_blocks));
-    if (n == 0) return HEC_OK;
-    uint32_t unchecked = 0;  // stripes without a spare shard: no map entry, never read
-    for (uint32_t j = 0; j < n; ++j) unchecked += __builtin_popcount(descs[j].present_mask & 0x3FFFu) <= 10;
-    GeomDevice* gd;
-    HEC_TRY(geom_device(rs, &gd));
-    HEC_TRY(ensure_check_plans(rs, gd, stream));  // before any launch: its first call uploads and waits
-    RaggedMeta meta;
-    HEC_TRY(meta.reserve(n, n_blocks));
-    RaggedScrubArgs v{};
-    HEC_TRY(meta.upload(descs, n, RaggedOp::Scrub, chunk_bytes, const_cast<uint8_t*>(d_base) /* only read */,
-                        n_blocks, stream, v.a));
-    v.a.tabs = gd->check.tabs;
-    v.a.lut = gd->check.lut;
-    v.a.bad_count = d_bad;
-    v.check = d_check;
-    v.suspects = d_suspects;
-    v.ratio_tabs = gd->check_ratio.tabs;
-    // the kernels only ever OR bits in: stale words must not leak through
-    HEC_HIP(hipMemsetAsync(d_check, 0, size_t(n) * 4, stream));
-    if (locate) HEC_HIP(hipMemsetAsync(d_suspects, 0, size_t(n) * 4, stream));
-    if (unchecked && d_unchecked) HEC_HIP(launch_add_word(d_unchecked, unchecked, stream));
-    if (n_blocks) {
-        HEC_HIP(launch_ragged_check(v, bitslice, stream));
-        // pass 2: only the stripes pass 1 flagged are read again (the counts are pass 1's)
-        if (locate) HEC_HIP(launch_ragged_locate(v, bitslice, stream));
-    }
-    HEC_HIP(hipEventRecord(meta.slot->free, stream));
-    return HEC_OK;
-}
+// The decode after a corrected ragged scrub: use[] = the masks it decodes
+// from, bad += the decode's count (stripes with fewer than ten shards),
+// unrepaired += the dirty stripes that keep their holes.
+struct RaggedDecodeTail {
+    uint32_t* use = nullptr;
+    uint32_t* bad = nullptr;
+    uint32_t* unrepaired = nullptr;
+};
 
-// hec_gpu_correct_ragged (d_use == nullptr, reconstruct == false) and
-// hec_gpu_reconstruct_corrected_ragged: gpu_ragged_scrub's locate with pass 2
-// fixing in place; the reconstruct then sets the use masks and decodes the
-// stripes whose survivors are consistent, from a map of its own in the same
-// metadata slot. d_bad: the scrub's count for the correct, the decode's for
-// the reconstruct; d_left: uncorrected, or unrepaired.
-int gpu_ragged_correct(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n,
-                       uint32_t min_spares, bool reconstruct, uint32_t* d_check, uint32_t* d_suspects,
-                       uint32_t* d_use, uint32_t* d_bad, uint32_t* d_unchecked, uint32_t* d_left,
-                       unsigned long long* d_corrected_bytes, hipStream_t stream) {
-    if (!d_check || !d_suspects || (reconstruct && !d_use)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    const bool bitslice = (n == 0 || descs) && ragged_scrub_pick(descs, n).bitslice;  // a null list fails below
-    const uint32_t chunk_bytes = bitslice ? kBsChunk : 4096;
-    uint64_t n_blocks, n_decode = 0;
-    HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Scrub, chunk_bytes, &n_blocks));
-    if (reconstruct) HEC_TRY(ragged_check_args(rs, d_base, descs, n, RaggedOp::Decode, 4096, &n_decode));
-    HEC_TRY(check_min_spares(min_spares));
-    if (n == 0) return HEC_OK;
-    uint32_t unchecked = 0;  // stripes without a spare shard: no scrub map entry, never read
-    for (uint32_t j = 0; j < n; ++j) unchecked += __builtin_popcount(descs[j].present_mask & 0x3FFFu) <= 10;
-    GeomDevice* gd;
-    HEC_TRY(geom_device(rs, &gd));
-    // every plan set before any launch: their first call uploads and waits
-    HEC_TRY(ensure_check_plans(rs, gd, stream));
-    if (reconstruct) HEC_TRY(ensure_dense_decode(rs, gd, stream));
-    RaggedMeta meta;
-    HEC_TRY(meta.reserve(n, n_blocks, reconstruct, n_decode));
+// The ragged scrubs (hec.h has each call's contract): the masked check of every
+// stripe over its own length and mask, out as run_scrub's; pass 2 walks pass
+// 1's map over the flagged stripes, naming (Locate) or also fixing in place
+// (Correct) what it explains. tail (hec_gpu_reconstruct_corrected_ragged): the
+// use masks are then set and the stripes whose survivors are consistent
+// decoded, from a map of its own in the same metadata slot.
+int gpu_ragged_scrub(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n, Pass2 pass2,
+                     uint32_t min_spares, const ScrubOut& out, const RaggedDecodeTail* tail, hipStream_t stream) {
+    if (!out.words || (pass2 != Pass2::None && !out.suspects) || (tail && !tail->use))
+        return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    RaggedCall c;
     RaggedCorrectArgs v{};
     RaggedArgs dec{};
-    HEC_TRY(meta.upload(descs, n, RaggedOp::Scrub, chunk_bytes, d_base, n_blocks, stream, v.a,
-                        reconstruct ? &dec : nullptr, n_decode));
-    v.a.tabs = gd->check.tabs;
-    v.a.lut = gd->check.lut;
-    v.a.bad_count = reconstruct ? nullptr : d_bad;
-    v.check = d_check;
-    v.suspects = d_suspects;
-    v.ratio_tabs = gd->check_ratio.tabs;
-    v.fix_tabs = gd->check_fix.tabs;
-    v.min_spares = min_spares;
-    v.uncorrected = reconstruct ? nullptr : d_left;
-    v.corrected_bytes = d_corrected_bytes;
+    HEC_TRY(c.begin(rs, d_base, descs, n, RaggedOp::Scrub, stream, v.a, nullptr, tail ? &dec : nullptr, min_spares));
+    if (!c.gd) return HEC_OK;
+    uint32_t unchecked = 0;  // stripes without a spare shard: no scrub map entry, never read
+    for (uint32_t j = 0; j < n; ++j) unchecked += __builtin_popcount(descs[j].present_mask & 0x3FFFu) <= 10;
+    v.a.tabs = c.gd->check.tabs;
+    v.a.lut = c.gd->check.lut;
+    v.a.bad_count = out.bad;
+    v.check = out.words;
+    v.suspects = out.suspects;
+    v.ratio_tabs = c.gd->check_ratio.tabs;
+    if (pass2 == Pass2::Correct) {
+        v.fix_tabs = c.gd->check_fix.tabs;
+        v.min_spares = min_spares;
+        v.uncorrected = out.left;
+        v.corrected_bytes = out.corrected_bytes;
+    }
     // the kernels only ever OR bits in: stale words must not leak through
-    HEC_HIP(hipMemsetAsync(d_check, 0, size_t(n) * 4, stream));
-    HEC_HIP(hipMemsetAsync(d_suspects, 0, size_t(n) * 4, stream));
-    if (unchecked && d_unchecked) HEC_HIP(launch_add_word(d_unchecked, unchecked, stream));
-    if (n_blocks) {
-        HEC_HIP(launch_ragged_check(v, bitslice, stream));
-        HEC_HIP(launch_ragged_correct(v, bitslice, stream));
+    HEC_HIP(hipMemsetAsync(out.words, 0, size_t(n) * 4, stream));
+    if (pass2 != Pass2::None) HEC_HIP(hipMemsetAsync(out.suspects, 0, size_t(n) * 4, stream));
+    if (unchecked && out.unchecked) HEC_HIP(launch_add_word(out.unchecked, unchecked, stream));
+    if (c.n_blocks) {
+        HEC_HIP(launch_ragged_check(v, c.bitslice, stream));
+        // pass 2: only the stripes pass 1 flagged are read again (the counts are pass 1's)
+        if (pass2 == Pass2::Locate) HEC_HIP(launch_ragged_locate(v, c.bitslice, stream));
+        if (pass2 == Pass2::Correct) HEC_HIP(launch_ragged_correct(v, c.bitslice, stream));
     }
-    if (reconstruct) {
-        HEC_HIP(launch_ragged_use_masks_corrected(v.a.items, const_cast<RaggedItem*>(dec.items), d_check, d_suspects,
-                                                  d_use, d_left, min_spares, n, stream));
-        dec.tabs = gd->decode_dense.tabs;
-        dec.lut = gd->decode_dense.lut;
-        dec.bad_count = d_bad;
-        if (n_decode) HEC_HIP(launch_rs104_ragged(dec, true, stream));
+    if (tail) {
+        HEC_HIP(launch_ragged_use_masks_corrected(v.a.items, const_cast<RaggedItem*>(dec.items), out.words,
+                                                  out.suspects, tail->use, tail->unrepaired, min_spares, n, stream));
+        dec.tabs = c.gd->decode_dense.tabs;
+        dec.lut = c.gd->decode_dense.lut;
+        dec.bad_count = tail->bad;
+        if (c.n_decode) HEC_HIP(launch_rs104_ragged(dec, true, stream));
     }
-    HEC_HIP(hipEventRecord(meta.slot->free, stream));
-    return HEC_OK;
+    return c.end(stream);
 }
 
 }  // namespace
@@ -550,18 +534,31 @@ int hec_gpu_correct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe
                            uint32_t min_spares, uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad_stripes,
                            uint32_t* d_unchecked, uint32_t* d_uncorrected, unsigned long long* d_corrected_bytes,
                            void* stream) {
-    return hec::gpu_ragged_correct(rs, d_base, descs, n_stripes, min_spares, false, d_check, d_suspects, nullptr,
-                                   d_bad_stripes, d_unchecked, d_uncorrected, d_corrected_bytes,
-                                   static_cast<hipStream_t>(stream));
+    hec::ScrubOut out;
+    out.words = d_check;
+    out.suspects = d_suspects;
+    out.bad = d_bad_stripes;
+    out.unchecked = d_unchecked;
+    out.left = d_uncorrected;
+    out.corrected_bytes = d_corrected_bytes;
+    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, hec::Pass2::Correct, min_spares, out, nullptr,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int hec_gpu_reconstruct_corrected_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs,
                                          uint32_t n_stripes, uint32_t min_spares, uint32_t* d_check,
                                          uint32_t* d_suspects, uint32_t* d_use_masks, uint32_t* d_bad_stripes,
                                          uint32_t* d_unrepaired, unsigned long long* d_corrected_bytes, void* stream) {
-    return hec::gpu_ragged_correct(rs, d_base, descs, n_stripes, min_spares, true, d_check, d_suspects, d_use_masks,
-                                   d_bad_stripes, nullptr, d_unrepaired, d_corrected_bytes,
-                                   static_cast<hipStream_t>(stream));
+    hec::ScrubOut out;  // the counts are the decode's
+    out.words = d_check;
+    out.suspects = d_suspects;
+    out.corrected_bytes = d_corrected_bytes;
+    hec::RaggedDecodeTail tail;
+    tail.use = d_use_masks;
+    tail.bad = d_bad_stripes;
+    tail.unrepaired = d_unrepaired;
+    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, hec::Pass2::Correct, min_spares, out, &tail,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int hec_gpu_encode_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n_stripes,
@@ -586,15 +583,24 @@ int hec_gpu_reconstruct_some_ragged(const hec_rs_t* rs, uint8_t* d_base, const h
 int hec_gpu_verify_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
                           uint32_t n_stripes, uint32_t* d_check, uint32_t* d_bad_stripes, uint32_t* d_unchecked,
                           void* stream) {
-    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, false, d_check, nullptr, d_bad_stripes, d_unchecked,
-                                 static_cast<hipStream_t>(stream));
+    hec::ScrubOut out;
+    out.words = d_check;
+    out.bad = d_bad_stripes;
+    out.unchecked = d_unchecked;
+    return hec::gpu_ragged_scrub(rs, const_cast<uint8_t*>(d_base) /* only read */, descs, n_stripes, hec::Pass2::None,
+                                 2, out, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int hec_gpu_locate_corrupt_ragged(const hec_rs_t* rs, const uint8_t* d_base, const hec_stripe_desc* descs,
                                   uint32_t n_stripes, uint32_t* d_check, uint32_t* d_suspects,
                                   uint32_t* d_bad_stripes, uint32_t* d_unchecked, void* stream) {
-    return hec::gpu_ragged_scrub(rs, d_base, descs, n_stripes, true, d_check, d_suspects, d_bad_stripes, d_unchecked,
-                                 static_cast<hipStream_t>(stream));
+    hec::ScrubOut out;
+    out.words = d_check;
+    out.suspects = d_suspects;
+    out.bad = d_bad_stripes;
+    out.unchecked = d_unchecked;
+    return hec::gpu_ragged_scrub(rs, const_cast<uint8_t*>(d_base) /* only read */, descs, n_stripes,
+                                 hec::Pass2::Locate, 2, out, nullptr, static_cast<hipStream_t>(stream));
 }
 
 const char* hec_ragged_scrub_kernel_name(const hec_stripe_desc* descs, uint32_t n_stripes) {

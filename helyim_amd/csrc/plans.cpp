@@ -131,6 +131,7 @@ int geom_device(const hec_rs* rs, GeomDevice** out) {
         return HEC_OK;
     }
     std::unique_ptr<GeomDevice> gd(new GeomDevice());
+    gd->k = uint32_t(rs->k);
     const bool is104 = rs->k == 10 && rs->m == 4;
     HostPlans hp;
     if (is104) hp.fixed_rows = 4;
@@ -322,188 +323,110 @@ int ensure_check_plans(const hec_rs* rs, GeomDevice* gd, hipStream_t s) {
 }
 
 // The coding arguments every strided launch shares, from a plan set and the
-// batch's layout. Returns whether every base and stride is 16-byte aligned.
-static bool fill_args(ApplyArgs& a, const DevicePlanSet& ps, const uint8_t* in_base, uint64_t in_stripe,
-                      uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard, uint64_t len,
-                      uint32_t n_stripes, uint32_t* bad) {
-    a.in_base = in_base;
-    a.in_stripe = in_stripe;
-    a.in_shard = in_shard;
-    a.out_base = out_base;
-    a.out_stripe = out_stripe;
-    a.out_shard = out_shard;
-    a.len = len;
-    a.n_stripes = n_stripes;
+// batch's layout.
+static void fill_args(ApplyArgs& a, const DevicePlanSet& ps, const Batch& b, uint32_t* bad) {
+    a.in_base = b.in.base;
+    a.in_stripe = b.in.stripe;
+    a.in_shard = b.in.shard;
+    a.out_base = b.out.base;
+    a.out_stripe = b.out.stripe;
+    a.out_shard = b.out.shard;
+    a.len = b.len;
+    a.n_stripes = b.n_stripes;
     a.plans = ps.plans;
     a.tabs = ps.tabs;
     a.idx = ps.idx;
     a.bad_count = bad;
     a.fast104 = ps.fast104 ? 1u : 0u;
-    const uint64_t align = uint64_t(reinterpret_cast<uintptr_t>(in_base)) | in_stripe | in_shard |
-                           uint64_t(reinterpret_cast<uintptr_t>(out_base)) | out_stripe | out_shard;
-    return (align % 16) == 0;
 }
-
-int run_apply(const DevicePlanSet& ps, uint32_t nin, const uint8_t* in_base, uint64_t in_stripe,
-              uint64_t in_shard, uint8_t* out_base, uint64_t out_stripe, uint64_t out_shard,
-              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* bad,
-              hipStream_t s, Completion* done, bool over_pcie) {
-    ApplyArgs a{};
-    if (done) HEC_TRY(done->arm(s, &a.done_count, &a.done_flag, &a.done_seq));
-    const bool aligned =
-        fill_args(a, ps, in_base, in_stripe, in_shard, out_base, out_stripe, out_shard, len, n_stripes, bad);
+// ... of a launch that picks each stripe's plan from its mask word.
+static void fill_mask_args(ApplyArgs& a, const DevicePlanSet& ps, const Batch& b, const uint32_t* masks,
+                           uint32_t* bad) {
+    fill_args(a, ps, b, bad);
     a.masks = masks;
     a.lut = ps.lut;
     a.mask_limit = ps.lut_bits ? ((1u << ps.lut_bits) - 1u) : 0u;
+}
+
+int run_apply(const DevicePlanSet& ps, uint32_t nin, const Batch& b, const uint32_t* masks, uint32_t* bad,
+              hipStream_t s, Completion* done, bool over_pcie) {
+    ApplyArgs a{};
+    if (done) HEC_TRY(done->arm(s, &a.done_count, &a.done_flag, &a.done_seq));
+    fill_mask_args(a, ps, b, masks, bad);
     if (masks && !ps.lut) return fail(HEC_ERR_INVALID_ARGUMENT, "per-stripe masks need a decode LUT");
-    HEC_HIP(launch_apply(a, int(nin), aligned, over_pcie && !masks, s));
+    HEC_HIP(launch_apply(a, int(nin), b.aligned(), over_pcie && !masks, s));
     return HEC_OK;
 }
 
-int run_some(const DevicePlanSet& ps, uint32_t nin, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-             uint64_t len, uint32_t n_stripes, const uint32_t* masks, const uint32_t* wants, uint32_t* bad,
-             hipStream_t s) {
-    if (!wants)  // "all": the decode's own launches
-        return run_apply(ps, nin, shards, stripe_stride, shard_stride, shards, stripe_stride, shard_stride, len,
-                         n_stripes, masks, bad, s);
+int run_some(const DevicePlanSet& ps, uint32_t nin, const Batch& b, const uint32_t* masks, const uint32_t* wants,
+             uint32_t* bad, hipStream_t s) {
+    if (!wants) return run_apply(ps, nin, b, masks, bad, s);  // "all": the decode's own launches
     SomeArgs v{};
-    const bool aligned =
-        fill_args(v.a, ps, shards, stripe_stride, shard_stride, shards, stripe_stride, shard_stride, len, n_stripes, bad);
-    v.a.masks = masks;
-    v.a.lut = ps.lut;
-    v.a.mask_limit = (1u << ps.lut_bits) - 1u;
+    fill_mask_args(v.a, ps, b, masks, bad);
     v.wants = wants;
     if (!ps.lut || !ps.fast104) return fail(HEC_ERR_INVALID_ARGUMENT, "reconstruct some needs the RS(10,4) decode LUT");
-    HEC_HIP(launch_some(v, aligned, s));
+    HEC_HIP(launch_some(v, b.aligned(), s));
     return HEC_OK;
 }
 
-// The arguments of a verify or locate launch over ps's encode plan; returns
-// fill_args' alignment.
-static bool fill_verify_args(VerifyArgs& v, const DevicePlanSet& ps, const uint8_t* data, uint64_t data_stripe,
-                             uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe,
-                             uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
-                             uint32_t* bad) {
-    v.mismatch = mismatch;
-    return fill_args(v.a, ps, data, data_stripe, data_shard, const_cast<uint8_t*>(parity) /* only read */,
-                     parity_stripe, parity_shard, len, n_stripes, bad);
+// Pass 2 of a scrub, the part every kernel argument type shares: pass 1's
+// arguments with its counters nulled (the counts are pass 1's), the words to
+// name the shards in, cleared, and the locate's constants.
+template <typename Args>
+static int second_pass(Args& v, const DevicePlanSet& ratio, const Batch& b, const ScrubOut& out, hipStream_t s) {
+    v.a.bad_count = nullptr;
+    v.suspects = out.suspects;
+    v.ratio_tabs = ratio.tabs;
+    HEC_HIP(hipMemsetAsync(out.suspects, 0, size_t(b.n_stripes) * 4, s));
+    return HEC_OK;
+}
+// ... and what a correcting pass 2 adds.
+template <typename Args>
+static void correct_pass(Args& v, const DevicePlanSet& fix, const ScrubOut& out) {
+    v.fix_tabs = fix.tabs;
+    v.uncorrected = out.left;
+    v.corrected_bytes = out.corrected_bytes;
 }
 
-int run_verify(const DevicePlanSet& ps, uint32_t nin, const uint8_t* data, uint64_t data_stripe,
-               uint64_t data_shard, const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len,
-               uint32_t n_stripes, uint32_t* mismatch, uint32_t* bad, hipStream_t s) {
-    if (n_stripes == 0) return HEC_OK;
-    VerifyArgs v{};
-    const bool aligned = fill_verify_args(v, ps, data, data_stripe, data_shard, parity, parity_stripe, parity_shard,
-                                          len, n_stripes, mismatch, bad);
+int run_scrub(const GeomDevice& gd, const Batch& b, const ScrubSpec& spec, const ScrubOut& out, hipStream_t s) {
+    if (b.n_stripes == 0) return HEC_OK;
+    const bool aligned = b.aligned();
     // the kernels only ever OR bits in: stale words must not leak through
-    HEC_HIP(hipMemsetAsync(mismatch, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_verify(v, int(nin), aligned, s));
-    return HEC_OK;
-}
-
-int run_locate(const GeomDevice& gd, const uint8_t* data, uint64_t data_stripe, uint64_t data_shard,
-               const uint8_t* parity, uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes,
-               uint32_t* mismatch, uint32_t* suspects, uint32_t* bad, hipStream_t s, bool pairs) {
-    if (n_stripes == 0) return HEC_OK;
-    // pass 1: the scrub itself (bit-sliced where it applies), at its own rate
-    HEC_TRY(run_verify(gd.encode, 10, data, data_stripe, data_shard, parity, parity_stripe, parity_shard, len,
-                       n_stripes, mismatch, bad, s));
-    // pass 2: only the stripes pass 1 flagged are read again (bad is pass 1's)
-    VerifyArgs v{};
-    const bool aligned = fill_verify_args(v, gd.encode, data, data_stripe, data_shard, parity, parity_stripe,
-                                          parity_shard, len, n_stripes, mismatch, nullptr);
-    v.suspects = suspects;
-    v.ratio_tabs = gd.locate.tabs;
-    v.pair_tabs = gd.locate_pairs.tabs;
-    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_locate(v, aligned, pairs, s));
-    return HEC_OK;
-}
-
-int run_correct(const GeomDevice& gd, uint8_t* data, uint64_t data_stripe, uint64_t data_shard, uint8_t* parity,
-                uint64_t parity_stripe, uint64_t parity_shard, uint64_t len, uint32_t n_stripes, uint32_t* mismatch,
-                uint32_t* suspects, uint32_t* bad, uint32_t* uncorrected, unsigned long long* corrected_bytes,
-                hipStream_t s, bool pairs) {
-    if (n_stripes == 0) return HEC_OK;
-    // pass 1: run_locate's
-    HEC_TRY(run_verify(gd.encode, 10, data, data_stripe, data_shard, parity, parity_stripe, parity_shard, len,
-                       n_stripes, mismatch, bad, s));
-    // pass 2: the locate's walk, fixing what it explains
-    CorrectArgs c{};
-    const bool aligned = fill_verify_args(c, gd.encode, data, data_stripe, data_shard, parity, parity_stripe,
-                                          parity_shard, len, n_stripes, mismatch, nullptr);
-    c.suspects = suspects;
-    c.ratio_tabs = gd.locate.tabs;
-    c.pair_tabs = gd.locate_pairs.tabs;
-    c.fix_tabs = gd.correct.tabs;
-    c.uncorrected = uncorrected;
-    c.corrected_bytes = corrected_bytes;
-    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_correct(c, aligned, pairs, s));
-    return HEC_OK;
-}
-
-// The arguments of a masked verify or locate launch over gd's check plans;
-// returns fill_args' alignment.
-static bool fill_check_args(CheckArgs& v, const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride,
-                            uint64_t shard_stride, uint64_t len, uint32_t n_stripes, const uint32_t* masks,
-                            uint32_t* check, uint32_t* bad, uint32_t* unchecked) {
-    // out_* = in_*: the check kernels only read; the masked correct writes through in_base (fix_shard)
-    v.check = check;
-    v.unchecked = unchecked;
-    v.a.masks = masks;
-    v.a.lut = gd.check.lut;
-    v.a.mask_limit = (1u << gd.check.lut_bits) - 1u;
-    return fill_args(v.a, gd.check, shards, stripe_stride, shard_stride, const_cast<uint8_t*>(shards) /* only read */,
-                     stripe_stride, shard_stride, len, n_stripes, bad);
-}
-
-int run_check(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-              uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* bad,
-              uint32_t* unchecked, hipStream_t s) {
-    if (n_stripes == 0) return HEC_OK;
-    CheckArgs v{};
-    const bool aligned =
-        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked);
-    HEC_HIP(hipMemsetAsync(check, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_check(v, aligned, s));
-    return HEC_OK;
-}
-
-int run_locate_present(const GeomDevice& gd, const uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-                       uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t* check, uint32_t* suspects,
-                       uint32_t* bad, uint32_t* unchecked, hipStream_t s) {
-    if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(run_check(gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked, s));
-    // pass 2: only the stripes pass 1 flagged are read again (the counts are pass 1's)
-    CheckArgs v{};
-    const bool aligned =
-        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, nullptr, nullptr);
-    v.suspects = suspects;
-    v.ratio_tabs = gd.check_ratio.tabs;
-    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
-    HEC_HIP(launch_locate_present(v, aligned, s));
-    return HEC_OK;
-}
-
-int run_correct_present(const GeomDevice& gd, uint8_t* shards, uint64_t stripe_stride, uint64_t shard_stride,
-                        uint64_t len, uint32_t n_stripes, const uint32_t* masks, uint32_t min_spares, uint32_t* check,
-                        uint32_t* suspects, uint32_t* bad, uint32_t* unchecked, uint32_t* uncorrected,
-                        unsigned long long* corrected_bytes, hipStream_t s) {
-    if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(run_check(gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, bad, unchecked, s));
-    // pass 2: the masked locate's walk, fixing what it explains
+    HEC_HIP(hipMemsetAsync(out.words, 0, size_t(b.n_stripes) * 4, s));
+    if (!spec.masks) {
+        // pass 1: the verify (bit-sliced where it applies), at its own rate
+        CorrectArgs v{};
+        fill_args(v.a, gd.encode, b, out.bad);
+        v.mismatch = out.words;
+        HEC_HIP(launch_verify(v, int(gd.k), aligned, s));
+        if (spec.pass2 == Pass2::None) return HEC_OK;
+        // pass 2: only the stripes pass 1 flagged are read again
+        HEC_TRY(second_pass(v, gd.locate, b, out, s));
+        v.pair_tabs = gd.locate_pairs.tabs;
+        if (spec.pass2 == Pass2::Locate) {
+            HEC_HIP(launch_locate(v, aligned, spec.pairs, s));
+            return HEC_OK;
+        }
+        correct_pass(v, gd.correct, out);
+        HEC_HIP(launch_correct(v, aligned, spec.pairs, s));
+        return HEC_OK;
+    }
+    // pass 1: the masked check. out = in: the check kernels only read, the
+    // masked correct writes through in_base (fix_shard)
     CorrectPresentArgs v{};
-    const bool aligned =
-        fill_check_args(v, gd, shards, stripe_stride, shard_stride, len, n_stripes, masks, check, nullptr, nullptr);
-    v.suspects = suspects;
-    v.ratio_tabs = gd.check_ratio.tabs;
-    v.fix_tabs = gd.check_fix.tabs;
-    v.uncorrected = uncorrected;
-    v.corrected_bytes = corrected_bytes;
-    v.min_spares = min_spares;
-    HEC_HIP(hipMemsetAsync(suspects, 0, size_t(n_stripes) * 4, s));
+    fill_mask_args(v.a, gd.check, b, spec.masks, out.bad);
+    v.check = out.words;
+    v.unchecked = out.unchecked;
+    HEC_HIP(launch_check(v, aligned, s));
+    if (spec.pass2 == Pass2::None) return HEC_OK;
+    HEC_TRY(second_pass(v, gd.check_ratio, b, out, s));
+    v.unchecked = nullptr;
+    if (spec.pass2 == Pass2::Locate) {
+        HEC_HIP(launch_locate_present(v, aligned, s));
+        return HEC_OK;
+    }
+    correct_pass(v, gd.check_fix, out);
+    v.min_spares = spec.min_spares;
     HEC_HIP(launch_correct_present(v, aligned, s));
     return HEC_OK;
 }

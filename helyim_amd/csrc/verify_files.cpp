@@ -78,23 +78,24 @@ void read_exact(ErrorSlot& err, int fd, const std::string& name, uint8_t* dst, u
 
 enum class ScrubMode { Verify, Locate, LocatePairs, Correct, CorrectPairs };
 
-// mode Locate / LocatePairs: every launch is run_locate instead of run_verify
-// (LocatePairs: with the pair search), a chunk's suspects words follow its
-// mismatch words at +per_chunk in the same result buffers, and the bad blocks
-// go to sus[] with their suspects word instead of to bad[].
-// mode Correct / CorrectPairs: the files are opened for writing, every launch
-// is run_correct, and once a chunk's event has fired each bad block's rows of
-// the shards its suspects word names are written back at the block's offset:
-// the only bytes of any file that are written. Every file written is
-// fdatasync'ed once before the return.
+// Every launch is one run_scrub whose ScrubSpec is fixed before the chunk loop.
+// mode Locate / LocatePairs: pass 2 is the locate (LocatePairs: with the pair
+// search), a chunk's suspects words follow its mismatch words at +per_chunk in
+// the same result buffers, and the bad blocks go to sus[] with their suspects
+// word instead of to bad[].
+// mode Correct / CorrectPairs: the files are opened for writing, pass 2 is the
+// correct, and once a chunk's event has fired each bad block's rows of the
+// shards its suspects word names are written back at the block's offset: the
+// only bytes of any file that are written. Every file written is fdatasync'ed
+// once before the return.
 // degraded (with locate): a missing file is an erased shard, not an error; its
-// row of a slot is neither read into nor read by the kernels, every launch is
-// run_locate_present with the volume's present mask, and the words are the
-// masked calls' (shard-index bits). *present_out (optional) = the files found.
+// row of a slot is neither read into nor read by the kernels, pass 1 is the
+// masked check with the volume's present mask, and the words are the masked
+// calls' (shard-index bits). *present_out (optional) = the files found.
 // degraded with mode Correct (hec_correct_ec_files_present): the present files
-// are opened for writing and every launch is run_correct_present with
-// min_spares, a named row is written back as above (the kernel names present
-// shards only); a volume with fewer spare files is only located.
+// are opened for writing and pass 2 is the masked correct with min_spares, a
+// named row is written back as above (the kernel names present shards only);
+// a volume with fewer spare files is only located.
 int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode, hec_scrub_bad* bad,
                          hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks,
                          bool degraded = false, uint32_t* present_out = nullptr, uint32_t min_spares = 2) {
@@ -160,6 +161,12 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
     uint8_t* zs[2] = {pinned_device_ptr(sc->slot[0]), pinned_device_ptr(sc->slot[1])};
     if (!zs[0] || !zs[1]) return fail(HEC_ERR_HIP, "pinned scrub slots are not addressable by the device");
 
+    ScrubSpec spec;  // of every launch
+    if (degraded) spec.masks = sc->masks_dev;
+    spec.pass2 = correct ? Pass2::Correct : locate ? Pass2::Locate : Pass2::None;
+    spec.pairs = pairs;
+    spec.min_spares = min_spares;
+
     const uint64_t total_blocks = (size + block - 1) / block;
     const uint64_t n_chunks = (size + cols - 1) / cols;
     size_t found = 0;
@@ -214,24 +221,13 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
         uint32_t* wd = sc->words_dev[q];
         // n blocks of blen bytes from column `first` of the slot on
         auto launch = [&](uint64_t first, uint64_t blen, uint64_t n) -> int {
-            const uint8_t* d = zs[q] + first * block;
-            const uint8_t* p = d + uint64_t(K) * pitch;
-            if (degraded && correct)
-                return run_correct_present(*gd, zs[q] + first * block, block, pitch, blen, uint32_t(n), sc->masks_dev,
-                                           min_spares, wd + first, wd + per_chunk + first, nullptr, nullptr, nullptr,
-                                           nullptr, sc->stream);
-            if (degraded)
-                return run_locate_present(*gd, d, block, pitch, blen, uint32_t(n), sc->masks_dev, wd + first,
-                                          wd + per_chunk + first, nullptr, nullptr, sc->stream);
-            if (correct)
-                return run_correct(*gd, zs[q] + first * block, block, pitch, zs[q] + first * block + uint64_t(K) * pitch,
-                                   block, pitch, blen, uint32_t(n), wd + first, wd + per_chunk + first, nullptr, nullptr,
-                                   nullptr, sc->stream, pairs);
-            if (locate)
-                return run_locate(*gd, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first,
-                                  wd + per_chunk + first, nullptr, sc->stream, pairs);
-            return run_verify(gd->encode, K, d, block, pitch, p, block, pitch, blen, uint32_t(n), wd + first, nullptr,
-                              sc->stream);
+            const Strided rows = arena(zs[q] + first * block, block, pitch);
+            ScrubOut out;
+            out.words = wd + first;
+            if (locate) out.suspects = wd + per_chunk + first;
+            const Batch b = degraded ? Batch::in_place(rows, blen, uint32_t(n))
+                                     : Batch::split_at(rows, K, blen, uint32_t(n));
+            return run_scrub(*gd, b, spec, out, sc->stream);
         };
         if (full) HEC_TRY(launch(0, block, full));
         if (tail) HEC_TRY(launch(full, tail, 1));
@@ -256,73 +252,59 @@ int verify_ec_files_impl(const std::string& base, uint64_t block, ScrubMode mode
 
 extern "C" {
 
-// The two entry points' shared prologue; has_out: the result array is there.
-static int scrub_args(const char* base_filename, uint64_t block_size, bool has_out, size_t cap, size_t* n_bad,
-                      uint64_t* n_blocks, uint64_t* block) {
+// The entry points' shared prologue, then the walk. Exactly one of bad and sus
+// may be there: the result array.
+static int scrub_files(const char* base_filename, uint64_t block_size, hec::ScrubMode mode, hec_scrub_bad* bad,
+                       hec_scrub_suspect* sus, size_t cap, size_t* n_bad, uint64_t* n_blocks, bool degraded = false,
+                       uint32_t* present_mask = nullptr, uint32_t min_spares = 2) {
+    if (present_mask) *present_mask = 0;
     if (n_bad) *n_bad = 0;
     if (n_blocks) *n_blocks = 0;
-    if (!base_filename || (cap && !has_out)) return hec::fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
-    *block = block_size ? block_size : HEC_SMALL_BLOCK_SIZE;
-    if (*block % 4096 != 0 || *block > 0xFFFFF000ull)
+    if (!base_filename || (cap && !bad && !sus)) return hec::fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t block = block_size ? block_size : HEC_SMALL_BLOCK_SIZE;
+    if (block % 4096 != 0 || block > 0xFFFFF000ull)
         return hec::fail(HEC_ERR_INVALID_ARGUMENT, "block_size must be a multiple of 4096 below 4 GiB");
-    return HEC_OK;
+    HEC_TRY(hec::check_min_spares(min_spares));
+    return hec::verify_ec_files_impl(base_filename, block, mode, bad, sus, cap, n_bad, n_blocks, degraded, present_mask,
+                                     min_spares);
 }
 
 int hec_verify_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_bad* bad, size_t cap, size_t* n_bad,
                         uint64_t* n_blocks) {
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Verify, bad, nullptr, cap, n_bad, n_blocks);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::Verify, bad, nullptr, cap, n_bad, n_blocks);
 }
 
 int hec_locate_corrupt_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                                 size_t* n_bad, uint64_t* n_blocks) {
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks);
 }
 
 int hec_locate_corrupt_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
                                       size_t cap, size_t* n_bad, uint64_t* n_blocks) {
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::LocatePairs, nullptr, bad, cap, n_bad,
-                                     n_blocks);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::LocatePairs, nullptr, bad, cap, n_bad, n_blocks);
 }
 
 int hec_correct_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                          size_t* n_bad, uint64_t* n_blocks) {
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks);
 }
 
 int hec_correct_pairs_ec_files(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad, size_t cap,
                                size_t* n_bad, uint64_t* n_blocks) {
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::CorrectPairs, nullptr, bad, cap, n_bad,
-                                     n_blocks);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::CorrectPairs, nullptr, bad, cap, n_bad, n_blocks);
 }
 
 int hec_locate_corrupt_ec_files_present(const char* base_filename, uint64_t block_size, hec_scrub_suspect* bad,
                                         size_t cap, size_t* n_bad, uint64_t* n_blocks, uint32_t* present_mask) {
-    if (present_mask) *present_mask = 0;
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks,
-                                     true, present_mask);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::Locate, nullptr, bad, cap, n_bad, n_blocks, true,
+                       present_mask);
 }
 
 int hec_correct_ec_files_present(const char* base_filename, uint64_t block_size, uint32_t min_spares,
                                  hec_scrub_suspect* bad, size_t cap, size_t* n_bad, uint64_t* n_blocks,
                                  uint32_t* present_mask) {
-    if (present_mask) *present_mask = 0;
-    uint64_t block;
-    HEC_TRY(scrub_args(base_filename, block_size, bad != nullptr, cap, n_bad, n_blocks, &block));
-    HEC_TRY(hec::check_min_spares(min_spares));
-    return hec::verify_ec_files_impl(base_filename, block, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks,
-                                     true, present_mask, min_spares);
+    return scrub_files(base_filename, block_size, hec::ScrubMode::Correct, nullptr, bad, cap, n_bad, n_blocks, true,
+                       present_mask, min_spares);
 }
 
 }  // extern "C"
