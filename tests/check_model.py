@@ -43,6 +43,17 @@ def check_matrix(mask: int):
     return B, E, A, H
 
 
+def syndrome_of(mask: int, errors: dict) -> list:
+    """errors: {shard: value} in one byte column -> the r syndrome bytes."""
+    B, E, _, H = check_matrix(mask)
+    ids = B + E
+    syn = [0] * len(E)
+    for c, v in errors.items():
+        for j in range(len(E)):
+            syn[j] ^= O.gf_mul(v, int(H[j, ids.index(c)]))
+    return syn
+
+
 def syndrome(stripe: np.ndarray, mask: int) -> np.ndarray:
     """stripe [14, L] uint8 -> syn [r, L]; only present shards are looked at."""
     B, E, A, _ = check_matrix(int(mask) & ALL)

@@ -24,6 +24,19 @@ MUL = PM.MUL
 _VALUES = np.arange(1, 256, dtype=np.uint8)
 
 
+def codewords(S, L, seed) -> np.ndarray:
+    """[S, 14, L] seeded codewords, the parity from the model's own tables."""
+    rng = np.random.default_rng(seed)
+    data = rng.integers(0, 256, (S, 10, L), dtype=np.uint8)
+    out = np.zeros((S, 14, L), dtype=np.uint8)
+    out[:, :10] = data
+    for j in range(4):
+        for i in range(10):
+            out[:, 10 + j] ^= MUL[int(M.P[j, i])][data[:, i]]
+    assert not M.syndromes(out).any()
+    return out
+
+
 def _pack(syn) -> np.ndarray:
     """syn [4, n] uint8 -> [n] uint32 keys."""
     syn = np.asarray(syn, dtype=np.uint8).astype(np.uint32)

@@ -22,6 +22,7 @@ shard, a skipped stripe or a parity slot ``data_only`` must leave alone.
 from __future__ import annotations
 
 import bisect
+import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -247,3 +248,77 @@ def assert_unchanged(before: Sequence[np.ndarray], actual: Sequence[np.ndarray],
                      note=None) -> None:
     """A call that failed by contract: no byte of any arena differs."""
     assert_footprint(Plan(before, stripes), actual, note)
+
+
+# ---- device and host arenas of the GPU suites -------------------------------------
+def present_of(masks, n):
+    return [present_flags(mk, n) for mk in masks]
+
+
+def to_device(arenas):
+    import torch
+    devs = [torch.from_numpy(a).cuda() for a in arenas]
+    assert all(d.data_ptr() % 256 == 0 for d in devs)  # the layout's own offsets decide the alignment
+    return devs
+
+
+def to_host(devs):
+    import torch
+    torch.cuda.synchronize()
+    return [d.cpu().numpy() for d in devs]
+
+
+def stream_ptr():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+HOST_ARENA = 3 << 20
+HOST_PATHS = ("pinned zero copy", "pageable pinned slots", "pageable copy2d")
+
+
+class HostArenas:
+    """Two pinned and two pageable buffers (64-byte aligned) the host cases
+    carve their arenas from."""
+
+    def __init__(self):
+        import torch
+        self.pinned_t = [torch.empty(HOST_ARENA, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.pinned = [t.numpy() for t in self.pinned_t]
+        self.raw = [np.empty(HOST_ARENA + 64, np.uint8) for _ in range(2)]
+        self.pageable = [r[(-r.ctypes.data) % 64:][:HOST_ARENA] for r in self.raw]
+
+    def take(self, path, stripes, rng):
+        """Arenas for `stripes` on this path, filled with seeded random bytes;
+        -> (live arenas the call works on, a copy of them before the call)."""
+        bufs = self.pinned if path == HOST_PATHS[0] else self.pageable
+        live = []
+        for sz, b in zip(arena_sizes(stripes), bufs):
+            assert sz <= HOST_ARENA and b.ctypes.data % 64 == 0
+            b[:sz] = random_arena(sz, rng)
+            live.append(b[:sz])
+        return live, [a.copy() for a in live]
+
+
+class host_path:
+    """Select one of the three host paths; the setting is restored on exit."""
+
+    def __init__(self, path):
+        self.path = path
+
+    def __enter__(self):
+        import helyim_amd as H
+        assert H.lib.hec_set_host_zero_copy(0 if self.path == HOST_PATHS[2] else 1) == 0
+        return self
+
+    def __exit__(self, *exc):
+        import helyim_amd as H
+        H.lib.hec_set_host_zero_copy(1)
+
+    def check_view(self, live, lay):
+        """The pinned arena is coded zero-copy, everything else is staged."""
+        import helyim_amd as H
+        z = ctypes.c_int(7)
+        p = live[lay.arena].ctypes.data + lay.base
+        assert H.lib.hec_host_zero_copy_view(p, lay.end - lay.base, ctypes.byref(z)) == 0
+        assert z.value == (1 if self.path == HOST_PATHS[0] else 0), (self.path, lay)

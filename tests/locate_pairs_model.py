@@ -102,3 +102,13 @@ def syndrome_of(errors) -> list:
         for r in range(R):
             syn[r] ^= O.gf_mul(v, int(H[r, c]))
     return syn
+
+
+def unexplained_triple(rng):
+    """{shard: value} of three wrong shards in one column for which the model
+    says bit 31 (nearly all do), and one it explains by a pair is skipped."""
+    while True:
+        group = sorted(int(c) for c in rng.choice(14, 3, replace=False))
+        errors = {c: int(rng.integers(1, 256)) for c in group}
+        if column_word(syndrome_of(errors)) == UNEXPLAINED:
+            return errors

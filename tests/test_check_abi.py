@@ -6,25 +6,23 @@ import os
 
 import pytest
 
+from abi_util import EC_SHARD_SIZE, EMPTY_SHARD, INVALID_ARGUMENT, L, SHARD_NOT_FOUND, TOO_FEW_PRESENT, call, volume
 from conftest import ROOT
 
-INVALID_ARGUMENT, EMPTY_SHARD, TOO_FEW_PRESENT, EC_SHARD_SIZE, SHARD_NOT_FOUND = 66, 11, 10, 34, 49
-P, L = 0x1000, 4096
 NAMES = ("hec_gpu_verify_present_batch", "hec_gpu_locate_corrupt_present_batch",
          "hec_gpu_reconstruct_checked_batch", "hec_check_kernel_name", "hec_locate_corrupt_ec_files_present")
 
 
-def gpu_check(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, res=P):
-    return lib.hec_gpu_verify_present_batch(rs, shards, st, sh, length, n, masks, res, None, None, None)
+def gpu_check(lib, rs, **args):
+    return call("hec_gpu_verify_present_batch", rs, **args)
 
 
-def gpu_locate(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, res=P, sus=P):
-    return lib.hec_gpu_locate_corrupt_present_batch(rs, shards, st, sh, length, n, masks, res, sus, None, None, None)
+def gpu_locate(lib, rs, **args):
+    return call("hec_gpu_locate_corrupt_present_batch", rs, **args)
 
 
-def gpu_checked(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, res=P, sus=P, use=P):
-    return lib.hec_gpu_reconstruct_checked_batch(rs, shards, st, sh, length, n, masks, res, sus, use, None, None,
-                                                 None)
+def gpu_checked(lib, rs, **args):
+    return call("hec_gpu_reconstruct_checked_batch", rs, **args)
 
 
 CALLS = {gpu_check: ("shards", "masks", "res"), gpu_locate: ("shards", "masks", "res", "sus"),
@@ -90,11 +88,6 @@ def test_other_codecs_are_refused_with_the_reason(k, m):
         assert call(H.lib, rs.handle, st=(k + m) * L, n=0) == INVALID_ARGUMENT
 
 
-def write_files(base, present, size=700, sizes=None):
-    for i in present:
-        open(str(base) + ".ec%02d" % i, "wb").write(b"\0" * (sizes or {}).get(i, size))
-
-
 def test_file_checks_need_no_device(tmp_path):
     import helyim_amd as H
     lib = H.lib
@@ -112,7 +105,7 @@ def test_file_checks_need_no_device(tmp_path):
     # 7 and 10 present: too few, the detail gives the count
     for count, ids in ((7, (0, 2, 3, 5, 8, 11, 13)), (10, range(2, 12))):
         base = tmp_path / ("few%d" % count)
-        write_files(base, ids)
+        volume(base, present=ids)
         assert locate(base) == TOO_FEW_PRESENT, count
         assert ("%d of 14" % count) in H._lib.last_detail()
         assert present.value == sum(1 << i for i in ids)
@@ -121,7 +114,7 @@ def test_file_checks_need_no_device(tmp_path):
         assert isinstance(e.value.inner, H.TooFewShardsPresent)
     # unequal sizes among the present files (the absent ones say nothing)
     base = tmp_path / "v"
-    write_files(base, [i for i in range(14) if i not in (0, 9)], sizes={6: 650})
+    volume(base, present=[i for i in range(14) if i not in (0, 9)], sizes={6: 650})
     for block in (1000, 4095, 4096 + 512):
         assert locate(base, block) == INVALID_ARGUMENT, block
     assert locate(base) == EC_SHARD_SIZE
@@ -137,7 +130,7 @@ def test_file_checks_need_no_device(tmp_path):
     # all-empty files: nothing to check, with 14 and with 11 present
     for name, ids in (("e14", range(14)), ("e11", (0, 1, 2, 4, 5, 6, 7, 9, 10, 12, 13))):
         empty = tmp_path / name
-        write_files(empty, ids, size=0)
+        volume(empty, size=0, present=ids)
         assert H.locate_corrupt_ec_files_present(str(empty), 4096) == (0, 0, [], sum(1 << i for i in ids))
     # the full-volume entry point still refuses a missing file
     assert lib.hec_locate_corrupt_ec_files(str(tmp_path / "e11").encode(), 4096, None, 0, None, None) == SHARD_NOT_FOUND

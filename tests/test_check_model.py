@@ -15,17 +15,6 @@ from oracle import rs_oracle as O
 DEGRADED = C.checkable_masks((1, 2, 3))
 
 
-def syndrome_of(mask, errors):
-    """errors: {shard: value} in one byte column -> the r syndrome bytes."""
-    B, E, _, H = C.check_matrix(mask)
-    ids = B + E
-    syn = [0] * len(E)
-    for c, v in errors.items():
-        for j in range(len(E)):
-            syn[j] ^= O.gf_mul(v, int(H[j, ids.index(c)]))
-    return syn
-
-
 def test_there_are_469_degraded_masks_and_470_checkable():
     assert len(DEGRADED) == 469 and len(C.checkable_masks()) == 470
     assert [len([m for m in DEGRADED if bin(m).count("1") == p]) for p in (11, 12, 13)] == [364, 91, 14]
@@ -76,11 +65,11 @@ def test_one_wrong_shard_is_named_for_every_mask():
         B, E, _, _ = C.check_matrix(m)
         for c in B + E:
             v = int(rng.integers(1, 256))
-            assert C.column_word(syndrome_of(m, {c: v}), m) == 1 << c, (hex(m), c, v)
+            assert C.column_word(C.syndrome_of(m, {c: v}), m) == 1 << c, (hex(m), c, v)
     for m in C.checkable_masks((1,))[::7]:
         B, E, _, _ = C.check_matrix(m)
         for c in B + E:
-            assert C.column_word(syndrome_of(m, {c: 1}), m) == C.UNEXPLAINED
+            assert C.column_word(C.syndrome_of(m, {c: 1}), m) == C.UNEXPLAINED
 
 
 def test_pairs_with_three_spares_are_unexplained():
@@ -91,7 +80,7 @@ def test_pairs_with_three_spares_are_unexplained():
         B, E, _, _ = C.check_matrix(m)
         for pair in itertools.combinations(B + E, 2):
             errors = {c: int(rng.integers(1, 256)) for c in pair}
-            assert C.column_word(syndrome_of(m, errors), m) == C.UNEXPLAINED, (hex(m), errors)
+            assert C.column_word(C.syndrome_of(m, errors), m) == C.UNEXPLAINED, (hex(m), errors)
 
 
 def test_pairs_with_two_spares_can_name_an_intact_shard():
@@ -105,7 +94,7 @@ def test_pairs_with_two_spares_can_name_an_intact_shard():
     v = O.mat_mul(O.mat_invert(sub), np.array(target, dtype=np.uint8).reshape(2, 1))
     errors = {B[0]: int(v[0, 0]), B[1]: int(v[1, 0])}
     assert all(errors.values())
-    assert C.column_word(syndrome_of(m, errors), m) == 1 << B[2]
+    assert C.column_word(C.syndrome_of(m, errors), m) == 1 << B[2]
 
 
 def test_use_masks_rule():

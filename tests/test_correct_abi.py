@@ -9,29 +9,16 @@ import stat
 
 import pytest
 
+from abi_util import (EC_SHARD_SIZE, EMPTY_SHARD, INVALID_ARGUMENT, IO, NO_DEVICE, SHARD_NOT_FOUND, L, P, c_parameters, call,
+                      has_gpu, volume)
 from conftest import ROOT
-from test_abi import has_gpu
 
-INVALID_ARGUMENT, EMPTY_SHARD, EC_SHARD_SIZE, SHARD_NOT_FOUND, NO_DEVICE = 66, 11, 34, 49, 65
-P, L = 0x1000, 4096
 BATCH = ("hec_gpu_correct_batch", "hec_gpu_correct_pairs_batch")
 FILES = ("hec_correct_ec_files", "hec_correct_pairs_ec_files")
 
 
-def gpu_correct(lib, name, rs, data=P, ds=14 * L, dsh=L, par=P + 10 * L, ps=14 * L, psh=L, length=L, n=2, res=P,
-                sus=P):
-    return getattr(lib, name)(rs, data, ds, dsh, par, ps, psh, length, n, res, sus, None, None, None, None)
-
-
-def c_parameters(header, name):
-    m = re.search(r"\b%s\s*\(([^;{]*?)\)\s*;" % name, header, flags=re.S)
-    assert m, name
-    return [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
-
-
-def codes():
-    hdr = open(os.path.join(ROOT, "include", "hec.h")).read()
-    return dict((k, int(v)) for k, v in re.findall(r"\b(HEC_(?:OK|ERR_\w+))\s*=\s*(\d+)", hdr))
+def gpu_correct(lib, name, rs, **args):
+    return call(name, rs, **args)
 
 
 def test_symbols_and_signatures():
@@ -102,11 +89,6 @@ def test_no_device_is_an_error_not_a_fallback():
         assert gpu_correct(H.lib, name, rs.handle) == NO_DEVICE, name
 
 
-def volume(base, size=700, odd=None):
-    for i in range(14):
-        open(str(base) + ".ec%02d" % i, "wb").write(b"\0" * (odd[1] if odd and i == odd[0] else size))
-
-
 @pytest.mark.parametrize("pairs", [False, True])
 def test_file_checks_need_no_device(tmp_path, pairs):
     import helyim_amd as H
@@ -150,7 +132,7 @@ def test_a_shard_that_cannot_be_opened_for_writing_is_an_io_error(tmp_path, pair
     is changed."""
     import errno
     import helyim_amd as H
-    io = codes()["HEC_ERR_IO"]
+    io = IO
     call = H.lib.hec_correct_pairs_ec_files if pairs else H.lib.hec_correct_ec_files
     base = tmp_path / "d"
     volume(base)

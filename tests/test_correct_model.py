@@ -17,20 +17,8 @@ UNEXPLAINED = CM.UNEXPLAINED
 VALUES = (0x01, 0xFF, 0x80, 0x5A)
 
 
-def codewords(S, L, seed):
-    rng = np.random.default_rng(seed)
-    data = rng.integers(0, 256, (S, 10, L), dtype=np.uint8)
-    out = np.zeros((S, 14, L), dtype=np.uint8)
-    out[:, :10] = data
-    for j in range(4):
-        for i in range(10):
-            out[:, 10 + j] ^= PM.MUL[int(M.P[j, i])][data[:, i]]
-    assert not M.syndromes(out).any()
-    return out
-
-
 def test_every_single_shard_is_restored():
-    good = codewords(14, 33, 1)
+    good = CM.codewords(14, 33, 1)
     bad = good.copy()
     for c in range(14):
         for n, v in enumerate(VALUES):
@@ -44,7 +32,7 @@ def test_every_single_shard_is_restored():
 
 
 def test_every_pair_is_restored():
-    good = codewords(91, 19, 2)
+    good = CM.codewords(91, 19, 2)
     bad = good.copy()
     rng = np.random.default_rng(22)
     for s, (a, b) in enumerate(PM.PAIRS):
@@ -61,7 +49,7 @@ def test_every_pair_is_restored():
 
 
 def test_single_form_leaves_two_and_three_wrong_shards_and_fixes_the_rest():
-    good = codewords(3, 40, 3)
+    good = CM.codewords(3, 40, 3)
     bad = good.copy()
     bad[0, 0, 7] ^= 0x11
     bad[0, 13, 7] ^= 0xFF   # two wrong in column 7
@@ -78,7 +66,7 @@ def test_single_form_leaves_two_and_three_wrong_shards_and_fixes_the_rest():
 
 
 def test_second_application_is_the_identity():
-    good = codewords(4, 25, 4)
+    good = CM.codewords(4, 25, 4)
     bad = good.copy()
     bad[0, 3, 1] ^= 0x44
     bad[1, 0, 24] ^= 0x10

@@ -10,25 +10,20 @@ import stat
 
 import pytest
 
+from abi_util import (EC_SHARD_SIZE, EMPTY_SHARD, INVALID_ARGUMENT, IO, NO_DEVICE, SHARD_NOT_FOUND, TOO_FEW_PRESENT, L,
+                      c_parameters, call, has_gpu, volume)
 from conftest import ROOT
-from test_abi import has_gpu
-from test_check_abi import write_files
-from test_correct_abi import c_parameters, codes
 
-INVALID_ARGUMENT, EMPTY_SHARD, TOO_FEW_PRESENT, EC_SHARD_SIZE, SHARD_NOT_FOUND, NO_DEVICE = 66, 11, 10, 34, 49, 65
-P, L = 0x1000, 4096
 BATCH = ("hec_gpu_correct_present_batch", "hec_gpu_reconstruct_corrected_batch")
 FILES = "hec_correct_ec_files_present"
 
 
-def gpu_correct(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, spares=2, res=P, sus=P):
-    return lib.hec_gpu_correct_present_batch(rs, shards, st, sh, length, n, masks, spares, res, sus, None, None,
-                                             None, None, None)
+def gpu_correct(lib, rs, **args):
+    return call("hec_gpu_correct_present_batch", rs, **args)
 
 
-def gpu_corrected(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, spares=2, res=P, sus=P, use=P):
-    return lib.hec_gpu_reconstruct_corrected_batch(rs, shards, st, sh, length, n, masks, spares, res, sus, use, None,
-                                                   None, None, None)
+def gpu_corrected(lib, rs, **args):
+    return call("hec_gpu_reconstruct_corrected_batch", rs, **args)
 
 
 CALLS = {gpu_correct: ("shards", "masks", "res", "sus"), gpu_corrected: ("shards", "masks", "res", "sus", "use")}
@@ -121,7 +116,7 @@ def test_file_checks_need_no_device(tmp_path):
         H.correct_ec_files_present(str(tmp_path / "missing"))
     for count, ids in ((1, (6,)), (7, (0, 2, 3, 5, 8, 11, 13)), (10, range(2, 12))):
         base = tmp_path / ("few%d" % count)
-        write_files(base, ids)
+        volume(base, present=ids)
         assert correct(base) == TOO_FEW_PRESENT, count
         assert ("%d of 14" % count) in H._lib.last_detail()
         assert present.value == sum(1 << i for i in ids)
@@ -129,7 +124,7 @@ def test_file_checks_need_no_device(tmp_path):
             H.correct_ec_files_present(str(base), 4096)
         assert isinstance(e.value.inner, H.TooFewShardsPresent)
     base = tmp_path / "v"
-    write_files(base, [i for i in range(14) if i not in (0, 9)], sizes={6: 650})
+    volume(base, present=[i for i in range(14) if i not in (0, 9)], sizes={6: 650})
     for block in (1000, 4095, 4096 + 512):
         assert correct(base, block) == INVALID_ARGUMENT, block
     for spares in (0, 1, 5):
@@ -147,7 +142,7 @@ def test_file_checks_need_no_device(tmp_path):
         H.correct_ec_files_present(str(base), 4096, cap=-1)
     for name, ids in (("e14", range(14)), ("e11", (0, 1, 2, 4, 5, 6, 7, 9, 10, 12, 13))):
         empty = tmp_path / name
-        write_files(empty, ids, size=0)
+        volume(empty, size=0, present=ids)
         assert H.correct_ec_files_present(str(empty), 4096) == (0, 0, [], sum(1 << i for i in ids))
 
 
@@ -157,10 +152,10 @@ def test_a_present_file_that_cannot_be_opened_for_writing_is_an_io_error(tmp_pat
     Both give HEC_ERR_IO with the errno before any device work; a missing file
     (ENOENT) is an erased shard."""
     import helyim_amd as H
-    io = codes()["HEC_ERR_IO"]
+    io = IO
     call = H.lib.hec_correct_ec_files_present
     base = tmp_path / "d"
-    write_files(base, [i for i in range(14) if i != 2])
+    volume(base, present=[i for i in range(14) if i != 2])
     os.remove(str(base) + ".ec05")
     os.mkdir(str(base) + ".ec05")
     assert call(str(base).encode(), 4096, 2, None, 0, None, None, None) == io
@@ -168,7 +163,7 @@ def test_a_present_file_that_cannot_be_opened_for_writing_is_an_io_error(tmp_pat
     with pytest.raises(H.Io):
         H.correct_ec_files_present(str(base), 4096)
     base = tmp_path / "r"
-    write_files(base, [i for i in range(14) if i != 2])
+    volume(base, present=[i for i in range(14) if i != 2])
     os.chmod(str(base) + ".ec09", stat.S_IRUSR)
     if os.access(str(base) + ".ec09", os.W_OK):
         return  # a user whom file modes do not bind (root)

@@ -16,8 +16,6 @@ import check_model as C
 import correct_model as CM
 import correct_present_model as CP
 from oracle import rs_oracle as O
-from test_check_model import syndrome_of
-from test_correct_model import codewords
 
 UNEXPLAINED, ALL = C.UNEXPLAINED, C.ALL
 MASKS = C.checkable_masks()  # 469 degraded ones and the full mask
@@ -27,7 +25,7 @@ def test_a_single_error_in_each_present_shard():
     """One stripe per mask, every present shard wrong at an offset of its own."""
     L = 16
     assert len(MASKS) == 470
-    good = codewords(len(MASKS), L, 5)
+    good = CM.codewords(len(MASKS), L, 5)
     bad = good.copy()
     rng = np.random.default_rng(55)
     for s, m in enumerate(MASKS):
@@ -59,7 +57,7 @@ def test_the_kernel_shortcut_is_the_enumerated_value():
         B, E, A, _ = C.check_matrix(m)
         for c in B + E:
             v = int(rng.integers(1, 256))
-            syn = syndrome_of(m, {c: v})
+            syn = C.syndrome_of(m, {c: v})
             assert CP.column_value(syn, m, c) == v
             if c in E:
                 assert syn[E.index(c)] == v and sum(1 for x in syn if x) == 1
@@ -71,7 +69,7 @@ def test_two_wrong_shards_with_three_spares_are_never_written():
     rng = np.random.default_rng(33)
     masks = [m for m in C.checkable_masks((3,))]
     L = 8
-    good = codewords(len(masks), L, 6)
+    good = CM.codewords(len(masks), L, 6)
     bad = good.copy()
     for s, m in enumerate(masks):
         ids = [i for i in range(14) if m >> i & 1]
@@ -94,7 +92,7 @@ def test_two_wrong_shards_with_two_spares_are_sometimes_taken_for_an_intact_one(
     n, intact, own = 4000, 0, 0
     for _ in range(n):
         a, b = (ids[i] for i in rng.choice(len(ids), 2, replace=False))
-        word = C.column_word(syndrome_of(m, {a: int(rng.integers(1, 256)), b: int(rng.integers(1, 256))}), m)
+        word = C.column_word(C.syndrome_of(m, {a: int(rng.integers(1, 256)), b: int(rng.integers(1, 256))}), m)
         if word != UNEXPLAINED:
             named = word.bit_length() - 1
             own += named in (a, b)
@@ -102,7 +100,7 @@ def test_two_wrong_shards_with_two_spares_are_sometimes_taken_for_an_intact_one(
     print("r = 2, two wrong survivors in a column: %d of %d named an intact shard (%.2f %%)" % (intact, n, 100 * intact / n))
     assert own == 0 and 0 < intact < n // 10
     # and the model then writes that intact shard, unless min_spares is 3
-    good = codewords(1, 4, 8)
+    good = CM.codewords(1, 4, 8)
     B, _, _, H = C.check_matrix(m)
     sub = H[:, [0, 1]]
     v = O.mat_mul(O.mat_invert(sub), H[:, [2]])
@@ -120,7 +118,7 @@ def test_two_wrong_shards_with_two_spares_are_sometimes_taken_for_an_intact_one(
 def test_min_spares_and_use_masks():
     R4, R3, R2, R1 = ALL, ALL & ~(1 << 3), ALL & ~(1 | 1 << 12), ALL & ~(1 << 2 | 1 << 7 | 1 << 11)
     masks = [R4, R3, R2, R1, 0x3FF, R3, R2 | 1 << 20, R3]
-    good = codewords(len(masks), 12, 9)
+    good = CM.codewords(len(masks), 12, 9)
     bad = good.copy()
     for s, c in ((0, 13), (1, 0), (2, 13), (3, 5), (4, 2), (6, 4)):
         bad[s, c, s] ^= 0x40 + s
@@ -144,7 +142,7 @@ def test_min_spares_and_use_masks():
 
 
 def test_the_full_mask_is_the_correct_model():
-    good = codewords(6, 40, 11)
+    good = CM.codewords(6, 40, 11)
     bad = good.copy()
     rng = np.random.default_rng(12)
     for s, c in itertools.product(range(4), range(14)):

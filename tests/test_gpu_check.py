@@ -10,7 +10,6 @@ shards, shard gaps and stripe gaps hold it, so a kernel that reads an absent
 shard or a byte at or past shard_len computes a wrong word here. Every device
 call is also a footprint check: the arena comes back byte for byte (or, for the
 checked reconstruct, equals the expected image), word S keeps its sentinel."""
-import functools
 import itertools
 import os
 
@@ -18,121 +17,25 @@ import numpy as np
 import pytest
 
 import check_model as C
-import footprint as F
 import locate_model as M
+import scrub_harness as SH
 from oracle import corc
+from scrub_harness import (ALL, BLOCK, Batch, FILL, LAUNCH_LIMIT, MASK_ROUND, R1, R2, R3, UNEXPLAINED, assert_words,
+                           checksum, clean_stripes, expect_words, flip, hexes, i32, lost,
+                           masked_block_words as block_words, read_words, result_words, with_stray_bits, write_volume)
 
 pytestmark = pytest.mark.gpu
 
-UNEXPLAINED, ALL = C.UNEXPLAINED, C.ALL
-SENTINEL_WORD = 0x5A5AA5A5
-FILL = 0xEE
 LENGTHS = (2048, 8192 + 2048, 1000, 4096 + 16)  # one fast chunk, five, generic with an 8-byte tail, generic
-
-
-def lost(*ids):
-    return ALL & ~sum(1 << i for i in ids)
-
-
-R3, R2, R1 = lost(3), lost(0, 12), lost(2, 7, 11)  # one mask for each number of spare shards below four
-
-
-@functools.lru_cache(maxsize=None)
-def clean_stripes(S, L, seed=0):
-    """[S, 14, L] with the C oracle's parity (never modified: tests corrupt copies)."""
-    rng = np.random.default_rng(1000003 * seed + 31 * L + S)
-    st = rng.integers(0, 256, (S, 14, L), dtype=np.uint8)
-    st[:, 10:] = corc.encode_stripes(np.ascontiguousarray(st[:, :10]))
-    st.setflags(write=False)
-    return st
-
-
-def layout_of(kind, L, S):
-    if kind == "aligned":   # 16-byte aligned base and strides: the fast kernel where L allows
-        return F.stripe_major(14, L, S, F.r16(L) + 48, 16)
-    if kind == "odd":       # odd base, odd strides: the unaligned generic kernel
-        return F.stripe_major(14, L, S, F.r16(L) + 17, 3, base=F.SLACK + 1)
-    assert kind == "shard-major"
-    return F.shard_major(14, L, S, F.r16(L) + 16, 48)
-
-
-class Batch:
-    """Stripes laid out in one arena; absent shards and every gap hold FILL."""
-
-    def __init__(self, stripes, masks, kind="aligned", fill=FILL):
-        S, n, L = stripes.shape
-        self.S, self.L, self.masks = S, L, [int(m) for m in masks]
-        self.layout = layout_of(kind, L, S)
-        self.stripes = F.stripes_of(self.layout)
-        size, = F.arena_sizes(self.stripes)
-        if fill is None:
-            self.arena = np.random.default_rng(5).integers(0, 256, size, dtype=np.uint8)
-        else:
-            self.arena = np.full(size, fill, dtype=np.uint8)
-        for s in range(S):
-            for i in range(14):
-                if self.masks[s] >> i & 1:
-                    self.shard(s, i)[:] = stripes[s, i]
-                elif fill is None:
-                    self.shard(s, i)[:] = FILL
-
-    def shard(self, s, i):
-        o = self.layout.off(s, i)
-        return self.arena[o:o + self.L]
-
-    def gather(self, arena=None):
-        a = self.arena if arena is None else arena
-        return np.stack([np.stack([a[self.layout.off(s, i):self.layout.off(s, i) + self.L] for i in range(14)])
-                         for s in range(self.S)])
-
-
-def words(n, S):
-    import torch
-    ts = [torch.full((S + 1,), -1, dtype=torch.int32, device="cuda") for _ in range(n)]  # stale 0xFFFFFFFF
-    for t in ts:
-        t[S] = SENTINEL_WORD
-    return ts
-
-
-def read_words(t, S):
-    out = t.cpu().numpy().view(np.uint32)
-    assert int(out[S]) == SENTINEL_WORD
-    return [int(w) for w in out[:S]]
 
 
 def device_locate(rs, b, locate=True, preset=(7, 5)):
     """The masked locate (or verify alone) on batch b -> (check, suspects,
-    bad_stripes, unchecked). Asserts the footprint."""
-    import torch
-    import helyim_amd as H
-    S, la = b.S, b.layout
-    dev = torch.from_numpy(b.arena).cuda()
-    assert dev.data_ptr() % 256 == 0
-    chk, sus = words(2, S)
-    masks = torch.tensor(np.array(b.masks + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
-    bad = torch.full((1,), preset[0], dtype=torch.int32, device="cuda")
-    unchecked = torch.full((1,), preset[1], dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    stream = torch.cuda.current_stream().cuda_stream
-    base = dev.data_ptr() + la.base
-    if locate:
-        rc = H.lib.hec_gpu_locate_corrupt_present_batch(rs.handle, base, la.stripe_stride, la.shard_stride, la.L, S,
-                                                        masks.data_ptr(), chk.data_ptr(), sus.data_ptr(),
-                                                        bad.data_ptr(), unchecked.data_ptr(), stream)
-    else:
-        rc = H.lib.hec_gpu_verify_present_batch(rs.handle, base, la.stripe_stride, la.shard_stride, la.L, S,
-                                                masks.data_ptr(), chk.data_ptr(), bad.data_ptr(),
-                                                unchecked.data_ptr(), stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged([b.arena], [dev.cpu().numpy()], b.stripes)
-    assert masks.cpu().numpy().view(np.uint32).tolist() == b.masks + [0x3FFF]
-    return (read_words(chk, S), read_words(sus, S) if locate else None, int(bad.item()) - preset[0],
-            int(unchecked.item()) - preset[1])
-
-
-def hexes(ws):
-    return [hex(w) for w in ws]
+    bad_stripes, unchecked), the counters without their presets. Asserts the
+    footprint."""
+    call = "hec_gpu_locate_corrupt_present_batch" if locate else "hec_gpu_verify_present_batch"
+    ws, (bad, unchecked) = SH.device_masked(call, rs, b, 2 if locate else 1, preset)
+    return ws[0], ws[1] if locate else None, bad - preset[0], unchecked - preset[1]
 
 
 def check_batch(rs, b, by_construction=None, note=None):
@@ -306,15 +209,6 @@ def test_layouts_give_the_same_words(gpu, L):
     assert runs[0] == runs[1] == runs[2]
 
 
-def with_stray_bits(masks, seed):
-    """Random bits 14..30 and bit 31 ORed into every mask: hec.h defines the
-    present mask of a stripe as d_present_masks[s] & 0x3FFF."""
-    rng = np.random.default_rng(seed)
-    out = [m | int(rng.integers(1, 1 << 17)) << 14 | 1 << 31 for m in masks]
-    assert all(o & ALL == m and o >> 14 for o, m in zip(out, masks))
-    return out
-
-
 @pytest.mark.parametrize("L", LENGTHS)
 def test_stray_mask_bits_change_nothing(gpu, L):
     """The batches of test_layouts_give_the_same_words (the fast and the
@@ -348,7 +242,7 @@ def test_full_masks_reproduce_locate(gpu, L):
     chk, sus = check_batch(rs, b, [1 << 3, 1 << 12, UNEXPLAINED, 0, 1 | 1 << 13, 0], L)
     la = b.layout
     dev = torch.from_numpy(b.arena).cuda()
-    mis_t, sus_t = words(2, S)
+    mis_t, sus_t = result_words(2, S)
     base = dev.data_ptr() + la.base
     rc = H.lib.hec_gpu_locate_corrupt_batch(rs.handle, base, la.stripe_stride, la.shard_stride,
                                             base + 10 * la.shard_stride, la.stripe_stride, la.shard_stride, L, S,
@@ -518,8 +412,8 @@ def checked_reconstruct(L, kind, stray=False):
             expected.shard(s, i)[:] = clean[s, i]
     la = b.layout
     dev = torch.from_numpy(b.arena).cuda()
-    chk, sus, use = words(3, S)
-    mt = torch.tensor(np.array(given + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
+    chk, sus, use = result_words(3, S)
+    mt = SH.masks_tensor(given)
     bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
     left = torch.full((1,), 5, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -532,10 +426,10 @@ def checked_reconstruct(L, kind, stray=False):
     torch.cuda.synchronize()
     after = dev.cpu().numpy()
     # every byte: only shards outside the use mask changed, and to the original bytes
-    F.assert_unchanged([expected.arena], [after], b.stripes)
+    SH.assert_arenas([expected.arena], [after], b.stripes, masks=masks)
     assert read_words(chk, S) == want_chk and read_words(sus, S) == want_sus
     assert read_words(use, S) == want_use, hexes(read_words(use, S))
-    assert mt.cpu().numpy().view(np.uint32).tolist() == given + [0x3FFF]
+    SH.assert_masks(mt.cpu().numpy(), given + [ALL])
     assert int(left.item()) == 5 + want_left and int(bad.item()) == 7 + 1
     for s in range(S):
         for i in range(14):
@@ -543,7 +437,7 @@ def checked_reconstruct(L, kind, stray=False):
                 o = la.off(s, i)
                 assert np.array_equal(after[o:o + L], b.arena[o:o + L]), (s, i)
     # the proof: the repaired stripes verify clean
-    ver, = words(1, S)
+    ver, = result_words(1, S)
     rc = H.lib.hec_gpu_verify_batch(rs.handle, base, la.stripe_stride, la.shard_stride, base + 10 * la.shard_stride,
                                     la.stripe_stride, la.shard_stride, L, S, ver.data_ptr(), None, stream)
     assert rc == 0
@@ -590,8 +484,6 @@ def test_checked_reconstruct_python_mirror(gpu):
 
 
 # ---- big batches: built, corrupted and compared on the device ----------------------
-MASK_ROUND = 2048 * 256  # stripes one round of the mask kernels takes: 2048 workgroups of 256 lanes
-LAUNCH_LIMIT = 1 << 23   # workgroups of one launch, and of one pass of a grid-stride loop
 CYCLE = [ALL, R3, R2, R1, 0x3FF]  # r = 4, 3, 2, 1 and p = 10, over the whole batch
 
 
@@ -620,36 +512,6 @@ def edge_hits(edge):
         S - 2: (R1, [(0, 0, 0x01)], UNEXPLAINED),
         S - 1: (lost(5), [(0, 15, 0x42)], 1 << 0),
     }
-
-
-def i32(values):
-    import torch
-    return torch.tensor(np.array(values, dtype=np.uint32).view(np.int32), device="cuda")
-
-
-def expect_words(S, idx, values, rest=0):
-    """[S + 1] words on the device: `rest` (a value or an [S] tensor), `values`
-    at the stripes idx, the sentinel at S -- what words(n, S) must become."""
-    import torch
-    t = torch.empty(S + 1, dtype=torch.int32, device="cuda")
-    t[:S] = rest
-    t[idx] = i32(values)
-    t[S] = SENTINEL_WORD
-    return t
-
-
-def assert_words(got, want, what):
-    import torch
-    if not torch.equal(got, want):
-        at = torch.nonzero(got != want).flatten()[:8].cpu().tolist()
-        pytest.fail(f"{what}: wrong at {at}: got {hexes(got[at].cpu().numpy().view(np.uint32))}, "
-                    f"expected {hexes(want[at].cpu().numpy().view(np.uint32))}")
-
-
-def checksum(t):
-    """One device reduction over every byte of a contiguous tensor."""
-    import torch
-    return int(t.view(torch.int64).sum().item())
 
 
 def masked_scrub_big(edge):
@@ -693,7 +555,7 @@ def masked_scrub_big(edge):
 
     # pass 1 alone, then both passes: words and counts, nothing else written
     for locate in (False, True):
-        chk, sus = words(2, S)
+        chk, sus = result_words(2, S)
         bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
         unchecked = torch.full((1,), 5, dtype=torch.int32, device="cuda")
         if locate:
@@ -712,7 +574,7 @@ def masked_scrub_big(edge):
     assert len(kept) == want_left + n_few
     kept_idx = idx[torch.tensor(kept, device="cuda")]
     expected[kept_idx] = t[kept_idx]
-    chk, sus, use = words(3, S)
+    chk, sus, use = result_words(3, S)
     bad = torch.full((1,), 7, dtype=torch.int32, device="cuda")
     left = torch.full((1,), 5, dtype=torch.int32, device="cuda")
     H.reconstruct_checked_batch(rs, t, masks, check=chk, suspects=sus, use_masks=use, bad_stripes=bad,
@@ -727,7 +589,7 @@ def masked_scrub_big(edge):
         wrong = torch.nonzero((t != expected).flatten(1).any(dim=1)).flatten()
         pytest.fail(f"image: {wrong.numel()} wrong stripes, the first {wrong[:8].cpu().tolist()}")
     # the proof: every stripe but the ones left alone verifies clean
-    ver, = words(1, S)
+    ver, = result_words(1, S)
     H.verify_batch(rs, t, mismatch=ver)
     torch.cuda.synchronize()
     assert torch.nonzero(ver[:S]).flatten().cpu().tolist() == [order[n] for n in kept]
@@ -751,44 +613,9 @@ def test_masked_scrub_past_one_launch(gpu):
 
 
 # ---- shard files -----------------------------------------------------------------
-BLOCK = 4096
-
-
 @pytest.fixture(scope="module")
 def volume(tmp_path_factory):
-    """A small volume written by generate_ec_files with small blocks: shards
-    that end in a short block."""
-    import helyim_amd as H
-    d = tmp_path_factory.mktemp("degraded")
-    base = str(d / "9")
-    large, small = 16 * 1001, 1001
-    open(base + ".dat", "wb").write(corc.splitmix64_bytes(99, 10 * large * 2 + 10 * small * 23 + 321).tobytes())
-    H.generate_ec_files(base, small, large, small)
-    files = [open(base + ".ec%02d" % i, "rb").read() for i in range(14)]
-    size = len(files[0])
-    assert all(len(f) == size for f in files) and size > 12 * BLOCK and size % BLOCK > 1
-    return files, size
-
-
-def write_volume(tmp_path, files, absent=()):
-    base = str(tmp_path / "v")
-    for i, f in enumerate(files):
-        if i not in absent:
-            open(base + ".ec%02d" % i, "wb").write(f)
-    return base
-
-
-def flip(base, shard, offset, value=0x5A):
-    with open(base + ".ec%02d" % shard, "r+b") as f:
-        f.seek(offset)
-        byte = f.read(1)
-        f.seek(offset)
-        f.write(bytes([byte[0] ^ value]))
-
-
-def block_words(files, mask, lo, hi):
-    block = np.stack([np.frombuffer(bytes(f[lo:hi]), np.uint8) for f in files])[None]
-    return C.check_words(block, [mask])[0], C.suspect_words(block, [mask])[0]
+    return SH.degraded_volume(str(tmp_path_factory.mktemp("degraded") / "9"))
 
 
 def test_files_one_missing_one_corrupt_then_rebuild(gpu, volume, tmp_path):

@@ -6,7 +6,7 @@ Every expected image, suspects word and byte count comes from
 tests/correct_model.py (the contract by brute force) applied to the arenas as
 they are, every expected mismatch word from the C oracle as in
 tests/test_gpu_verify.py. The arenas, layouts and helpers are those of
-tests/test_gpu_locate_pairs.py, and every device call is also a footprint
+tests/scrub_harness.py, and every device call is also a footprint
 check: the arenas afterwards equal the model's image byte for byte -- slack,
 gaps and the bytes past shard_len included -- and result word S is untouched."""
 import os
@@ -15,16 +15,17 @@ import numpy as np
 import pytest
 
 import correct_model as CM
-import footprint as F
 import locate_model as M
 import locate_pairs_model as PM
-from test_gpu_locate_pairs import (ALL, BIG_BLOCKS, BIG_SIZE, EDGE, LAYOUTS, LENGTHS, NEIGHBOURS, RUN, SINGLES, TRIPLE_AT,
-                                   UNEXPLAINED, big_entries, big_volume, bits, ec_names, gather, hex_list,
-                                   in_place_layout, read_words, result_words, unexplained_triple)
-from test_gpu_verify import clean_case, copies, flip_positions, oracle_words, shard_of
+import scrub_harness as SH
+from scrub_harness import (ALL, BIG_BLOCKS, BIG_SIZE, EDGE, NEIGHBOURS, RUN, SINGLES, TRIPLE_AT, UNEXPLAINED,
+                           big_entries, big_volume, bits, clean_case, copies, ec_names, flip_positions, gather, hexes,
+                           in_place_layout, oracle_words, shard_of)
 
 pytestmark = pytest.mark.gpu
 
+LENGTHS = (8192, 8192 + 2048, 4096 + 16, 1000, 17, 1)
+LAYOUTS = (0, 3)  # scrub_harness.layouts: aligned stripe-major with gaps, odd base
 BAD0, UNC0, BYTES0 = 7, 5, 11  # presets of the three accumulated counters
 
 
@@ -32,25 +33,11 @@ def device_correct(rs, arenas, stripes, data, par, expected, pairs):
     """One of the two calls on the arenas -> (mismatch [S], suspects [S],
     bad_stripes, uncorrected, corrected_bytes). Asserts that the arenas
     afterwards equal `expected` in every byte."""
-    import torch
-    import helyim_amd as H
-    S = data.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    assert all(d.data_ptr() % 256 == 0 for d in devs)
-    mis, sus = result_words(2, S)
-    bad = torch.full((1,), BAD0, dtype=torch.int32, device="cuda")
-    unc = torch.full((1,), UNC0, dtype=torch.int32, device="cuda")
-    nbytes = torch.full((1,), BYTES0, dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-    call = H.lib.hec_gpu_correct_pairs_batch if pairs else H.lib.hec_gpu_correct_batch
-    rc = call(rs.handle, devs[data.arena].data_ptr() + data.base, data.stripe_stride, data.shard_stride,
-              devs[par.arena].data_ptr() + par.base, par.stripe_stride, par.shard_stride, data.L, S, mis.data_ptr(),
-              sus.data_ptr(), bad.data_ptr(), unc.data_ptr(), nbytes.data_ptr(),
-              torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(expected, [d.cpu().numpy() for d in devs], stripes, ("pairs" if pairs else "single"))
-    return read_words(mis, S), read_words(sus, S), int(bad.item()), int(unc.item()), int(nbytes.item())
+    call = "hec_gpu_correct_pairs_batch" if pairs else "hec_gpu_correct_batch"
+    (mis, sus), (bad, unc, nbytes) = SH.device_words(call, rs, arenas, stripes, data, par, 2, [BAD0, UNC0, BYTES0],
+                                                     wide_last=True, expected=expected,
+                                                     note="pairs" if pairs else "single")
+    return mis, sus, bad, unc, nbytes
 
 
 def model_image(work, stripes, pairs):
@@ -70,12 +57,12 @@ def check_correct(rs, work, stripes, data, par, pairs, note=None, want_sus=None,
     expected, sus_model, changed = model_image(work, stripes, pairs)
     want_mis = oracle_words(work, stripes, 10, 4)
     if want_sus is not None:
-        assert sus_model == want_sus, (note, hex_list(sus_model), hex_list(want_sus))
+        assert sus_model == want_sus, (note, hexes(sus_model), hexes(want_sus))
     if restored is not None:
         assert all(np.array_equal(e, r) for e, r in zip(expected, restored)), note
     mis, sus, bad, unc, nbytes = device_correct(rs, copies(work), stripes, data, par, expected, pairs)
-    assert sus == sus_model, (note, pairs, hex_list(sus), hex_list(sus_model))
-    assert mis == want_mis, (note, pairs, hex_list(mis), hex_list(want_mis))
+    assert sus == sus_model, (note, pairs, hexes(sus), hexes(sus_model))
+    assert mis == want_mis, (note, pairs, hexes(mis), hexes(want_mis))
     assert bad == BAD0 + sum(1 for w in want_mis if w), (note, pairs)
     assert unc == UNC0 + sum(1 for w in sus_model if w & UNEXPLAINED), (note, pairs, unc)
     assert nbytes == BYTES0 + changed, (note, pairs, nbytes, changed)
@@ -137,17 +124,9 @@ def test_five_shards_at_five_offsets(gpu, L):
             shard_of(work, stripes, 1, shard)[pos] ^= value
         named = bits(*(h[0] for h in hits))
         # the repair on a copy: left alone, unrepaired + 1
-        devs = [torch.from_numpy(a).cuda() for a in copies(work)]
-        mis, sus, masks = result_words(3, S)
-        left = torch.full((1,), 7, dtype=torch.int32, device="cuda")
-        rc = H.lib.hec_gpu_repair_batch(rs.handle, devs[layout.arena].data_ptr() + layout.base, layout.stripe_stride,
-                                        layout.shard_stride, L, S, mis.data_ptr(), sus.data_ptr(), masks.data_ptr(),
-                                        left.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        assert rc == 0, (rc, H._lib.last_detail())
-        torch.cuda.synchronize()
-        F.assert_unchanged(work, [d.cpu().numpy() for d in devs], stripes, name)
-        assert read_words(sus, S) == [0, named, 0, 0, 0] and int(left.item()) == 7 + 1, name
-        assert read_words(masks, S) == [ALL] * S, name
+        _, sus, masks, left, _ = SH.device_repair("hec_gpu_repair_batch", rs, copies(work), stripes, layout, work)
+        assert sus == [0, named, 0, 0, 0] and left == 7 + 1, name
+        assert masks == [ALL] * S, name
         # the correct
         for pairs in (False, True):
             check_correct(rs, work, stripes, data, par, pairs, name, [0, named, 0, 0, 0], restored=arenas)
@@ -193,7 +172,7 @@ def test_unexplained_triples_stay_and_count_once(gpu, L):
     rs = H.ReedSolomon(10, 4)
     rng = np.random.default_rng(6)
     triple_at = sorted({p % L for p in (5, 1024 + 5, 4096 + 7, 8192 + 2047)})
-    triples = [unexplained_triple(rng) for _ in triple_at]
+    triples = [PM.unexplained_triple(rng) for _ in triple_at]
     for which in LAYOUTS:
         name, data, par, stripes, arenas = clean_case(10, 4, L, 5, which)
         work = copies(arenas)
@@ -329,7 +308,7 @@ def test_files(gpu, tmp_path):
     for shard in (2, 13):
         for o in range(run, run + 4096):
             bad[shard][o] ^= int(rng.integers(1, 256))
-    triple, t_at = unexplained_triple(rng), 7 * BLOCK + 9
+    triple, t_at = PM.unexplained_triple(rng), 7 * BLOCK + 9
     for c, v in triple.items():
         bad[c][t_at] ^= v
     last = size - 1

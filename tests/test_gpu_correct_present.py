@@ -6,7 +6,7 @@ Every expected image, word and count comes from tests/correct_present_model.py
 (the contract by brute force, on top of tests/check_model.py) applied to the
 batch as it is; where the test built the damage itself the words and the
 restored image are asserted by construction too. The arena harness is that of
-tests/test_gpu_check.py: absent shards, shard gaps and stripe gaps hold a
+tests/scrub_harness.py (Batch): absent shards, shard gaps and stripe gaps hold a
 sentinel byte, result word S a sentinel word, and every device call is also a
 whole-arena comparison against the model's image -- an absent shard, a gap or a
 byte at or past shard_len that was read or written shows."""
@@ -18,13 +18,13 @@ import pytest
 
 import check_model as C
 import correct_present_model as CP
-import footprint as F
-from test_check_model import syndrome_of
-from test_gpu_check import (ALL, BLOCK, FILL, LENGTHS, R1, R2, R3, UNEXPLAINED, Batch, block_words, clean_stripes, flip,
-                            hexes, lost, read_words, volume, with_stray_bits, words, write_volume)  # noqa: F401
+import scrub_harness as SH
+from scrub_harness import (ALL, BLOCK, Batch, FILL, R1, R2, R3, UNEXPLAINED, clean_stripes, flip, hexes, lost,
+                           masked_block_words as block_words, read_words, result_words, with_stray_bits, write_volume)
 
 pytestmark = pytest.mark.gpu
 
+LENGTHS = (2048, 8192 + 2048, 1000, 4096 + 16)  # one fast chunk, five, generic with an 8-byte tail, generic
 KINDS = ("aligned", "odd", "shard-major")
 BAD0, UNCHECKED0, UNC0, BYTES0 = 7, 5, 3, 11  # presets of the four accumulated counters
 
@@ -44,29 +44,10 @@ def device_correct(rs, b, expected, min_spares=2, given=None):
     """hec_gpu_correct_present_batch on b -> (check, suspects, bad_stripes,
     unchecked, uncorrected, corrected_bytes), the counters without their
     presets. Asserts that the arena afterwards equals `expected` in every byte."""
-    import torch
-    import helyim_amd as H
-    S, la = b.S, b.layout
-    given = b.masks if given is None else given
-    dev = torch.from_numpy(b.arena).cuda()
-    assert dev.data_ptr() % 256 == 0
-    chk, sus = words(2, S)
-    masks = torch.tensor(np.array(list(given) + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
-    bad = torch.full((1,), BAD0, dtype=torch.int32, device="cuda")
-    unchecked = torch.full((1,), UNCHECKED0, dtype=torch.int32, device="cuda")
-    unc = torch.full((1,), UNC0, dtype=torch.int32, device="cuda")
-    nbytes = torch.full((1,), BYTES0, dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-    rc = H.lib.hec_gpu_correct_present_batch(rs.handle, dev.data_ptr() + la.base, la.stripe_stride, la.shard_stride,
-                                             la.L, S, masks.data_ptr(), min_spares, chk.data_ptr(), sus.data_ptr(),
-                                             bad.data_ptr(), unchecked.data_ptr(), unc.data_ptr(), nbytes.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged([expected], [dev.cpu().numpy()], b.stripes, min_spares)
-    assert masks.cpu().numpy().view(np.uint32).tolist() == list(given) + [0x3FFF]
-    return (read_words(chk, S), read_words(sus, S), int(bad.item()) - BAD0, int(unchecked.item()) - UNCHECKED0,
-            int(unc.item()) - UNC0, int(nbytes.item()) - BYTES0)
+    presets = [BAD0, UNCHECKED0, UNC0, BYTES0]
+    (chk, sus), got = SH.device_masked("hec_gpu_correct_present_batch", rs, b, 2, presets, wide_last=True,
+                                       min_spares=min_spares, given=given, expected=expected, note=min_spares)
+    return (chk, sus) + tuple(g - p0 for g, p0 in zip(got, presets))
 
 
 def check_correct(rs, b, min_spares=2, note=None, want_sus=None, restored=None, given=None, want_counts=None):
@@ -94,31 +75,15 @@ def check_correct(rs, b, min_spares=2, note=None, want_sus=None, restored=None, 
 def device_reconstruct(rs, b, expected, corrected, min_spares=2):
     """hec_gpu_reconstruct_corrected_batch (or the checked one) on b -> (check,
     suspects, use masks, bad_stripes, unrepaired, corrected_bytes)."""
-    import torch
-    import helyim_amd as H
-    S, la = b.S, b.layout
-    dev = torch.from_numpy(b.arena).cuda()
-    chk, sus, use = words(3, S)
-    masks = torch.tensor(np.array(b.masks + [0x3FFF], dtype=np.uint32).view(np.int32), device="cuda")
-    bad = torch.full((1,), BAD0, dtype=torch.int32, device="cuda")
-    left = torch.full((1,), UNC0, dtype=torch.int32, device="cuda")
-    nbytes = torch.full((1,), BYTES0, dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-    stream = torch.cuda.current_stream().cuda_stream
-    head = (rs.handle, dev.data_ptr() + la.base, la.stripe_stride, la.shard_stride, la.L, S, masks.data_ptr())
     if corrected:
-        rc = H.lib.hec_gpu_reconstruct_corrected_batch(*head, min_spares, chk.data_ptr(), sus.data_ptr(),
-                                                       use.data_ptr(), bad.data_ptr(), left.data_ptr(),
-                                                       nbytes.data_ptr(), stream)
+        (chk, sus, use), (bad, left, nbytes) = SH.device_masked(
+            "hec_gpu_reconstruct_corrected_batch", rs, b, 3, [BAD0, UNC0, BYTES0], wide_last=True,
+            min_spares=min_spares, expected=expected, note="corrected")
     else:
-        rc = H.lib.hec_gpu_reconstruct_checked_batch(*head, chk.data_ptr(), sus.data_ptr(), use.data_ptr(),
-                                                     bad.data_ptr(), left.data_ptr(), stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged([expected], [dev.cpu().numpy()], b.stripes, "corrected" if corrected else "checked")
-    assert masks.cpu().numpy().view(np.uint32).tolist() == b.masks + [0x3FFF]
-    return (read_words(chk, S), read_words(sus, S), read_words(use, S), int(bad.item()) - BAD0,
-            int(left.item()) - UNC0, int(nbytes.item()) - BYTES0)
+        (chk, sus, use), (bad, left) = SH.device_masked("hec_gpu_reconstruct_checked_batch", rs, b, 3, [BAD0, UNC0],
+                                                        expected=expected, note="checked")
+        nbytes = BYTES0
+    return chk, sus, use, bad - BAD0, left - UNC0, nbytes - BYTES0
 
 
 def positions_of_interest(L):
@@ -271,7 +236,7 @@ def test_two_wrong_survivors_in_one_column(gpu):
     while taken is None or unexplained is None:
         a, c = (ids2[i] for i in rng.choice(len(ids2), 2, replace=False))
         errors = {a: int(rng.integers(1, 256)), c: int(rng.integers(1, 256))}
-        word = C.column_word(syndrome_of(R2, errors), R2)
+        word = C.column_word(C.syndrome_of(R2, errors), R2)
         if word == UNEXPLAINED:
             unexplained = unexplained or errors
         else:
@@ -350,7 +315,7 @@ def test_full_masks_reproduce_correct(gpu, L):
                                            want_sus=[1 << 3, 1 << 12, UNEXPLAINED | 1 << 11, 0, 1 | 1 << 13, 0])
         la = b.layout
         dev = torch.from_numpy(b.arena).cuda()
-        mis_t, sus_t = words(2, S)
+        mis_t, sus_t = result_words(2, S)
         unc = torch.zeros(1, dtype=torch.int32, device="cuda")
         nbytes = torch.zeros(1, dtype=torch.int64, device="cuda")
         base = dev.data_ptr() + la.base
@@ -504,6 +469,11 @@ def test_encode_corrupt_correct_verify_in_stream_order_and_python_mirrors(gpu):
 
 
 # ---- shard files -----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def volume(tmp_path_factory):
+    return SH.degraded_volume(str(tmp_path_factory.mktemp("degraded") / "9"))
+
+
 def read_files(base, ids=range(14)):
     return {i: open(base + ".ec%02d" % i, "rb").read() for i in ids}
 

@@ -15,61 +15,29 @@ import os
 import numpy as np
 import pytest
 
-import footprint as F
 import locate_model as M
 from oracle import corc
-from test_gpu_verify import SENTINEL, clean_case, copies, flip_positions, oracle_words, shard_of
+import scrub_harness as SH
+from scrub_harness import (ALL, BLOCK, LAUNCH_LIMIT, MASK_ROUND, assert_words, clean_case, copies, expect_words, flip,
+                           flip_positions, gather, hexes, in_place_layout, oracle_words, result_words, shard_of)
 
 pytestmark = pytest.mark.gpu
 
 UNEXPLAINED = M.UNEXPLAINED
 LENGTHS = (8192, 8192 + 2048, 4096 + 16, 1000, 17, 1)
-LAYOUTS = (0, 3)  # test_gpu_verify.layouts: aligned stripe-major with gaps, odd base
-ALL = 0x3FFF
-
-
-def gather(arenas, stripes):
-    """The stripes' shards as they are in the arenas -> [S, 14, L]."""
-    return np.stack([np.stack([shard_of(arenas, stripes, s, i) for i in range(14)]) for s in range(len(stripes))])
+LAYOUTS = (0, 3)  # scrub_harness.layouts: aligned stripe-major with gaps, odd base
 
 
 def model_words(arenas, stripes):
     return M.suspect_words(gather(arenas, stripes))
 
 
-def result_words(n, S):
-    import torch
-    ts = [torch.full((S + 1,), -1, dtype=torch.int32, device="cuda") for _ in range(n)]  # stale 0xFFFFFFFF
-    for t in ts:
-        t[S] = SENTINEL
-    return ts
-
-
-def read_words(t, S):
-    out = t.cpu().numpy().view(np.uint32)
-    assert int(out[S]) == SENTINEL
-    return [int(w) for w in out[:S]]
-
-
 def device_locate(rs, arenas, stripes, data, par, preset_bad=7):
     """hec_gpu_locate_corrupt_batch on the arenas -> (mismatch [S], suspects
     [S], bad_stripes). Asserts the footprint."""
-    import torch
-    import helyim_amd as H
-    S = data.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    assert all(d.data_ptr() % 256 == 0 for d in devs)
-    mis, sus = result_words(2, S)
-    bad = torch.full((1,), preset_bad, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    rc = H.lib.hec_gpu_locate_corrupt_batch(rs.handle, devs[data.arena].data_ptr() + data.base, data.stripe_stride,
-                                            data.shard_stride, devs[par.arena].data_ptr() + par.base,
-                                            par.stripe_stride, par.shard_stride, data.L, S, mis.data_ptr(),
-                                            sus.data_ptr(), bad.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(arenas, [d.cpu().numpy() for d in devs], stripes)
-    return read_words(mis, S), read_words(sus, S), int(bad.item())
+    (mis, sus), (bad,) = SH.device_words("hec_gpu_locate_corrupt_batch", rs, arenas, stripes, data, par, 2,
+                                         [preset_bad])
+    return mis, sus, bad
 
 
 def check_locate(rs, work, stripes, data, par, by_construction=None, note=None):
@@ -86,10 +54,6 @@ def check_locate(rs, work, stripes, data, par, by_construction=None, note=None):
     return sus
 
 
-def hex_list(ws):
-    return [hex(w) for w in ws]
-
-
 # ---- device batches --------------------------------------------------------------
 @pytest.mark.parametrize("L", LENGTHS)
 def test_clean_batch(gpu, L):
@@ -98,7 +62,7 @@ def test_clean_batch(gpu, L):
     for which in LAYOUTS:
         name, data, par, stripes, arenas = clean_case(10, 4, L, 5, which)
         mis, sus, bad = device_locate(rs, copies(arenas), stripes, data, par)
-        assert mis == [0] * 5 and sus == [0] * 5, (name, hex_list(mis), hex_list(sus))
+        assert mis == [0] * 5 and sus == [0] * 5, (name, hexes(mis), hexes(sus))
         assert bad == 7, name
 
 
@@ -293,37 +257,7 @@ def test_encode_then_locate_in_stream_order(gpu):
 
 # ---- repair ----------------------------------------------------------------------
 def device_repair(rs, arenas, stripes, layout, expected, preset_left=7):
-    """hec_gpu_repair_batch on the in-place layout -> (mismatch, suspects,
-    masks, unrepaired, verify words afterwards). Asserts that the arenas equal
-    `expected` in every byte."""
-    import torch
-    import helyim_amd as H
-    S = layout.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    mis, sus, masks = result_words(3, S)
-    left = torch.full((1,), preset_left, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    stream = torch.cuda.current_stream().cuda_stream
-    base = devs[layout.arena].data_ptr() + layout.base
-    rc = H.lib.hec_gpu_repair_batch(rs.handle, base, layout.stripe_stride, layout.shard_stride, layout.L, S,
-                                    mis.data_ptr(), sus.data_ptr(), masks.data_ptr(), left.data_ptr(), stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(expected, [d.cpu().numpy() for d in devs], stripes)
-    after, = result_words(1, S)
-    rc = H.lib.hec_gpu_verify_batch(rs.handle, base, layout.stripe_stride, layout.shard_stride,
-                                    base + 10 * layout.shard_stride, layout.stripe_stride, layout.shard_stride,
-                                    layout.L, S, after.data_ptr(), None, stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    return read_words(mis, S), read_words(sus, S), read_words(masks, S), int(left.item()), read_words(after, S)
-
-
-def in_place_layout(data, par):
-    """The 14-shard layout of a clean_case whose parity follows its data."""
-    assert par.base == data.base + 10 * data.shard_stride and par.arena == data.arena
-    assert (par.stripe_stride, par.shard_stride) == (data.stripe_stride, data.shard_stride)
-    return data._replace(shards=14)
+    return SH.device_repair("hec_gpu_repair_batch", rs, arenas, stripes, layout, expected, preset_left)
 
 
 def expected_masks(sus):
@@ -358,11 +292,11 @@ def test_repair(gpu, L):
         for shard, pos in hits[3]:
             shard_of(expected, stripes, 3, shard)[pos] = shard_of(work, stripes, 3, shard)[pos]
         mis, sus, masks, left, after = device_repair(rs, work, stripes, layout, expected)
-        assert sus == want_sus and mis == want_mis, (name, hex_list(sus), hex_list(mis))
-        assert masks == expected_masks(want_sus), (name, hex_list(masks))
+        assert sus == want_sus and mis == want_mis, (name, hexes(sus), hexes(mis))
+        assert masks == expected_masks(want_sus), (name, hexes(masks))
         assert masks[3] == ALL and masks[4] == ALL and masks[2] == ALL & ~(1 << 2 | 1 << 7 | 1 << 10 | 1 << 12)
         assert left == 7 + 1, name
-        assert after == [0, 0, 0, want_mis[3], 0, 0], (name, hex_list(after))
+        assert after == [0, 0, 0, want_mis[3], 0, 0], (name, hexes(after))
 
 
 def test_repair_leaves_five_suspects_alone(gpu):
@@ -385,10 +319,6 @@ def test_repair_leaves_five_suspects_alone(gpu):
 
 
 # ---- big batches: built, corrupted and compared on the device ----------------------
-MASK_ROUND = 2048 * 256  # stripes one round of repair_masks_kernel takes: 2048 workgroups of 256 lanes
-LAUNCH_LIMIT = 1 << 23   # workgroups of one launch, and of one pass of a grid-stride loop
-
-
 def edge_hits(edge):
     """stripe -> (flips [(shard, pos, value)], suspects word by construction)
     of a batch of edge + 5 stripes of 16 bytes: one-shard flips (repaired) in
@@ -414,29 +344,6 @@ def edge_hits(edge):
     }
 
 
-def i32(values):
-    import torch
-    return torch.tensor(np.array(values, dtype=np.uint32).view(np.int32), device="cuda")
-
-
-def expect_words(S, idx, values, rest=0):
-    """[S + 1] words on the device: `rest` everywhere, `values` at the stripes
-    idx, the sentinel at S -- what result_words(n, S) must become."""
-    import torch
-    t = torch.full((S + 1,), rest, dtype=torch.int32, device="cuda")
-    t[idx] = i32(values)
-    t[S] = SENTINEL
-    return t
-
-
-def assert_words(got, want, what):
-    import torch
-    if not torch.equal(got, want):
-        at = torch.nonzero(got != want).flatten()[:8].cpu().tolist()
-        pytest.fail(f"{what}: wrong at {at}: got {hex_list(got[at].cpu().numpy().view(np.uint32))}, "
-                    f"expected {hex_list(want[at].cpu().numpy().view(np.uint32))}")
-
-
 def locate_and_repair_big(edge):
     """hec_gpu_locate_corrupt_batch, then hec_gpu_repair_batch, over edge + 5
     stripes of 16 bytes with edge_hits' corruption. Expected words of the dirty
@@ -459,7 +366,7 @@ def locate_and_repair_big(edge):
             t[s, shard, pos] ^= value
     dirty = t[idx].cpu().numpy()
     want_sus, want_mis = M.suspect_words(dirty), M.mismatch_words(dirty)
-    assert want_sus == [hits[s][1] for s in order], hex_list(want_sus)
+    assert want_sus == [hits[s][1] for s in order], hexes(want_sus)
     assert all(want_mis)
     want_masks = expected_masks(want_sus)
     kept = [n for n, m in enumerate(want_masks) if m == ALL]  # dirty and left alone
@@ -514,9 +421,6 @@ def test_locate_and_repair_past_one_launch(gpu):
 
 
 # ---- shard files -----------------------------------------------------------------
-BLOCK = 4096
-
-
 @pytest.fixture(scope="module")
 def shard_files(tmp_path_factory):
     """Oracle-written shard files of a seeded .dat (as test_gpu_verify's): each
@@ -524,26 +428,15 @@ def shard_files(tmp_path_factory):
     d = tmp_path_factory.mktemp("locate")
     base = str(d / "7")
     large, small = 64 * 1001, 1001
-    open(base + ".dat", "wb").write(corc.splitmix64_bytes(77, 10 * large * 3 + 10 * small * 57 + 123).tobytes())
-    assert corc.write_ec_files(base, small, large, small) == 0
-    files = [open(base + ".ec%02d" % i, "rb").read() for i in range(14)]
+    files = SH.oracle_volume(base, 77, large, small, 123)
     size = len(files[0])
     assert all(len(f) == size for f in files) and size % BLOCK > 1
     return base, files, size
 
 
-def flip(base, shard, offset, value=0x5A):
-    with open(base + ".ec%02d" % shard, "r+b") as f:
-        f.seek(offset)
-        b = f.read(1)
-        f.seek(offset)
-        f.write(bytes([b[0] ^ value]))
-
-
 def block_words(files, lo, hi):
     """(mismatch, suspects) of the column block [lo, hi) by the model."""
-    block = np.stack([np.frombuffer(bytes(f[lo:hi]), np.uint8) for f in files])[None]
-    return M.mismatch_words(block)[0], M.suspect_words(block)[0]
+    return SH.block_words(files, lo, hi, M.mismatch_words, M.suspect_words)
 
 
 def test_files_locate_then_rebuild(gpu, shard_files, tmp_path):

@@ -16,66 +16,26 @@ import os
 import numpy as np
 import pytest
 
-import footprint as F
 import locate_model as M
 import locate_pairs_model as PM
-from test_gpu_verify import SENTINEL, clean_case, copies, flip_positions, oracle_words, shard_of
+import scrub_harness as SH
+from scrub_harness import (ALL, BIG_BLOCKS, BIG_SIZE, BLOCK, EDGE, TRIPLE_AT, big_entries, big_volume, bits,
+                           clean_case, copies, ec_names, flip_positions, gather, hexes, in_place_layout, oracle_words,
+                           shard_of)
 
 pytestmark = pytest.mark.gpu
 
 UNEXPLAINED = PM.UNEXPLAINED
 LENGTHS = (8192, 8192 + 2048, 4096 + 16, 1000, 17, 1)
-LAYOUTS = (0, 3)  # test_gpu_verify.layouts: aligned stripe-major with gaps, odd base
-ALL = 0x3FFF
+LAYOUTS = (0, 3)  # scrub_harness.layouts: aligned stripe-major with gaps, odd base
 PAIRS_CALL, SINGLE_CALL = "hec_gpu_locate_corrupt_pairs_batch", "hec_gpu_locate_corrupt_batch"
-
-
-def bits(*shards):
-    return sum(1 << c for c in shards)
-
-
-def hex_list(ws):
-    return [hex(w) for w in ws]
-
-
-def gather(arenas, stripes):
-    """The stripes' shards as they are in the arenas -> [S, 14, L]."""
-    return np.stack([np.stack([shard_of(arenas, stripes, s, i) for i in range(14)]) for s in range(len(stripes))])
-
-
-def result_words(n, S):
-    import torch
-    ts = [torch.full((S + 1,), -1, dtype=torch.int32, device="cuda") for _ in range(n)]  # stale 0xFFFFFFFF
-    for t in ts:
-        t[S] = SENTINEL
-    return ts
-
-
-def read_words(t, S):
-    out = t.cpu().numpy().view(np.uint32)
-    assert int(out[S]) == SENTINEL
-    return [int(w) for w in out[:S]]
 
 
 def device_locate(call, rs, arenas, stripes, data, par, preset_bad=7):
     """`call` (one of the two locate entry points) on the arenas -> (mismatch
     [S], suspects [S], bad_stripes). Asserts the footprint."""
-    import torch
-    import helyim_amd as H
-    S = data.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    assert all(d.data_ptr() % 256 == 0 for d in devs)
-    mis, sus = result_words(2, S)
-    bad = torch.full((1,), preset_bad, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    rc = getattr(H.lib, call)(rs.handle, devs[data.arena].data_ptr() + data.base, data.stripe_stride,
-                              data.shard_stride, devs[par.arena].data_ptr() + par.base, par.stripe_stride,
-                              par.shard_stride, data.L, S, mis.data_ptr(), sus.data_ptr(), bad.data_ptr(),
-                              torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(arenas, [d.cpu().numpy() for d in devs], stripes)
-    return read_words(mis, S), read_words(sus, S), int(bad.item())
+    (mis, sus), (bad,) = SH.device_words(call, rs, arenas, stripes, data, par, 2, [preset_bad])
+    return mis, sus, bad
 
 
 def check_pairs(rs, work, stripes, data, par, by_construction=None, note=None, single=None):
@@ -86,28 +46,18 @@ def check_pairs(rs, work, stripes, data, par, by_construction=None, note=None, s
     want_sus = PM.suspect_words(shards)
     want_mis = oracle_words(work, stripes, 10, 4)
     if by_construction is not None:
-        assert want_sus == by_construction, (note, hex_list(want_sus), hex_list(by_construction))
+        assert want_sus == by_construction, (note, hexes(want_sus), hexes(by_construction))
     assert [w != 0 for w in want_mis] == [w != 0 for w in want_sus], note
     mis, sus, bad = device_locate(PAIRS_CALL, rs, work, stripes, data, par)
-    assert sus == want_sus, (note, hex_list(sus), hex_list(want_sus))
-    assert mis == want_mis, (note, hex_list(mis), hex_list(want_mis))
+    assert sus == want_sus, (note, hexes(sus), hexes(want_sus))
+    assert mis == want_mis, (note, hexes(mis), hexes(want_mis))
     assert bad == 7 + sum(1 for w in want_mis if w), note
     if single is not None:
         mis1, sus1, bad1 = device_locate(SINGLE_CALL, rs, work, stripes, data, par)
-        assert sus1 == (sus if single == "same" else single), (note, hex_list(sus1))
+        assert sus1 == (sus if single == "same" else single), (note, hexes(sus1))
         assert sus1 == M.suspect_words(shards), note
         assert (mis1, bad1) == (mis, bad), note
     return sus
-
-
-def unexplained_triple(rng):
-    """{shard: value} of three wrong shards in one column for which the model
-    says bit 31 (nearly all do), and one it explains by a pair is skipped."""
-    while True:
-        group = sorted(int(c) for c in rng.choice(14, 3, replace=False))
-        errors = {c: int(rng.integers(1, 256)) for c in group}
-        if PM.column_word(PM.syndrome_of(errors)) == UNEXPLAINED:
-            return errors
 
 
 # ---- device batches --------------------------------------------------------------
@@ -118,7 +68,7 @@ def test_clean_batch(gpu, L):
     for which in LAYOUTS:
         name, data, par, stripes, arenas = clean_case(10, 4, L, 5, which)
         mis, sus, bad = device_locate(PAIRS_CALL, rs, copies(arenas), stripes, data, par)
-        assert mis == [0] * 5 and sus == [0] * 5, (name, hex_list(mis), hex_list(sus))
+        assert mis == [0] * 5 and sus == [0] * 5, (name, hexes(mis), hexes(sus))
         assert bad == 7, name
 
 
@@ -214,7 +164,7 @@ def test_bytes_of_one_dword_are_independent(gpu, L):
     import helyim_amd as H
     rs = H.ReedSolomon(10, 4)
     rng = np.random.default_rng(4)
-    triple = unexplained_triple(rng)
+    triple = PM.unexplained_triple(rng)
     o = (L - 1) // 4 * 4 - 4  # 12 at L = 17, 10232 at 10 KiB: the second dword from the end
     assert o % 4 == 0 and o + 4 <= L
     for which in LAYOUTS:
@@ -239,7 +189,7 @@ def test_three_wrong_shards_are_unexplained(gpu):
     rs = H.ReedSolomon(10, 4)
     S, L = 60, 17
     rng = np.random.default_rng(3)
-    triples = [unexplained_triple(rng) for _ in range(S)]
+    triples = [PM.unexplained_triple(rng) for _ in range(S)]
     for which in LAYOUTS:
         name, data, par, stripes, arenas = clean_case(10, 4, L, S, which)
         work = copies(arenas)
@@ -332,37 +282,7 @@ def test_python_mirror(gpu):
 
 # ---- repair ----------------------------------------------------------------------
 def device_repair(rs, arenas, stripes, layout, expected, preset_left=7):
-    """hec_gpu_repair_pairs_batch on the in-place layout -> (mismatch, suspects,
-    masks, unrepaired, verify words afterwards). Asserts that the arenas equal
-    `expected` in every byte."""
-    import torch
-    import helyim_amd as H
-    S = layout.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    mis, sus, masks = result_words(3, S)
-    left = torch.full((1,), preset_left, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    stream = torch.cuda.current_stream().cuda_stream
-    base = devs[layout.arena].data_ptr() + layout.base
-    rc = H.lib.hec_gpu_repair_pairs_batch(rs.handle, base, layout.stripe_stride, layout.shard_stride, layout.L, S,
-                                          mis.data_ptr(), sus.data_ptr(), masks.data_ptr(), left.data_ptr(), stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(expected, [d.cpu().numpy() for d in devs], stripes)
-    after, = result_words(1, S)
-    rc = H.lib.hec_gpu_verify_batch(rs.handle, base, layout.stripe_stride, layout.shard_stride,
-                                    base + 10 * layout.shard_stride, layout.stripe_stride, layout.shard_stride,
-                                    layout.L, S, after.data_ptr(), None, stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    return read_words(mis, S), read_words(sus, S), read_words(masks, S), int(left.item()), read_words(after, S)
-
-
-def in_place_layout(data, par):
-    """The 14-shard layout of a clean_case whose parity follows its data."""
-    assert par.base == data.base + 10 * data.shard_stride and par.arena == data.arena
-    assert (par.stripe_stride, par.shard_stride) == (data.stripe_stride, data.shard_stride)
-    return data._replace(shards=14)
+    return SH.device_repair("hec_gpu_repair_pairs_batch", rs, arenas, stripes, layout, expected, preset_left)
 
 
 @pytest.mark.parametrize("L", [8192 + 2048, 1000])
@@ -375,7 +295,7 @@ def test_repair(gpu, L):
     import helyim_amd as H
     rs = H.ReedSolomon(10, 4)
     S = 5
-    triple = unexplained_triple(np.random.default_rng(5))
+    triple = PM.unexplained_triple(np.random.default_rng(5))
     hits = {0: [(1, 40, 0x21), (2, 40, 0x84), (7, L - 2, 0x01)],
             1: [(0, 3, 0x10), (3, 3, 0x20), (5, L // 2, 0x30), (9, L // 2, 0x40), (12, L - 1, 0x50)],
             2: [(c, L // 3, v) for c, v in triple.items()],
@@ -388,36 +308,30 @@ def test_repair(gpu, L):
             for shard, pos, value in flips:
                 shard_of(work, stripes, s, shard)[pos] ^= value
         want_sus = PM.suspect_words(gather(work, stripes))
-        assert want_sus == [bits(1, 2, 7), bits(0, 3, 5, 9, 12), UNEXPLAINED, 0, bits(6, 13)], hex_list(want_sus)
+        assert want_sus == [bits(1, 2, 7), bits(0, 3, 5, 9, 12), UNEXPLAINED, 0, bits(6, 13)], hexes(want_sus)
         want_mis = oracle_words(work, stripes, 10, 4)
         expected = copies(arenas)
         for s in (1, 2):  # left as corrupted
             for shard, pos, _ in hits[s]:
                 shard_of(expected, stripes, s, shard)[pos] = shard_of(work, stripes, s, shard)[pos]
         mis, sus, masks, left, after = device_repair(rs, work, stripes, layout, expected)
-        assert sus == want_sus and mis == want_mis, (name, hex_list(sus), hex_list(mis))
-        assert masks == [ALL & ~bits(1, 2, 7), ALL, ALL, ALL, ALL & ~bits(6, 13)], (name, hex_list(masks))
+        assert sus == want_sus and mis == want_mis, (name, hexes(sus), hexes(mis))
+        assert masks == [ALL & ~bits(1, 2, 7), ALL, ALL, ALL, ALL & ~bits(6, 13)], (name, hexes(masks))
         assert left == 7 + 2, name
-        assert after == [0, want_mis[1], want_mis[2], 0, 0], (name, hex_list(after))
+        assert after == [0, want_mis[1], want_mis[2], 0, 0], (name, hexes(after))
         assert want_mis[1] and want_mis[2]
 
 
 # ---- shard files -----------------------------------------------------------------
-BLOCK = 4096
-
-
 def test_files(gpu, tmp_path):
     """A small volume written by the library itself with small blocks. .ec03
     and .ec11 are corrupted over the same 100-byte run, .ec05 elsewhere: the
     entries equal the model on the file bytes, and the existing file locate
     reports bit 31 for the block of the run."""
     import helyim_amd as H
-    from oracle import corc
     base = str(tmp_path / "9")
     large, small = 16 * 1001, 1001
-    open(base + ".dat", "wb").write(corc.splitmix64_bytes(99, 10 * large * 2 + 10 * small * 7 + 55).tobytes())
-    H.generate_ec_files(base, small, large, small)
-    files = [bytearray(open(base + ".ec%02d" % i, "rb").read()) for i in range(14)]
+    files = [bytearray(f) for f in SH.library_volume(base, 99, 10 * large * 2 + 10 * small * 7 + 55)]
     size = len(files[0])
     n_blocks = -(-size // BLOCK)
     assert all(len(f) == size for f in files) and n_blocks >= 8 and size % BLOCK
@@ -433,8 +347,7 @@ def test_files(gpu, tmp_path):
         open(base + ".ec%02d" % shard, "wb").write(files[shard])
 
     def block_words(model, lo):
-        block = np.stack([np.frombuffer(bytes(f[lo:lo + BLOCK]), np.uint8) for f in files])[None]
-        return (lo, BLOCK, M.mismatch_words(block)[0], model.suspect_words(block)[0])
+        return (lo, BLOCK) + SH.block_words(files, lo, lo + BLOCK, M.mismatch_words, model.suspect_words)
 
     lows = [run // BLOCK * BLOCK, x5 // BLOCK * BLOCK]
     want = [block_words(PM, lo) for lo in lows]
@@ -455,71 +368,6 @@ def test_files(gpu, tmp_path):
 
 
 # ---- shard files longer than the two slots -----------------------------------------
-BIG_SIZE = (8 << 20) + 300_007
-# 64 KiB: three chunks of 64 blocks, slot 0 used twice; 0: the 1 MiB default,
-# four blocks per chunk; 5 MiB: larger than a chunk's 4 MiB, so one block per
-# chunk, and the last chunk is a short block alone (3 MiB + 300007)
-BIG_BLOCKS = (65536, 0, 5 << 20)
-EDGE = 4 << 20  # the first chunk edge at 64 KiB and 1 MiB blocks
-RUN = (EDGE - 2048, EDGE + 2048)
-SINGLES = [(11, 5), (2, EDGE - 1), (13, EDGE), (0, (8 << 20) - 1), (10, 8 << 20), (4, BIG_SIZE - 1)]
-NEIGHBOURS = [(6, (6 << 20) + 99), (9, (6 << 20) + 100)]
-TRIPLE_AT = (8 << 20) + 200_009  # the last chunk at every block size; alone in its 64 KiB block
-
-
-def big_volume(seed):
-    """-> (good, bad, cols, triple): fourteen streams of BIG_SIZE bytes, ten of
-    seeded random bytes and the oracle's parity of them (one encode call:
-    parity is bytewise, no block geometry), and a damaged copy. Single flips
-    in six different files, data and parity, at the first and the last byte
-    and on both sides of 4 MiB and 8 MiB; two different files wrong in
-    neighbouring columns; files 2 and 13 wrong in the same columns over a run
-    of 4096 that straddles 4 MiB -- except that of the two columns at the edge
-    itself each is wrong in one of the two files only (file 2 at 4 MiB - 1,
-    file 13 at 4 MiB: the single flips there; a third wrong file in a column
-    of the run would leave it unexplained for good); and one column with
-    three wrong files the pair model calls unexplained. cols: every damaged
-    column, ascending."""
-    from oracle import corc
-    rng = np.random.default_rng(seed)
-    good = [rng.integers(0, 256, BIG_SIZE, dtype=np.uint8) for _ in range(10)] + \
-           [np.zeros(BIG_SIZE, np.uint8) for _ in range(4)]
-    corc.CReedSolomon(10, 4).encode(good)
-    bad = [g.copy() for g in good]
-    for shard, o in SINGLES + NEIGHBOURS:
-        bad[shard][o] ^= 0x33
-    lo, hi = RUN
-    for shard in (2, 13):
-        x = rng.integers(1, 256, hi - lo, dtype=np.uint8)
-        x[EDGE - 1 - lo] = x[EDGE - lo] = 0
-        bad[shard][lo:hi] ^= x
-    triple = unexplained_triple(rng)
-    for c, v in triple.items():
-        bad[c][TRIPLE_AT] ^= v
-    cols = np.array(sorted({o for _, o in SINGLES + NEIGHBOURS} | set(range(lo, hi)) | {TRIPLE_AT}))
-    assert all((bad[i] != good[i]).sum() == sum(1 for o in cols if bad[i][o] != good[i][o]) for i in range(14))
-    return good, bad, cols, triple
-
-
-def big_entries(model, files, cols, width):
-    """The entries of a scrub of `files` at blocks of `width` bytes, from the
-    model on the damaged columns of each block: a column the oracle encoded
-    and nobody touched has a zero syndrome."""
-    want = []
-    for lo in sorted({int(o) // width * width for o in cols}):
-        hi = min(lo + width, BIG_SIZE)
-        sel = cols[(cols >= lo) & (cols < hi)]
-        block = np.stack([f[sel] for f in files])[None]
-        mis, sus = M.mismatch_words(block)[0], model.suspect_words(block)[0]
-        if mis:
-            want.append((lo, hi - lo, mis, sus))
-    return want
-
-
-def ec_names(base):
-    return [base + ".ec%02d" % i for i in range(14)]
-
-
 def test_files_longer_than_the_two_slots(gpu, tmp_path):
     """hec_locate_corrupt_pairs_ec_files over three chunks (64 KiB and 1 MiB
     blocks: slot 0 is used twice, its words collected while later chunks are

@@ -5,22 +5,25 @@ masks.
 Every expected value comes from tests/correct_present_model.py (correct,
 use_masks) and tests/check_model.py, applied stripe by stripe to that stripe's
 own [1, 14, L] bytes as they are in the arena. The arena harness is
-tests/test_gpu_ragged_scrub.py's: absent shards, the slack after each shard up
+tests/scrub_harness.py's Ragged: absent shards, the slack after each shard up
 to its stride and the gaps between stripes hold a sentinel byte. Every device
 call is also a footprint check: the arena that comes back equals the model's
 image byte for byte (slack, gaps and absent shards included), the result
 arrays start stale with a sentinel in word S that must survive, and the
 counters start non-zero and advance by exactly the model's amounts.
 
-The shapes are test_gpu_ragged_scrub.py's LENGTHS and MASKS: one vector, a
+The shapes are the ragged scrub suite's LENGTHS and MASKS: one vector, a
 tail, a second map entry, one and three bit-sliced entries, every value of r."""
 import numpy as np
 import pytest
 
 import check_model as C
 import correct_present_model as M
-from test_gpu_ragged_scrub import (ALL, FILL, LENGTHS, MASKS, NINE, R1, R2, R3, R4, TEN, UNEXPLAINED, Ragged,
-                                   clean_stripe, flip_cases, hexes, kernel_name, read_words, rs104, words)
+import scrub_harness as SH
+from scrub_harness import (ALL, FILL, NINE, R1, R2, R3, R4, RAGGED_LENGTHS as LENGTHS, RAGGED_MASKS as MASKS, Ragged,
+                           TEN, UNEXPLAINED, hexes, ragged_flip_cases as flip_cases,
+                           ragged_kernel_name as kernel_name, ragged_stripe as clean_stripe, read_words, result_words,
+                           rs104)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,9 +50,7 @@ def model(b, min_spares=2):
 
 
 def counters():
-    import torch
-    small = [torch.full((1,), v, dtype=torch.int32, device="cuda") for v in PRESET[:3]]
-    return small + [torch.full((1,), PRESET[3], dtype=torch.int64, device="cuda")]
+    return SH.preset_counters(PRESET, wide_last=True)
 
 
 def advanced(ts):
@@ -58,27 +59,18 @@ def advanced(ts):
 
 def check_correct(rs, b, min_spares=2, note=None, want_sus=None):
     """correct_ragged on b against the model -> (image, check, suspects)."""
-    import torch
     import helyim_amd as H
     img, want_chk, want, left, changed = model(b, min_spares)
     if want_sus is not None:
         assert want == want_sus, (note, hexes(want), hexes(want_sus))
-    S = b.S
-    dev = torch.from_numpy(b.arena).cuda()
-    chk, sus = words(2, S)
-    bad, unchecked, uncorrected, nbytes = cs = counters()
-    torch.cuda.synchronize()
-    H.correct_ragged(rs, dev, b.descs(), min_spares, check=chk, suspects=sus, bad_stripes=bad, unchecked=unchecked,
-                     uncorrected=uncorrected, corrected_bytes=nbytes)
-    torch.cuda.synchronize()
-    got = dev.cpu().numpy()
-    diff = np.flatnonzero(got != img)
-    assert diff.size == 0, (note, "the arena differs from the model's image at", diff[:8].tolist())
-    chk, sus = read_words(chk, S), read_words(sus, S)
+    (chk, sus), got, _ = SH.device_ragged(H.correct_ragged, rs, b, ("check", "suspects"),
+                                          ("bad_stripes", "unchecked", "uncorrected", "corrected_bytes"), PRESET,
+                                          wide_last=True, min_spares=min_spares, expected=img, note=note)
+    cs = [g - p for g, p in zip(got, PRESET)]
     assert chk == want_chk, (note, hexes(chk), hexes(want_chk))
     assert sus == want, (note, hexes(sus), hexes(want))
-    assert advanced(cs) == [sum(1 for w in want_chk if w), C.unchecked_count(b.masks()), left, changed], \
-        (note, advanced(cs), left, changed)
+    assert cs == [sum(1 for w in want_chk if w), C.unchecked_count(b.masks()), left, changed], \
+        (note, cs, left, changed)
     check_correct.counted = (left, changed)  # the model's, which the device's equal
     return img, chk, sus
 
@@ -87,7 +79,6 @@ def check_reconstruct(rs, b, min_spares=2, note=None):
     """reconstruct_corrected_ragged on b against the models -> (arena, use masks).
     A rebuilt stripe's survivors must be their originals after the correct
     (asserted on the CPU), so its holes are expected to hold the originals."""
-    import torch
     import helyim_amd as H
     img, want_chk, want_sus, _, changed = model(b, min_spares)
     want_use, want_left = M.use_masks(b.masks(), want_chk, want_sus, min_spares)
@@ -103,21 +94,14 @@ def check_reconstruct(rs, b, min_spares=2, note=None):
                     assert np.array_equal(img[o:o + L], clean_stripe(L, s)[i]), (note, s, i)
                 else:
                     img[o:o + L] = clean_stripe(L, s)[i]
-    S = b.S
-    dev = torch.from_numpy(b.arena).cuda()
-    chk, sus, use = words(3, S)
-    bad, _, unrepaired, nbytes = cs = counters()
-    torch.cuda.synchronize()
-    H.reconstruct_corrected_ragged(rs, dev, b.descs(), min_spares, check=chk, suspects=sus, use_masks=use,
-                                   bad_stripes=bad, unrepaired=unrepaired, corrected_bytes=nbytes)
-    torch.cuda.synchronize()
-    got = dev.cpu().numpy()
-    diff = np.flatnonzero(got != img)
-    assert diff.size == 0, (note, "the arena differs from the expected image at", diff[:8].tolist())
-    assert read_words(chk, S) == want_chk and read_words(sus, S) == want_sus, note
-    use = read_words(use, S)
+    presets = (PRESET[0], PRESET[2], PRESET[3])
+    (chk, sus, use), got, dev = SH.device_ragged(H.reconstruct_corrected_ragged, rs, b, ("check", "suspects", "use_masks"),
+                                                 ("bad_stripes", "unrepaired", "corrected_bytes"), presets,
+                                                 wide_last=True, min_spares=min_spares, expected=img, note=note)
+    assert chk == want_chk and sus == want_sus, note
     assert use == want_use, (note, hexes(use), hexes(want_use))
-    assert advanced(cs) == [short, 0, want_left, changed], (note, advanced(cs), short, want_left, changed)
+    cs = [g - p for g, p in zip(got, presets)]
+    assert cs == [short, want_left, changed], (note, cs, short, want_left, changed)
     return dev, use
 
 
@@ -412,7 +396,7 @@ def test_five_calls_back_to_back(gpu):
     state = []
     for b, recon, *_ in runs:
         dev = torch.from_numpy(b.arena).cuda()
-        state.append((dev, words(3, b.S), counters()))
+        state.append((dev, result_words(3, b.S), counters()))
     torch.cuda.synchronize()
     for (b, recon, *_), (dev, (chk, sus, use), cs) in zip(runs, state):
         if recon:

@@ -14,138 +14,25 @@ stale with a sentinel in word S that must survive, the counters start non-zero.
 The shapes are the smallest that reach each path: 16 bytes (one lane's vector),
 1000 (a tail with an 8-byte remainder), 2048, 4096 + 16 (a second map entry of
 one vector), 8192 (one bit-sliced entry), 24576 (three)."""
-import functools
-
 import numpy as np
 import pytest
 
 import check_model as C
-from oracle import corc
+import scrub_harness as SH
+from scrub_harness import (ALL, NINE, R1, R2, R3, R4, RAGGED_LENGTHS as LENGTHS, RAGGED_MASKS as MASKS, Ragged, TEN,
+                           UNEXPLAINED, hexes, ragged_flip_cases as flip_cases, ragged_kernel_name as kernel_name,
+                           ragged_stripe as clean_stripe, rs104)
 
 pytestmark = pytest.mark.gpu
 
-UNEXPLAINED, ALL = C.UNEXPLAINED, C.ALL
-SENTINEL_WORD = 0x5A5AA5A5
-FILL = 0xEE
-LENGTHS = (16, 1000, 2048, 4096 + 16, 8192, 24576)
-
-
-def lost(*ids):
-    return ALL & ~sum(1 << i for i in ids)
-
-
-R4, R3, R2, R1 = ALL, lost(3), lost(0, 12), lost(2, 7, 11)
-TEN, NINE = lost(1, 4, 9, 13), lost(0, 5, 6, 10, 12)
-MASKS = (R4, R3, R2, R1, TEN, NINE)
-
-
-def r16(n):
-    return (n + 15) // 16 * 16
-
-
-@functools.lru_cache(maxsize=None)
-def clean_stripe(L, seed=0):
-    """[14, L] with the C oracle's parity (never modified: batches hold copies)."""
-    rng = np.random.default_rng(7919 * seed + L)
-    st = rng.integers(0, 256, (1, 14, L), dtype=np.uint8)
-    st[:, 10:] = corc.encode_stripes(np.ascontiguousarray(st[:, :10]))
-    st.setflags(write=False)
-    return st[0]
-
-
-class Ragged:
-    """Stripes (L, mask) back to back in one arena; absent shards, the slack of
-    every shard and every gap hold FILL."""
-
-    def __init__(self, shapes, present=None):
-        self.shapes = [(int(L), int(m)) for L, m in shapes]
-        self.S = len(self.shapes)
-        self.offs, self.strides = [], []
-        off = 64
-        for L, _ in self.shapes:
-            stride = r16(L) + 48
-            self.offs.append(off)
-            self.strides.append(stride)
-            off += 14 * stride + 64
-        self.arena = np.full(off, FILL, dtype=np.uint8)
-        for s, (L, m) in enumerate(self.shapes):
-            held = m if present is None else present[s]  # which shards hold data in memory
-            for i in range(14):
-                if held >> i & 1:
-                    self.shard(s, i)[:] = clean_stripe(L, s)[i]
-
-    def shard(self, s, i):
-        o = self.offs[s] + i * self.strides[s]
-        return self.arena[o:o + self.shapes[s][0]]
-
-    def flip(self, s, i, pos, xor=0x41):
-        """pos may be shard_len and past it: the slack up to the stride."""
-        self.arena[self.offs[s] + i * self.strides[s] + pos] ^= xor
-
-    def gather(self, s, arena=None):
-        a = self.arena if arena is None else arena
-        L = self.shapes[s][0]
-        return np.stack([a[self.offs[s] + i * self.strides[s]:][:L] for i in range(14)])
-
-    def masks(self):
-        return [m for _, m in self.shapes]
-
-    def descs(self, masks=None):
-        masks = self.masks() if masks is None else masks
-        return [(self.offs[s], self.strides[s], self.shapes[s][0], masks[s]) for s in range(self.S)]
-
-    def entries(self, chunk=4096):
-        """Map entries of the table form: none for a stripe that is not read."""
-        return sum(-(-L // chunk) for L, m in self.shapes if bin(m & ALL).count("1") > 10)
-
-    def model(self):
-        chk, sus = [], []
-        for s, (_, m) in enumerate(self.shapes):
-            st = self.gather(s)[None]
-            chk += C.check_words(st, [m])
-            sus += C.suspect_words(st, [m])
-        return chk, sus
-
-
-def words(n, S):
-    import torch
-    ts = [torch.full((S + 1,), -1, dtype=torch.int32, device="cuda") for _ in range(n)]  # stale 0xFFFFFFFF
-    for t in ts:
-        t[S] = SENTINEL_WORD
-    return ts
-
-
-def read_words(t, S):
-    out = t.cpu().numpy().view(np.uint32)
-    assert int(out[S]) == SENTINEL_WORD
-    return [int(w) for w in out[:S]]
-
-
 def device_scrub(rs, b, locate=True, preset=(7, 5), masks=None):
     """The ragged locate (or the verify alone) on b -> (check, suspects,
-    bad_stripes, unchecked). Asserts the footprint."""
-    import torch
+    bad_stripes, unchecked), the counters without their presets. Asserts the
+    footprint."""
     import helyim_amd as H
-    S = b.S
-    dev = torch.from_numpy(b.arena).cuda()
-    assert dev.data_ptr() % 256 == 0
-    chk, sus = words(2, S)
-    bad = torch.full((1,), preset[0], dtype=torch.int32, device="cuda")
-    unchecked = torch.full((1,), preset[1], dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    if locate:
-        H.locate_corrupt_ragged(rs, dev, b.descs(masks), check=chk, suspects=sus, bad_stripes=bad,
-                                unchecked=unchecked)
-    else:
-        H.verify_ragged(rs, dev, b.descs(masks), check=chk, bad_stripes=bad, unchecked=unchecked)
-    torch.cuda.synchronize()
-    assert np.array_equal(dev.cpu().numpy(), b.arena), "the scrub wrote into the arena"
-    return (read_words(chk, S), read_words(sus, S) if locate else None, int(bad.item()) - preset[0],
-            int(unchecked.item()) - preset[1])
-
-
-def hexes(ws):
-    return [hex(w) for w in ws]
+    fn, names = (H.locate_corrupt_ragged, ("check", "suspects")) if locate else (H.verify_ragged, ("check",))
+    ws, (bad, unchecked), _ = SH.device_ragged(fn, rs, b, names, ("bad_stripes", "unchecked"), preset, masks=masks)
+    return ws[0], ws[1] if locate else None, bad - preset[0], unchecked - preset[1]
 
 
 def check_batch(rs, b, by_construction=None, note=None):
@@ -161,16 +48,6 @@ def check_batch(rs, b, by_construction=None, note=None):
     chk1, _, bad1, unchecked1 = device_scrub(rs, b, locate=False)
     assert (chk1, bad1, unchecked1) == (chk, bad, unchecked), note
     return chk, sus
-
-
-def kernel_name(b):
-    import helyim_amd as H
-    return H.ragged_scrub_kernel_name(b.descs())
-
-
-def rs104():
-    import helyim_amd as H
-    return H.ReedSolomon(10, 4)
 
 
 # ---- 1. clean mixed batch ------------------------------------------------------
@@ -193,18 +70,6 @@ def test_clean_mixed_batch(gpu):
 
 
 # ---- 2. single flipped bytes ---------------------------------------------------
-def flip_cases(lengths, masks):
-    """(L, mask, shard, pos): the first and the last byte, in a shard of B and in one of E."""
-    out = []
-    for L in lengths:
-        for m in masks:
-            B, E = C.split(m)
-            for n, pos in enumerate((0, L - 1)):
-                out.append((L, m, B[(3 + n + L) % 10], pos))
-                out.append((L, m, E[(n + L) % len(E)], pos))
-    return out
-
-
 @pytest.mark.parametrize("form", ["table", "bit-sliced"])
 def test_single_flipped_bytes(gpu, form):
     """One flipped byte per stripe names its shard (r >= 2) or sets bit 31

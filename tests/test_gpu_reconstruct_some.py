@@ -10,7 +10,7 @@ import pytest
 
 import footprint as F
 import some_model as M
-from test_gpu_footprint import HOST_PATHS, HostArenas, host_path, present_of, stream_ptr, to_device, to_host
+from footprint import HOST_PATHS, HostArenas, host_path, present_of, stream_ptr, to_device, to_host
 
 pytestmark = pytest.mark.gpu
 

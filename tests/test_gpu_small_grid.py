@@ -10,8 +10,10 @@ to 960 GB of shards) at the product's limits.
 
 One child process per file (`python -m pytest <file> -m gpu` with HEC_LIB_PATH
 set); tests/small_grid_probe.py runs first in the child and ends it unless the
-limits are live. A child that dies of a signal or runs out of time fails every
-remaining file without starting another process on the device."""
+limits are live. Every child has a time limit of its own. A child that dies of
+a signal or runs out of time fails every remaining file without starting
+another process on the device: all children start from run_child below, so
+the rule holds by construction."""
 import os
 import re
 import subprocess
@@ -28,7 +30,31 @@ VARIANT = os.path.join(ROOT, "build", "variants", "libhec_smallgrid.so")
 CHILD_TIMEOUT = 300  # seconds; a child takes about what its file takes with the product library
 
 FILES = ["test_gpu_check.py", "test_gpu_locate.py", "test_gpu_verify.py", "test_gpu_generic_codecs.py",
-         "test_gpu_footprint.py", "test_gpu_intervals.py", "test_gpu_parity.py"]
+         "test_gpu_footprint.py", "test_gpu_intervals.py", "test_gpu_parity.py",
+         # With four workgroups every batch of the file runs second and later iterations of the correct
+         # kernel's grid-stride loop, stores included, and the verify launches ahead of it go in several
+         # ranges. Largest device batch 2053 stripes of 4 KiB; largest file scrub fourteen shard files of
+         # 8 MiB + 300007 bytes in blocks of up to 5 MiB (one stripe per block, about 120 MB in all).
+         "test_gpu_correct.py",
+         # The same for the masked correct kernel; the check launches ahead of it go in several ranges and
+         # the use-mask kernel goes round after 1024 stripes. Largest batch 2053 stripes of 4 KiB.
+         "test_gpu_correct_present.py",
+         # Second and later iterations of the pair kernel's grid-stride loop on every batch; the verify,
+         # mask and reconstruct launches around it go in several ranges and rounds. Sizes as test_gpu_correct.py.
+         "test_gpu_locate_pairs.py",
+         # The clean batch and the batch of single flips have more than 100 map entries each
+         # (test_ragged_scrub_batches_pass_one_launch_of_the_variant), so pass 1 goes in several launches
+         # (launch_ragged's block_base and XCD eighths per launch), and with four workgroups pass 2 runs
+         # second and later rounds over the map on every batch with more than four 4 KiB ranges.
+         "test_gpu_ragged_scrub.py",
+         # The same for the correct pass (test_ragged_correct_batches_pass_one_launch_of_the_variant); the
+         # decode of the corrected reconstruct goes through launch_ragged's launches from its own map.
+         "test_gpu_ragged_correct.py",
+         # Every strided batch goes in stripe ranges of at most 100 workgroups, where the want words have to
+         # advance with the masks; the generic kernel runs second and later iterations of its grid-stride
+         # loop, and the ragged batches are split into several launches.
+         "test_gpu_reconstruct_some.py"]
+TIMEOUTS = {"test_gpu_reconstruct_some.py": 420}  # about a minute with the product library; the others CHILD_TIMEOUT
 
 # Deselected under the variant, by node id. Only two kinds: shapes of more than
 # 2 GiB of device memory or more than 2^20 stripes ("size"), and expectations
@@ -73,6 +99,12 @@ DESELECT = {
         ("test_strided_batch_shard_len_near_4gib[4294975488]", "size: 56 GiB in HBM"),
         ("test_config5_whole_batch_vs_oracle", "size: 32 GiB in HBM, and 17 of this child's 26 s"),
     ],
+    "test_gpu_correct.py": [],
+    "test_gpu_correct_present.py": [],
+    "test_gpu_locate_pairs.py": [],
+    "test_gpu_ragged_scrub.py": [],
+    "test_gpu_ragged_correct.py": [],
+    "test_gpu_reconstruct_some.py": [],
 }
 
 _stopped = []  # why no further child may start (a child died of a signal or ran out of time)
@@ -113,20 +145,39 @@ def test_variant_is_built_and_its_limits_are_live():
         assert product["hec_decode_kernel_name", 101 * 2048].startswith("rs104_narrow_kernel<DEC=true")
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", FILES)
-def test_suite_against_small_grid(gpu, name):
+def test_ragged_scrub_batches_pass_one_launch_of_the_variant():
+    """The entry counts FILES' comment on test_gpu_ragged_scrub.py relies on, from the file's own shapes."""
+    import test_gpu_ragged_scrub as T
+    clean = T.Ragged([(L, m) for L in T.LENGTHS for m in T.MASKS] + [(24576, m) for m in (T.R3, T.R2, T.R1) * 3])
+    flips = T.Ragged([(L, m) for L, m, _, _ in T.flip_cases(T.LENGTHS, (T.R4, T.R3, T.R2, T.R1))])
+    assert clean.entries() > probe.MAX_LAUNCH_BLOCKS and flips.entries() > 2 * probe.MAX_LAUNCH_BLOCKS
+    assert clean.entries() > probe.LOCATE_MAX_BLOCKS
+
+
+def test_ragged_correct_batches_pass_one_launch_of_the_variant():
+    """The same for test_gpu_ragged_correct.py."""
+    import test_gpu_ragged_correct as T
+    clean = T.Ragged(T.clean_shapes())
+    flips = T.Ragged([(L, m) for L, m, _, _ in T.single_flip_cases("table")])
+    assert clean.entries() > probe.MAX_LAUNCH_BLOCKS and flips.entries() > 2 * probe.MAX_LAUNCH_BLOCKS
+    assert clean.entries() > probe.LOCATE_MAX_BLOCKS and flips.entries() > probe.LOCATE_MAX_BLOCKS
+
+
+def run_child(name, deselect, timeout):
+    """tests/<name> in a child process against the variant; every child of this
+    module starts here, and none starts after one died of a signal or ran out
+    of time."""
     assert not _stopped, "not started: " + _stopped[0]
     assert os.path.exists(VARIANT), VARIANT + " is missing: `make all` builds it"
     cmd = [sys.executable, "-m", "pytest", "-p", "small_grid_probe", os.path.join("tests", name), "-m", "gpu", "-q",
            "--maxfail=5", "-p", "no:cacheprovider"]
-    for node, _reason in DESELECT[name]:
+    for node, _reason in deselect:
         cmd += ["--deselect", f"tests/{name}::{node}"]
     t0 = time.monotonic()
     try:
-        r = subprocess.run(cmd, env=child_env(), cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+        r = subprocess.run(cmd, env=child_env(), cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     except subprocess.TimeoutExpired as e:
-        _stopped.append(f"the child of {name} was killed after {CHILD_TIMEOUT} s")
+        _stopped.append(f"the child of {name} was killed after {timeout} s")
         out = e.stdout if isinstance(e.stdout, str) else (e.stdout or b"").decode(errors="replace")
         pytest.fail(_stopped[0] + "\n" + tail(out))
     wall = time.monotonic() - t0
@@ -139,4 +190,10 @@ def test_suite_against_small_grid(gpu, name):
           f"{passed} passed, {wall:.1f} s")
     assert r.returncode == 0, f"{name} under the small-grid variant (return code {r.returncode}):\n{tail(out)}"
     assert passed > 0, tail(out)
-    assert deselected == len(DESELECT[name]), f"a deselected node id of {name} matches no test:\n{tail(out)}"
+    assert deselected == len(deselect), f"a deselected node id of {name} matches no test:\n{tail(out)}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FILES)
+def test_suite_against_small_grid(gpu, name):
+    run_child(name, DESELECT[name], TIMEOUTS.get(name, CHILD_TIMEOUT))

@@ -19,89 +19,21 @@ import numpy as np
 import pytest
 
 import footprint as F
+import scrub_harness as SH
 from oracle import corc
+from scrub_harness import SENTINEL, clean_case, copies, flip_positions, oracle_words, shard_of
 
 pytestmark = pytest.mark.gpu
 
 INVALID_ARGUMENT, EC_SHARD_SIZE, SHARD_NOT_FOUND = 66, 34, 49
-SENTINEL = 0x5A5AA5A5
 LENGTHS = (8192, 16384, 8192 + 2048, 4096 + 16, 1000, 17, 1)
-
-
-def layouts(k, m, L, S):
-    """(name, data layout, parity layout): stripe-major with a 48-byte shard
-    gap, shard-major, data and parity in separate arenas, an odd base."""
-    n = k + m
-    a = F.stripe_major(n, L, S, F.r16(L) + 48, 16)
-    b = F.shard_major(n, L, S, F.r16(L) + 16, 48)
-    d = F.stripe_major(n, L, S, F.r16(L) + 16, 16, base=F.SLACK + 3)
-    yield "stripe-major gap 48", a.sub(0, k), a.sub(k, m)
-    yield "shard-major", b.sub(0, k), b.sub(k, m)
-    yield "separate arenas", F.stripe_major(k, L, S, F.r16(L) + 48, 16), \
-        F.shard_major(m, L, S, F.r16(L) + 16, 48, arena=1)
-    yield "odd base", d.sub(0, k), d.sub(k, m)
-
-
-@functools.lru_cache(maxsize=None)
-def clean_case(k, m, L, S, which):
-    """A layout and its arenas with correct parity everywhere (never modified:
-    tests corrupt copies). -> (name, data, par, stripes, arenas)."""
-    name, data, par = list(layouts(k, m, L, S))[which]
-    stripes = F.stripes_of(data, par)
-    rng = np.random.default_rng(1000 * L + 10 * S + which + 7 * k + m)
-    raw = [F.random_arena(sz, rng) for sz in F.arena_sizes(stripes)]
-    arenas = F.plan_encode(raw, stripes, k, m).expected  # the raw bytes with the oracle's parity in place
-    for a in arenas:
-        a.setflags(write=False)
-    return name, data, par, stripes, arenas
-
-
-def copies(arenas):
-    return [np.array(a, copy=True) for a in arenas]
-
-
-def shard_of(arenas, stripes, s, i):
-    a, o = stripes[s].locs[i]
-    return arenas[a][o:o + stripes[s].L]
-
-
-def oracle_words(arenas, stripes, k, m):
-    rs = corc.CReedSolomon(k, m)
-    words = []
-    for s, st in enumerate(stripes):
-        bufs = [shard_of(arenas, stripes, s, i).copy() for i in range(k)] + \
-               [np.zeros(st.L, np.uint8) for _ in range(m)]
-        rs.encode(bufs)
-        words.append(sum(1 << j for j in range(m) if (bufs[k + j] != shard_of(arenas, stripes, s, k + j)).any()))
-    return words
 
 
 def device_verify(rs, arenas, stripes, data, par, preset_bad=7):
     """Run hec_gpu_verify_batch on the arenas -> (words [S], bad_stripes).
     Asserts the footprint: arenas unchanged, word S untouched."""
-    import torch
-    import helyim_amd as H
-    S = data.S
-    devs = [torch.from_numpy(a).cuda() for a in arenas]
-    assert all(d.data_ptr() % 256 == 0 for d in devs)
-    res = torch.full((S + 1,), -1, dtype=torch.int32, device="cuda")  # 0xFFFFFFFF: stale words must not leak
-    res[S] = SENTINEL
-    bad = torch.full((1,), preset_bad, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    rc = H.lib.hec_gpu_verify_batch(rs.handle, devs[data.arena].data_ptr() + data.base, data.stripe_stride,
-                                    data.shard_stride, devs[par.arena].data_ptr() + par.base, par.stripe_stride,
-                                    par.shard_stride, data.L, S, res.data_ptr(), bad.data_ptr(),
-                                    torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, (rc, H._lib.last_detail())
-    torch.cuda.synchronize()
-    F.assert_unchanged(arenas, [d.cpu().numpy() for d in devs], stripes)
-    out = res.cpu().numpy().view(np.uint32)
-    assert int(out[S]) == SENTINEL
-    return [int(w) for w in out[:S]], int(bad.item())
-
-
-def flip_positions(L):
-    return sorted({p for p in (0, L - 1, 4095, 4096, 16 * 255, 8191, 8192) if 0 <= p < L})
+    (words,), (bad,) = SH.device_words("hec_gpu_verify_batch", rs, arenas, stripes, data, par, 1, [preset_bad])
+    return words, bad
 
 
 # ---- device batches --------------------------------------------------------------

@@ -6,19 +6,19 @@ import os
 
 import pytest
 
+from abi_util import (EC_SHARD_SIZE, EMPTY_SHARD, INVALID_ARGUMENT, L, P, SHARD_NOT_FOUND, c_parameters, call,  # noqa: F401
+                      volume)
 from conftest import ROOT
 
-INVALID_ARGUMENT, EMPTY_SHARD, EC_SHARD_SIZE, SHARD_NOT_FOUND = 66, 11, 34, 49
-P, L = 0x1000, 4096
 NAMES = ("hec_gpu_locate_corrupt_batch", "hec_gpu_repair_batch", "hec_locate_corrupt_ec_files")
 
 
-def gpu_locate(lib, rs, data=P, ds=14 * L, dsh=L, par=P + 10 * L, ps=14 * L, psh=L, length=L, n=2, res=P, sus=P):
-    return lib.hec_gpu_locate_corrupt_batch(rs, data, ds, dsh, par, ps, psh, length, n, res, sus, None, None)
+def gpu_locate(lib, rs, **args):
+    return call("hec_gpu_locate_corrupt_batch", rs, **args)
 
 
-def gpu_repair(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, res=P, sus=P, masks=P):
-    return lib.hec_gpu_repair_batch(rs, shards, st, sh, length, n, res, sus, masks, None, None)
+def gpu_repair(lib, rs, **args):
+    return call("hec_gpu_repair_batch", rs, **args)
 
 
 def test_symbols_and_signatures():
@@ -94,8 +94,7 @@ def test_file_locate_checks_need_no_device(tmp_path):
     with pytest.raises(H.ShardNotFound):
         H.locate_corrupt_ec_files(str(tmp_path / "missing"))
     base = tmp_path / "v"
-    for i in range(14):
-        open(str(base) + ".ec%02d" % i, "wb").write(b"\0" * (700 if i != 6 else 650))
+    volume(base, odd=(6, 650))
     for block in (1000, 4095, 4096 + 512):
         assert locate(base, block) == INVALID_ARGUMENT, block
     assert locate(base, 4096) == EC_SHARD_SIZE
@@ -108,8 +107,7 @@ def test_file_locate_checks_need_no_device(tmp_path):
     with pytest.raises(ValueError):
         H.locate_corrupt_ec_files(str(base), 4096, cap=-1)
     empty = tmp_path / "e"
-    for i in range(14):
-        open(str(empty) + ".ec%02d" % i, "wb").close()
+    volume(empty, size=0)
     assert H.locate_corrupt_ec_files(str(empty), 4096) == (0, 0, [])
 
 

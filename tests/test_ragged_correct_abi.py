@@ -6,24 +6,18 @@ import os
 
 import pytest
 
+from abi_util import EMPTY_SHARD, FULL, INVALID_ARGUMENT, P, call_ragged, descs_of, two  # noqa: F401
 from conftest import ROOT
-from test_ragged_scrub_abi import EMPTY_SHARD, FULL, INVALID_ARGUMENT, P, descs_of, two
 
 NAMES = ("hec_gpu_correct_ragged", "hec_gpu_reconstruct_corrected_ragged")
 
 
-def correct(lib, rs, base=P, descs="two", n=None, res=P, sus=P, min_spares=2):
-    d = two() if isinstance(descs, str) else descs
-    return lib.hec_gpu_correct_ragged(rs, base, None if d is None else d.ctypes.data,
-                                      (0 if d is None else len(d)) if n is None else n, min_spares, res, sus, None,
-                                      None, None, None, None)
+def correct(lib, rs, **args):
+    return call_ragged("hec_gpu_correct_ragged", rs, **args)
 
 
-def reconstruct(lib, rs, base=P, descs="two", n=None, res=P, sus=P, use=P, min_spares=2):
-    d = two() if isinstance(descs, str) else descs
-    return lib.hec_gpu_reconstruct_corrected_ragged(rs, base, None if d is None else d.ctypes.data,
-                                                    (0 if d is None else len(d)) if n is None else n, min_spares,
-                                                    res, sus, use, None, None, None, None)
+def reconstruct(lib, rs, **args):
+    return call_ragged("hec_gpu_reconstruct_corrected_ragged", rs, **args)
 
 
 CALLS = {correct: ("base", "res", "sus"), reconstruct: ("base", "res", "sus", "use")}

@@ -3,40 +3,20 @@ and every argument and descriptor check that precedes device work (fake
 non-null pointers are never touched)."""
 import os
 
-import numpy as np
 import pytest
 
+from abi_util import EMPTY_SHARD, FULL, INVALID_ARGUMENT, P, call_ragged, descs_of, two  # noqa: F401
 from conftest import ROOT
 
-INVALID_ARGUMENT, EMPTY_SHARD = 66, 11
-P, FULL = 0x1000, 0x3FFF
 NAMES = ("hec_gpu_verify_ragged", "hec_gpu_locate_corrupt_ragged", "hec_ragged_scrub_kernel_name")
 
 
-def descs_of(rows):
-    import helyim_amd.batch as B
-    return np.array([tuple(r) for r in rows], dtype=B.desc_dtype())
+def verify(lib, rs, **args):
+    return call_ragged("hec_gpu_verify_ragged", rs, **args)
 
 
-def two(**change):
-    """Two valid stripes back to back; change = fields of stripe 1."""
-    rows = [dict(offset=0, shard_stride=4096, shard_len=4096, present_mask=FULL),
-            dict(offset=14 * 4096, shard_stride=1008, shard_len=1000, present_mask=FULL & ~(1 << 3))]
-    rows[1].update(change)
-    return descs_of([(r["offset"], r["shard_stride"], r["shard_len"], r["present_mask"]) for r in rows])
-
-
-def verify(lib, rs, base=P, descs="two", n=None, res=P):
-    d = two() if isinstance(descs, str) else descs
-    return lib.hec_gpu_verify_ragged(rs, base, None if d is None else d.ctypes.data,
-                                     (0 if d is None else len(d)) if n is None else n, res, None, None, None)
-
-
-def locate(lib, rs, base=P, descs="two", n=None, res=P, sus=P):
-    d = two() if isinstance(descs, str) else descs
-    return lib.hec_gpu_locate_corrupt_ragged(rs, base, None if d is None else d.ctypes.data,
-                                             (0 if d is None else len(d)) if n is None else n, res, sus, None, None,
-                                             None)
+def locate(lib, rs, **args):
+    return call_ragged("hec_gpu_locate_corrupt_ragged", rs, **args)
 
 
 CALLS = {verify: ("base", "res"), locate: ("base", "res", "sus")}

@@ -8,24 +8,22 @@ import re
 import numpy as np
 import pytest
 
+from abi_util import L, P, c_parameters, call, codes, has_gpu
 from conftest import ROOT
-from test_abi import has_gpu
-from test_correct_abi import c_parameters, codes
 
 C = codes()
 INVALID_ARGUMENT, EMPTY_SHARD, NO_DEVICE = C["HEC_ERR_INVALID_ARGUMENT"], C["HEC_ERR_EMPTY_SHARD"], C["HEC_ERR_NO_DEVICE"]
-P, L = 0x1000, 4096
 NEW = ("hec_gpu_reconstruct_some_batch", "hec_gpu_reconstruct_some_ragged", "hec_host_reconstruct_some_batch",
        "hec_rs_reconstruct_some", "hec_rs_reconstruct_some_batch", "hec_reconstruct_some_kernel_name",
        "hec_reconstruct_some_batch_kernel_name")
 
 
-def gpu_some(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, wants=P):
-    return lib.hec_gpu_reconstruct_some_batch(rs, shards, st, sh, length, n, masks, wants, None, None)
+def gpu_some(lib, rs, **args):
+    return call("hec_gpu_reconstruct_some_batch", rs, **args)
 
 
-def host_some(lib, rs, shards=P, st=14 * L, sh=L, length=L, n=2, masks=P, wants=P):
-    return lib.hec_host_reconstruct_some_batch(rs, shards, st, sh, length, n, masks, wants, None)
+def host_some(lib, rs, **args):
+    return call("hec_host_reconstruct_some_batch", rs, **args)
 
 
 STRIDED = (gpu_some, host_some)

@@ -5,7 +5,7 @@ share their prologues, so the order of the checks inside a prologue is pinned
 here, for every strided, pairs, present-mask and ragged scrub call."""
 import pytest
 
-from test_ragged_scrub_abi import two
+from abi_util import two
 
 INVALID_ARGUMENT, EMPTY_SHARD = 66, 11
 P, L = 0x1000, 4096

@@ -4,16 +4,15 @@ import ctypes
 
 import pytest
 
-INVALID_ARGUMENT, EMPTY_SHARD, EC_SHARD_SIZE, SHARD_NOT_FOUND = 66, 11, 34, 49
-P, L = 0x1000, 4096
+from abi_util import EC_SHARD_SIZE, EMPTY_SHARD, INVALID_ARGUMENT, L, P, SHARD_NOT_FOUND, call, volume  # noqa: F401
 
 
-def gpu_verify(lib, rs, data=P, ds=14 * L, dsh=L, par=P + 10 * L, ps=14 * L, psh=L, length=L, n=2, res=P):
-    return lib.hec_gpu_verify_batch(rs, data, ds, dsh, par, ps, psh, length, n, res, None, None)
+def gpu_verify(lib, rs, **args):
+    return call("hec_gpu_verify_batch", rs, **args)
 
 
-def host_verify(lib, rs, data=P, ds=14 * L, dsh=L, par=P + 10 * L, ps=14 * L, psh=L, length=L, n=2, res=P):
-    return lib.hec_host_verify_batch(rs, data, ds, dsh, par, ps, psh, length, n, res, None)
+def host_verify(lib, rs, **args):
+    return call("hec_host_verify_batch", rs, **args)
 
 
 @pytest.mark.parametrize("call", [gpu_verify, host_verify])
@@ -58,8 +57,7 @@ def test_file_scrub_checks_need_no_device(tmp_path):
     with pytest.raises(H.ShardNotFound):
         H.verify_ec_files(str(tmp_path / "missing"))
     base = tmp_path / "v"
-    for i in range(14):
-        open(str(base) + ".ec%02d" % i, "wb").write(b"\0" * (700 if i != 6 else 650))
+    volume(base, odd=(6, 650))
     for block in (1000, 4095, 4096 + 512):
         assert scrub(base, block) == INVALID_ARGUMENT, block
     assert scrub(base, 4096) == EC_SHARD_SIZE
