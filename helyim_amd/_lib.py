@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HEC_LIB_PATH: measurement and test builds only (tools/tune.py and
-# tests/test_gpu_small_grid.py load the Makefile's kernel variants).
+# tests/test_gpu_small_grid.py and test_gpu_small_chunk.py load the Makefile's variants).
 LIB_PATH = os.environ.get("HEC_LIB_PATH") or os.path.join(_HERE, "libhec.so")
 
 if not os.path.exists(LIB_PATH):

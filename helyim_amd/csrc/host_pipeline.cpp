@@ -9,12 +9,12 @@
 #include <cstring>
 
 #include "hec_internal.hpp"
+#include "host_chunks.hpp"  // kChunkBytes: target bytes of one chunk's shards
 
 namespace hec {
 namespace {
 
 constexpr int kDepth = 3;
-constexpr uint64_t kChunkBytes = 96ull << 20;  // target bytes of one chunk's 14 shards
 
 // One slot of the per-device pool of pipelines (SlotPool, hec_internal.hpp):
 // concurrent host batches on one device -- other threads, or two ranges of one
@@ -727,5 +727,16 @@ int hec_set_host_zero_copy(int on) {
     zero_copy_enabled() = on != 0;
     return HEC_OK;
 }
+
+#ifdef HEC_TEST_HOST_CHUNKS
+// Test builds only (host_chunks.hpp): the chunk sizes this library was
+// compiled with, so a test can prove that the variant it loaded is the one it
+// meant. The shipped library does not export this.
+void hec_test_host_chunk_limits(uint64_t* chunk_bytes, uint64_t* chunk_cols, uint64_t* read_piece) {
+    *chunk_bytes = hec::kChunkBytes;
+    *chunk_cols = hec::kChunkCols;
+    *read_piece = hec::kReadPiece;
+}
+#endif
 
 }  // extern "C"

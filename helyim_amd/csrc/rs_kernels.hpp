@@ -29,7 +29,7 @@ constexpr int kThreads = 256;               // 4 waves of 64 lanes
 // Makefile's smallgrid variant), so that batches of a few hundred stripes go
 // in several launches, grid-stride iterations and mask rounds. The shipped
 // library defines neither. Only rs_kernels.hip reads the two limits, the one
-// file a variant recompiles.
+// file that variant recompiles.
 #ifdef HEC_MAX_LAUNCH_BLOCKS
 constexpr uint64_t kMaxLaunchBlocks = HEC_MAX_LAUNCH_BLOCKS;
 #else

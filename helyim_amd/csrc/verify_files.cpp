@@ -26,13 +26,12 @@
 #include <cstring>
 
 #include "file_util.hpp"
+#include "host_chunks.hpp"  // kChunkCols per shard of one chunk, kReadPiece per pread task
 
 namespace hec {
 namespace {
 
 constexpr int K = 10, M = 4, N = 14;
-constexpr uint64_t kChunkCols = 4ull << 20;  // target bytes per shard of one chunk (14 x that per slot)
-constexpr uint64_t kReadPiece = 1ull << 20;  // bytes of one pread task
 
 // One slot of the per-device pool of scrubs (SlotPool): its stream, the two
 // pinned chunk slots and the result words of each.

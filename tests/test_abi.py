@@ -45,6 +45,10 @@ def test_speed_settings_are_the_three_host_path_knobs():
                  "hec_set_bitslice_vector_bytes", "hec_set_ragged_encode_remap", "hec_set_host_encode_narrow",
                  "hec_set_xcd_parts", "hec_set_chunk_rotation", "hec_set_file_zero_copy", "hec_file_path_stats"):
         assert not hasattr(helyim_amd.lib, gone), gone
+    # the queries of the Makefile's test variants: the product library exports neither
+    product = ctypes.CDLL(os.path.join(ROOT, "helyim_amd", "libhec.so"))
+    for test_only in ("hec_test_launch_limits", "hec_test_host_chunk_limits"):
+        assert not hasattr(product, test_only), test_only
 
 
 def test_library_is_gfx950_code_object():

@@ -288,19 +288,25 @@ def check_host_encode(rs, k, m, rng, hp, host_arenas, name, data, par, devices=N
     F.assert_footprint(plan, live, (hp.path, name, data, par))
 
 
-def check_host_reconstruct(rs, k, m, rng, hp, host_arenas, name, lay, devices=None):
+def check_host_reconstruct(rs, k, m, rng, hp, host_arenas, name, lay, devices=None, masks=None):
     stripes = F.stripes_of(lay)
     live, before = host_arenas.take(hp.path, stripes, rng)
-    masks = masks_for(rng, lay.S, k, m)
+    n_bad = (1 if lay.S >= 3 else 0) if masks is None else sum(bin(mk & ((1 << (k + m)) - 1)).count("1") < k
+                                                                for mk in masks)
+    masks = masks_for(rng, lay.S, k, m) if masks is None else masks
     plan = F.plan_reconstruct(before, stripes, k, m, present_of(masks, k + m))
     hp.check_view(live, lay)
     rc, bad = host_reconstruct(rs, live, lay, masks, devices)
     assert rc == 0, name
     F.assert_footprint(plan, live, (hp.path, name, lay, [hex(x) for x in masks]))
-    assert bad == plan.n_bad == (1 if lay.S >= 3 else 0), name
+    assert bad == plan.n_bad == n_bad, name
 
 
-@pytest.mark.parametrize("L", [17, 2048, 4096 + 3, 8192])
+HOST_LENGTHS = [17, 2048, 4096 + 3, 8192]
+MIXED = (1000, [0, 1, 4, 5, 0, 5, 4, 1, 1, 0, 5])  # shard length, shards lost per stripe
+
+
+@pytest.mark.parametrize("L", HOST_LENGTHS)
 @pytest.mark.parametrize("path", HOST_PATHS)
 def test_host_batch_footprint(gpu, host_arenas, path, L):
     """hec_host_encode_batch with distinct data and parity pointers and
@@ -323,6 +329,28 @@ def test_host_batch_footprint(gpu, host_arenas, path, L):
                 check_host_encode(rs, 10, 4, rng, hp, host_arenas, *case)
             for case in layouts:
                 check_host_reconstruct(rs, 10, 4, rng, hp, host_arenas, *case)
+
+
+@pytest.mark.parametrize("path", HOST_PATHS)
+def test_host_reconstruct_footprint_mixed_erasure_counts(gpu, host_arenas, path):
+    """hec_host_reconstruct_batch with 0, 1, 4 and 5 shards lost in stripes
+    next to each other (masks_for's counts vary from stripe to stripe too, but
+    by seed, and its shapes are one stripe or all stripes per chunk in either
+    build). Eleven stripes of 1000 bytes: chunks of 3, 3, 3 and 2 stripes in
+    the small-chunk build, with 4 | 5, 5 | 4 and 1 | 0 lost at the chunk edges;
+    a mask or a rebuilt shard taken from the neighbouring stripe or from the
+    slot's first changes a byte the image keeps, or the count."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(10, 4)
+    L, lost = MIXED
+    S = len(lost)
+    rng = np.random.default_rng(5500 + HOST_PATHS.index(path))
+    with host_path(path) as hp:
+        for name, lay in [*family_a(14, L, S, pads=(16,), gaps=(48,)), *family_b(14, L, S, pads=((16, 48),)),
+                          *family_d(14, L, S)]:
+            masks = [0x3FFF & ~sum(1 << int(i) for i in rng.choice(14, e, replace=False)) for e in lost]
+            masks[4] |= 0x7FFFC000  # stray bits above the shard count
+            check_host_reconstruct(rs, 10, 4, rng, hp, host_arenas, name, lay, masks=masks)
 
 
 @pytest.mark.parametrize("L", [2048, 4096 + 3])

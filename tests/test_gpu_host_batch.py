@@ -161,6 +161,45 @@ def test_host_batches_generic_geometry(gpu, k, m, pin):
     assert np.array_equal(a, want)
 
 
+GENERIC_CHUNKED = (6, 3, 41, 1000)  # k, m, stripes, shard length
+
+
+@pytest.mark.parametrize("pin", [True, False])
+def test_host_batch_generic_codec_per_stripe_masks(gpu, pin):
+    """RS(6,3) on 41 stripes of 1000 bytes with a mask of its own per stripe:
+    0 to 4 shards lost in turn (4 cannot be rebuilt: counted and left as it
+    was), the lost slots holding other stripes' bytes, against the C oracle.
+    Pageable, it is one chunk in the product and eight chunks of 5 stripes and
+    one of 1 in the small-chunk build (tests/test_gpu_small_chunk.py)."""
+    import torch
+    import helyim_amd as H
+    import helyim_amd.batch as B
+    k, m, S, L = GENERIC_CHUNKED
+    n = k + m
+    rng = np.random.default_rng(63)
+    rs, ors = H.ReedSolomon(k, m), corc.CReedSolomon(k, m)
+    t = torch.zeros((S, n, L), dtype=torch.uint8)
+    if pin:
+        t = t.pin_memory()
+    a = t.numpy()
+    a[:, :k] = rng.integers(0, 256, (S, k, L), dtype=np.uint8)
+    want = a.copy()
+    for s in range(S):
+        ors.encode([want[s, i] for i in range(n)])
+    B.host_encode_batch(rs, t)
+    assert np.array_equal(a, want)
+    masks = np.full(S, (1 << n) - 1, np.uint32)
+    for s in range(S):
+        for i in rng.choice(n, s % (m + 2), replace=False):
+            masks[s] &= ~np.uint32(1 << int(i))
+            a[s, int(i)] = want[(s + 1) % S, int(i)]  # a neighbour's shard: stale, plausible bytes
+    before = a.copy()
+    lost = [s for s in range(S) if s % (m + 2) == m + 1]
+    assert B.host_reconstruct_batch(rs, t, masks) == len(lost) == 8
+    for s in range(S):
+        assert np.array_equal(a[s], before[s] if s in lost else want[s]), (s, hex(int(masks[s])))
+
+
 # ---- one host batch over a device set (hec_host_*_batch_multi) -------------
 # The 1-GPU box repeats device 0: every range runs concurrently on its own
 # host thread, pipeline and streams, which is the code an 8-GPU node runs with
@@ -168,7 +207,10 @@ def test_host_batches_generic_geometry(gpu, k, m, pin):
 # multiple of the list length) and at one stripe per range.
 @pytest.mark.parametrize("devices,S,L,pin", [([0, 0], 7, 4096 + 3, True), ([0, 0, 0], 40, 1 << 20, True),
                                              ([0, 0], 9, 65536 + 5, False), ([0] * 5, 3, 1000, True),
-                                             ([0, 0, 0, 0], 5, 17, False)])
+                                             ([0, 0, 0, 0], 5, 17, False),
+                                             # ranges of 13, 14 and 14 stripes, each in chunks of 3 stripes under
+                                             # the small-chunk build: range edges and chunk edges at different stripes
+                                             ([0, 0, 0], 41, 1000, False), ([0, 0, 0], 41, 1000, True)])
 def test_host_batch_multi_device_encode_and_every_erasure_count(gpu, devices, S, L, pin):
     import helyim_amd as H
     import helyim_amd.batch as B
@@ -186,11 +228,11 @@ def test_host_batch_multi_device_encode_and_every_erasure_count(gpu, devices, S,
         for i in rng.choice(14, e, replace=False):
             masks[s] &= ~np.uint32(1 << int(i))
             a[s, int(i)] = 0xA5
+    before = a.copy()
     bad = B.host_reconstruct_batch(rs, t, masks, devices=devices)
-    assert bad == sum(1 for s in range(S) if s % 6 == 5)
-    for s in range(S):
-        if s % 6 <= 4:
-            assert np.array_equal(a[s], want[s]), s
+    assert bad == sum(1 for s in range(S) if s % 6 == 5)  # summed over the ranges
+    for s in range(S):  # rebuilt, or left byte for byte as it was
+        assert np.array_equal(a[s], want[s] if s % 6 <= 4 else before[s]), s
 
 
 def test_host_batch_multi_device_errors(gpu):

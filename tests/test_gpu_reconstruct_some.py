@@ -254,6 +254,9 @@ def host_some(rs, live, lay, masks, wants):
     return rc, bad.value
 
 
+HOST_S, HOST_LENGTHS = 64, (1000, 2048)
+
+
 @pytest.mark.parametrize("path", HOST_PATHS[1:2] + HOST_PATHS[:1] + HOST_PATHS[2:])
 def test_host_batch(gpu, host_arenas, path):
     """6. The three host paths at L = 1000 and 2048, 64 stripes. The
@@ -268,12 +271,12 @@ def test_host_batch(gpu, host_arenas, path):
             live, _ = host_arenas.take(path, F.stripes_of(lay), rng)
             pairs = random_pairs(rng, 64)
             assert host_some(rs, live, lay, [m for m, _ in pairs], [w for _, w in pairs])[0] == 0
-        for L in (1000, 2048):
-            for lay in (F.stripe_major(N, L, 64, F.r16(L) + 16, 48), F.shard_major(N, L, 64, F.r16(L) + 16, 48),
-                        F.stripe_major(N, L, 64, L + 3, 5)):
+        for L in HOST_LENGTHS:
+            for lay in (F.stripe_major(N, L, HOST_S, F.r16(L) + 16, 48),
+                        F.shard_major(N, L, HOST_S, F.r16(L) + 16, 48), F.stripe_major(N, L, HOST_S, L + 3, 5)):
                 stripes = F.stripes_of(lay)
                 live, before = host_arenas.take(path, stripes, rng)
-                pairs = random_pairs(rng, 64)
+                pairs = random_pairs(rng, HOST_S)
                 short = erase(rng, 5)  # 9 present: counted when it wants a lost shard, a no-op when not
                 pairs[:3] = [(pairs[0][0], noisy(rng, pairs[0][0], 0)), (short, 0xFFFFFFFF),
                              (short, noisy(rng, short, 0))]
@@ -284,6 +287,55 @@ def test_host_batch(gpu, host_arenas, path):
                 assert rc == 0
                 F.assert_footprint(plan, live, (path, lay))
                 M.assert_counted(plan, bad, (path, lay))
+
+
+EDGE_S, EDGE_L = 64, 1000  # 22 chunks in the small-chunk build: 21 of 3 stripes and one of 1
+
+
+def edge_pairs(rng, S):
+    """A (mask, want) pair of its own per stripe, five kinds in turn: all lost
+    shards wanted, one of several wanted, 9 present and none wanted (a no-op,
+    not counted), 9 present and one lost shard wanted (counted), all present.
+    Five kinds against chunks of three stripes: every kind falls on either side
+    of a chunk edge and at every position of a chunk, with its neighbours of
+    other kinds. -> (pairs, stripes counted)"""
+    pairs = []
+    for s in range(S):
+        kind = s % 5
+        m = erase(rng, (1 + s % 4, 2 + s % 3, 5, 5, 0)[kind])
+        gone = [i for i in range(N) if not (m >> i) & 1]
+        w = (0xFFFFFFFF, 1 << gone[s % len(gone)] if gone else 0, 0, 1 << gone[s % len(gone)] if gone else 0,
+             0xFFFFFFFF)[kind]
+        pairs.append((m, noisy(rng, m, w)))
+    return pairs, sum(1 for s in range(S) if s % 5 == 3)
+
+
+@pytest.mark.parametrize("path", HOST_PATHS)
+def test_host_batch_across_chunk_edges(gpu, host_arenas, path):
+    """6b. 64 stripes of 1000 bytes whose masks and wants differ from stripe to
+    stripe (edge_pairs), on the three host paths, stripe-major and shard-major:
+    footprint and counter against some_model. The product takes the batch in
+    one chunk; in the small-chunk build (tests/test_gpu_small_chunk.py) every
+    stripe lies at a chunk edge, so the want words must advance with the masks
+    (wants + s0), each slot's launch must take its own words, and a stripe
+    that wants nothing must stay uncounted past chunk 0."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(K, MP)
+    rng = np.random.default_rng(650 + HOST_PATHS.index(path))
+    S, L = EDGE_S, EDGE_L
+    with host_path(path) as hp:
+        for lay in (F.stripe_major(N, L, S, F.r16(L) + 16, 48), F.shard_major(N, L, S, F.r16(L) + 16, 48)):
+            stripes = F.stripes_of(lay)
+            live, before = host_arenas.take(path, stripes, rng)
+            pairs, counted = edge_pairs(rng, S)
+            masks, wants = [m for m, _ in pairs], [w for _, w in pairs]
+            plan = M.plan_reconstruct_some(before, stripes, K, MP, present_of(masks, N), wants)
+            assert plan.n_bad == counted and plan.n_noop_short == sum(1 for s in range(S) if s % 5 == 2)
+            hp.check_view(live, lay)
+            rc, bad = host_some(rs, live, lay, masks, wants)
+            assert rc == 0
+            F.assert_footprint(plan, live, (path, lay))
+            M.assert_counted(plan, bad, (path, lay))
 
 
 def per_call_stripe(rng, k, m, L, base):

@@ -12,21 +12,19 @@ One child process per file (`python -m pytest <file> -m gpu` with HEC_LIB_PATH
 set); tests/small_grid_probe.py runs first in the child and ends it unless the
 limits are live. Every child has a time limit of its own. A child that dies of
 a signal or runs out of time fails every remaining file without starting
-another process on the device: all children start from run_child below, so
-the rule holds by construction."""
+another process on the device: all children start from run_child of
+tests/variant_children.py, so the rule holds by construction."""
 import os
-import re
 import subprocess
 import sys
-import time
 
 import pytest
 
 import small_grid_probe as probe
+import variant_children as C
+from variant_children import ROOT, TESTS, tail
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
-VARIANT = os.path.join(ROOT, "build", "variants", "libhec_smallgrid.so")
+VARIANT = C.variant_path("smallgrid")
 CHILD_TIMEOUT = 300  # seconds; a child takes about what its file takes with the product library
 
 FILES = ["test_gpu_check.py", "test_gpu_locate.py", "test_gpu_verify.py", "test_gpu_generic_codecs.py",
@@ -107,23 +105,9 @@ DESELECT = {
     "test_gpu_reconstruct_some.py": [],
 }
 
-_stopped = []  # why no further child may start (a child died of a signal or ran out of time)
-
 
 def child_env():
-    env = dict(os.environ)
-    env["HEC_LIB_PATH"] = VARIANT
-    env["PYTHONPATH"] = os.pathsep.join([TESTS] + [p for p in env.get("PYTHONPATH", "").split(os.pathsep) if p])
-    return env
-
-
-def tail(text, n=60):
-    return "\n".join(text.splitlines()[-n:])
-
-
-def count(word, text):
-    m = re.search(r"(\d+) " + word, text.splitlines()[-1] if text.strip() else "")
-    return int(m.group(1)) if m else 0
+    return C.child_env(VARIANT)
 
 
 def test_variant_is_built_and_its_limits_are_live():
@@ -164,33 +148,8 @@ def test_ragged_correct_batches_pass_one_launch_of_the_variant():
 
 
 def run_child(name, deselect, timeout):
-    """tests/<name> in a child process against the variant; every child of this
-    module starts here, and none starts after one died of a signal or ran out
-    of time."""
-    assert not _stopped, "not started: " + _stopped[0]
-    assert os.path.exists(VARIANT), VARIANT + " is missing: `make all` builds it"
-    cmd = [sys.executable, "-m", "pytest", "-p", "small_grid_probe", os.path.join("tests", name), "-m", "gpu", "-q",
-           "--maxfail=5", "-p", "no:cacheprovider"]
-    for node, _reason in deselect:
-        cmd += ["--deselect", f"tests/{name}::{node}"]
-    t0 = time.monotonic()
-    try:
-        r = subprocess.run(cmd, env=child_env(), cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    except subprocess.TimeoutExpired as e:
-        _stopped.append(f"the child of {name} was killed after {timeout} s")
-        out = e.stdout if isinstance(e.stdout, str) else (e.stdout or b"").decode(errors="replace")
-        pytest.fail(_stopped[0] + "\n" + tail(out))
-    wall = time.monotonic() - t0
-    out = r.stdout + r.stderr
-    if r.returncode < 0:
-        _stopped.append(f"the child of {name} died of signal {-r.returncode}")
-        pytest.fail(_stopped[0] + "\n" + tail(out))
-    passed, deselected = count("passed", r.stdout), count("deselected", r.stdout)
-    print(f"small grid {name}: {passed + deselected + count('failed', r.stdout)} collected, {deselected} deselected, "
-          f"{passed} passed, {wall:.1f} s")
-    assert r.returncode == 0, f"{name} under the small-grid variant (return code {r.returncode}):\n{tail(out)}"
-    assert passed > 0, tail(out)
-    assert deselected == len(deselect), f"a deselected node id of {name} matches no test:\n{tail(out)}"
+    """tests/<name> in a child process against the variant (variant_children.run_child)."""
+    C.run_child("small grid", VARIANT, "small_grid_probe", name, deselect, timeout)
 
 
 @pytest.mark.gpu

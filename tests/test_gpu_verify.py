@@ -489,7 +489,10 @@ def test_host_verify_across_chunks(gpu, k, m, L, pitch, C, S):
     import helyim_amd as H
     from helyim_amd import batch
     n = k + m
-    assert C == max(1, CHUNK_BYTES // (n * -(-L // 256) * 256)) and 3 * C < S < 4 * C  # else kChunkBytes changed
+    # else kChunkBytes changed; a small-chunk build (tests/test_gpu_small_chunk.py) takes the same batch, dirty
+    # stripes and reference words in thousands of chunks, whose edges then fall elsewhere
+    if not hasattr(H.lib, "hec_test_host_chunk_limits"):
+        assert C == max(1, CHUNK_BYTES // (n * -(-L // 256) * 256)) and 3 * C < S < 4 * C
     rs = H.ReedSolomon(k, m)
     image = chunked_image(k, m, L, pitch, S)
     dirty, want, _ = chunk_damage(image, k, m, L, C)
