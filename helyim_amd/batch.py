@@ -453,22 +453,42 @@ def _device_list(devices):
     return (ctypes.c_int * len(ds))(*ds), len(ds)
 
 
+def _host_layout(rs: ReedSolomon, stripes: torch.Tensor):
+    """Check host stripes[S, total, L] -> (S, L, shards, parity): the (address,
+    stripe stride, shard stride) of the whole arena, and of its parity shards."""
+    _check_host(stripes, rs)
+    S, _n, L = stripes.shape
+    st, sh = stripes.stride(0), stripes.stride(1)
+    base = stripes.data_ptr()
+    return S, L, (base, st, sh), (base + rs.data_shard_count() * sh, st, sh)
+
+
+def _host_masks(S: int, masks, name: str):
+    """masks -> a contiguous uint32 numpy array of one word per stripe."""
+    import numpy as np
+    m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint32))
+    if m.size != S:
+        raise ValueError(f"{m.size} {name} masks for {S} stripes")
+    return m
+
+
+def _host_call(name: str, rs: ReedSolomon, devices, *args) -> None:
+    """lib.<name> on the current device, or with a device list lib.<name>_multi."""
+    if devices is None:
+        check(getattr(lib, name)(rs.handle, *args))
+        return
+    arr, nd = _device_list(devices)
+    check(getattr(lib, name + "_multi")(rs.handle, arr, nd, *args))
+
+
 def host_encode_batch(rs: ReedSolomon, stripes: torch.Tensor, devices=None) -> None:
     """Host-memory stripes[S, total, L] (pin_memory() for full PCIe rate):
     parity computed on the GPU, pipelined H2D -> kernel -> D2H. devices (a
     list of GPU ids, repeats allowed): contiguous stripe ranges, one per entry,
     coded concurrently (hec_host_encode_batch_multi); None = the current
     device."""
-    _check_host(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
-    if devices is None:
-        check(lib.hec_host_encode_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S))
-        return
-    arr, nd = _device_list(devices)
-    check(lib.hec_host_encode_batch_multi(rs.handle, arr, nd, base, st, sh, base + k * sh, st, sh, L, S))
+    S, L, shards, parity = _host_layout(rs, stripes)
+    _host_call("hec_host_encode_batch", rs, devices, *shards, *parity, L, S)
 
 
 def host_reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks, devices=None) -> int:
@@ -476,20 +496,10 @@ def host_reconstruct_batch(rs: ReedSolomon, stripes: torch.Tensor, present_masks
     (fewer than data_shards present). devices: as host_encode_batch
     (hec_host_reconstruct_batch_multi)."""
     import ctypes
-    import numpy as np
-    _check_host(stripes, rs)
-    S, n, L = stripes.shape
-    m = np.ascontiguousarray(np.asarray(present_masks, dtype=np.uint32))
-    if m.size != S:
-        raise ValueError(f"{m.size} present masks for {S} stripes")
+    S, L, shards, _parity = _host_layout(rs, stripes)
+    m = _host_masks(S, present_masks, "present")
     bad = ctypes.c_uint32(0)
-    if devices is None:
-        check(lib.hec_host_reconstruct_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1),
-                                             L, S, m.ctypes.data, ctypes.byref(bad)))
-    else:
-        arr, nd = _device_list(devices)
-        check(lib.hec_host_reconstruct_batch_multi(rs.handle, arr, nd, stripes.data_ptr(), stripes.stride(0),
-                                                   stripes.stride(1), L, S, m.ctypes.data, ctypes.byref(bad)))
+    _host_call("hec_host_reconstruct_batch", rs, devices, *shards, L, S, m.ctypes.data, ctypes.byref(bad))
     return int(bad.value)
 
 
@@ -499,16 +509,12 @@ def host_reconstruct_some_batch(rs: ReedSolomon, stripes: torch.Tensor, present_
     PCIe. Returns the number of skipped stripes (fewer than 10 shards present
     and an erased shard wanted)."""
     import ctypes
-    import numpy as np
-    _check_host(stripes, rs)
-    S, n, L = stripes.shape
-    m = np.ascontiguousarray(np.asarray(present_masks, dtype=np.uint32))
-    w = np.ascontiguousarray(np.asarray(want_masks, dtype=np.uint32))
-    if m.size != S or w.size != S:
-        raise ValueError(f"{m.size} present masks and {w.size} want masks for {S} stripes")
+    S, L, shards, _parity = _host_layout(rs, stripes)
+    m = _host_masks(S, present_masks, "present")
+    w = _host_masks(S, want_masks, "want")
     bad = ctypes.c_uint32(0)
-    check(lib.hec_host_reconstruct_some_batch(rs.handle, stripes.data_ptr(), stripes.stride(0), stripes.stride(1),
-                                              L, S, m.ctypes.data, w.ctypes.data, ctypes.byref(bad)))
+    _host_call("hec_host_reconstruct_some_batch", rs, None, *shards, L, S, m.ctypes.data, w.ctypes.data,
+               ctypes.byref(bad))
     return int(bad.value)
 
 
@@ -517,13 +523,9 @@ def host_verify_batch(rs: ReedSolomon, stripes: torch.Tensor):
     returns the uint32 ``[S]`` numpy array of mismatch words (verify_batch's
     contract). Only the words come back over PCIe; the stripes are not written."""
     import numpy as np
-    _check_host(stripes, rs)
-    k = rs.data_shard_count()
-    S, n, L = stripes.shape
-    st, sh = stripes.stride(0), stripes.stride(1)
-    base = stripes.data_ptr()
+    S, L, shards, parity = _host_layout(rs, stripes)
     words = np.zeros(max(S, 1), dtype=np.uint32)
-    check(lib.hec_host_verify_batch(rs.handle, base, st, sh, base + k * sh, st, sh, L, S, words.ctypes.data, None))
+    _host_call("hec_host_verify_batch", rs, None, *shards, *parity, L, S, words.ctypes.data, None)
     return words[:S]
 
 

@@ -127,9 +127,10 @@ uint64_t batch_span(uint64_t stripe_stride, uint64_t shard_stride, uint32_t shar
     return uint64_t(stripes - 1) * stripe_stride + uint64_t(shards - 1) * shard_stride + len;
 }
 
-// Test hook: HEC_TEST_HOST_FAIL_AFTER_CHUNK=i fails a copy-pipeline encode
-// right after queueing chunk i's kernel, so a test can check that the work
-// queued before an error return has landed when the call returns
+// Test hook: HEC_TEST_HOST_FAIL_AFTER_CHUNK=i fails a host batch on the copy
+// pipeline (any operation: the hook sits in run_host_op's one loop) right
+// after queueing chunk i's kernel, so a test can check that the work queued
+// before an error return has landed when the call returns
 // (tests/test_gpu_host_batch.py). Read per call; -1 = off.
 int forced_failure_chunk() {
     const char* v = std::getenv("HEC_TEST_HOST_FAIL_AFTER_CHUNK");
@@ -156,63 +157,20 @@ uint32_t load_masks(uint32_t* dst, const uint32_t* src, uint32_t c, uint32_t ful
     return bad;
 }
 
-// fn(first, count) for each run of adjacent set bits of `bits` below n, over
-// the first `cap` set bits only (the run the cap falls in is cut there).
-template <typename F>
-int for_bit_runs(uint32_t bits, int n, int cap, F fn) {
-    int used = 0;
-    for (int i = 0; i < n && used < cap;) {
-        if (!((bits >> i) & 1)) {
+// fn(first, count) for each run of adjacent i in [lo, hi) with on(i); no run
+// crosses `cut`.
+template <typename On, typename F>
+int for_runs(int lo, int hi, int cut, On on, F fn) {
+    for (int i = lo; i < hi;) {
+        if (!on(i)) {
             ++i;
             continue;
         }
-        int j = i;
-        while (j < n && ((bits >> j) & 1) && used + (j - i) < cap) ++j;
+        int j = i + 1;
+        while (j < hi && j != cut && on(j)) ++j;
         HEC_TRY(fn(i, j - i));
-        used += j - i;
         i = j;
     }
-    return HEC_OK;
-}
-
-// Pageable batches with zero copy on: chunks of C stripes go through the two
-// pinned slots, coded in place there on streams[0]. pack(s0, c, q) fills slot q
-// on the host, launch(c, q) queues its kernel, unpack(s0, c, q) hands the
-// results back; packing chunk i+1 and unpacking chunk i-1 overlap the kernel
-// of chunk i.
-template <typename Pack, typename Launch, typename Unpack>
-int two_slot_loop(Pipeline* p, uint32_t n_stripes, uint32_t C, Pack pack, Launch launch, Unpack unpack) {
-    uint32_t prev_s0 = 0, prev_c = 0;
-    int q = 0;
-    for (uint32_t s0 = 0; s0 < n_stripes; s0 += C, q ^= 1) {
-        const uint32_t c = std::min(C, n_stripes - s0);
-        pack(s0, c, q);
-        HEC_TRY(launch(c, q));
-        HEC_HIP(hipEventRecord(p->hdone[q], p->streams[0]));
-        if (s0 > 0) {  // the previous chunk (other slot) is done or nearly: hand it back
-            HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
-            unpack(prev_s0, prev_c, q ^ 1);
-        }
-        prev_s0 = s0, prev_c = c;
-    }
-    HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
-    unpack(prev_s0, prev_c, q ^ 1);
-    return HEC_OK;
-}
-
-// The copy pipeline: chunk `it` of C stripes runs on stream and device slot
-// q = it % kDepth. in(s0, c, q) queues its H2D copies, launch(c, q, it) its
-// kernel, out(s0, c, q) its D2H copies; all streams are drained at the end.
-template <typename In, typename Launch, typename Out>
-int copy_loop(Pipeline* p, uint32_t n_stripes, uint32_t C, In in, Launch launch, Out out) {
-    for (uint32_t s0 = 0, it = 0; s0 < n_stripes; s0 += C, ++it) {
-        const uint32_t c = std::min(C, n_stripes - s0);
-        const int q = int(it % kDepth);
-        HEC_TRY(in(s0, c, q));
-        HEC_TRY(launch(c, q, it));
-        HEC_TRY(out(s0, c, q));
-    }
-    for (auto st : p->streams) HEC_HIP(hipStreamSynchronize(st));
     return HEC_OK;
 }
 
@@ -282,13 +240,295 @@ int run_device_ranges(const int* devices, size_t n_devices, uint32_t n_stripes,
     return HEC_OK;
 }
 
-// hec_host_reconstruct_batch (h_want_masks == nullptr: every erased shard,
-// today's launches) and hec_host_reconstruct_some_batch: one body. With want
-// words a stripe takes part only where it wants an erased shard, and only the
-// wanted shards are computed, stored and brought back.
-int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
-                     uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
-                     const uint32_t* h_want_masks, uint32_t* n_bad_stripes);
+// The shards of a stripe that move one way: those i of [lo, hi) the operation
+// names for that stripe (HostOp::goes_in / comes_back). About `typical` of
+// them do: the byte hint the host pool splits a pack or an unpack by.
+struct ShardRange {
+    int lo = 0, hi = 0, typical = 0;
+};
+
+// What a host batch operation states; run_host_op carries it down whichever
+// staging path the caller's memory takes.
+struct HostOp {
+    const hec_rs_t* rs = nullptr;
+    GeomDevice* gd = nullptr;  // rs on the current device (run_host_op sets it)
+    // The caller's memory, as the Batch a launch over it would get. Shards
+    // [0, split) of a stripe lie in host.in and [split, n) in host.out, each
+    // arena with its own strides; split == 0: one in-place arena holds all n.
+    Batch host;
+    int split = 0;
+    ShardRange in, out;  // staged in before the launch, brought back after it
+    // Per-stripe words. masks: present masks in, with wants the want masks too;
+    // goes_in, comes_back and the launch see both as load_masks normalised
+    // them. words: one result word per stripe out.
+    const uint32_t* masks = nullptr;
+    const uint32_t* wants = nullptr;
+    uint32_t* words = nullptr;
+    // A launch over a staging slot gets the length rounded up to 16 (the pad
+    // bytes of the pitch are computed but never copied back), or with true_len
+    // the length itself.
+    bool true_len = false;
+    uint32_t* n_bad_stripes = nullptr;
+
+    const Strided& arena_of(int i) const { return i < split ? host.in : host.out; }
+    uint8_t* shard(uint32_t s, int i) const {  // host address of shard i of stripe s
+        const Strided& a = arena_of(i);
+        return a.base + s * a.stripe + uint64_t(i < split ? i : i - split) * a.shard;
+    }
+    // Whether shard i of a stripe with these words is staged in / brought back.
+    virtual bool goes_in(uint32_t /*mask*/, uint32_t /*want*/, int /*i*/) const { return true; }
+    virtual bool comes_back(uint32_t /*mask*/, uint32_t /*want*/, int /*i*/) const { return true; }
+    // Once per call, before the first launch (plans the launch needs).
+    virtual int prepare(hipStream_t) { return HEC_OK; }
+    // Queue the kernels over b on s. words: b's per-stripe words in device
+    // memory (the masks in, or the result words out); wants likewise, or null.
+    virtual int launch(const Batch& b, uint32_t* words, const uint32_t* wants, hipStream_t s, bool over_pcie) = 0;
+    // The last chunk is home. bad: what load_masks counted over the call.
+    virtual void done(uint32_t /*bad*/) {}
+    virtual ~HostOp() = default;
+};
+
+// One host batch, down one of three staging paths:
+//  1. direct view: the caller's arenas are pinned, GPU-addressable ranges
+//     (host_device_view): one launch runs over them in place;
+//  2. pageable memory with zero copy on: chunks of C stripes are packed on the
+//     host pool into the two pinned slots, coded in place there over PCIe on
+//     streams[0] and unpacked; packing chunk i+1 and unpacking chunk i-1
+//     overlap the kernel of chunk i;
+//  3. the copy pipeline: chunk `it` runs H2D, kernel and D2H on stream and
+//     device slot it % kDepth; all streams are drained at the end.
+// A slot holds C stripes of n shards at pitch Lp: shard i of its stripe s is at
+// slot + s * n * Lp + i * Lp.
+int run_host_op(HostOp& op) {
+    const hec_rs_t* rs = op.rs;
+    HEC_TRY(geom_device(rs, &op.gd));
+    Lease<Pipeline> p;
+    HEC_TRY(lease_slot(p));
+    const int k = rs->k, n = rs->n;
+    const uint64_t len = op.host.len;
+    const uint32_t S = op.host.n_stripes;
+    const uint32_t full = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1);
+    uint32_t bad = 0;
+
+    // slots of slot_bytes and `count` words a slot
+    auto reserve = [&](size_t slot_bytes, uint32_t count) -> int {
+        HEC_TRY(p->reserve(slot_bytes, op.masks || op.words ? count : 1));
+        return op.wants ? p->reserve_wants(count) : HEC_OK;
+    };
+    // the masks of stripes [s0, s0 + c) into slot q's host words, and on to the device on streams[q]
+    auto load_words = [&](int q, uint32_t s0, uint32_t c) {
+        if (op.masks)
+            bad += load_masks(p->mask_host[q], op.masks + s0, c, full, k, p->want_host[q],
+                              op.wants ? op.wants + s0 : nullptr);
+    };
+    auto send_words = [&](int q, uint32_t c) -> int {
+        if (!op.masks) return HEC_OK;
+        HEC_HIP(hipMemcpyAsync(p->mask_dev[q], p->mask_host[q], size_t(c) * 4, hipMemcpyHostToDevice, p->streams[q]));
+        if (op.wants)
+            HEC_HIP(hipMemcpyAsync(p->want_dev[q], p->want_host[q], size_t(c) * 4, hipMemcpyHostToDevice,
+                                   p->streams[q]));
+        return HEC_OK;
+    };
+    // whether shard i of stripe s of slot q's chunk moves in (or back)
+    auto moves = [&](bool in, int q, uint32_t s, int i) {
+        uint32_t mask = full, want = 0;
+        if (op.masks) {
+            mask = p->mask_host[q][s];
+            want = op.wants ? p->want_host[q][s] : ~mask & full;
+        }
+        return in ? op.goes_in(mask, want, i) : op.comes_back(mask, want, i);
+    };
+
+    // 1. direct view
+    auto view = [&](const Strided& a, int shards, uint8_t** dev) {
+        return host_device_view(a.base, batch_span(a.stripe, a.shard, uint32_t(shards), len, S), dev);
+    };
+    uint8_t *zin, *zout;
+    if (view(op.host.in, op.split ? op.split : n, &zin) &&
+        (op.split ? view(op.host.out, n - op.split, &zout) : (zout = zin, true))) {
+        HEC_TRY(reserve(0, S));
+        HEC_TRY(op.prepare(p->streams[0]));
+        load_words(0, 0, S);  // to the device: the caller's array may be pageable
+        HEC_TRY(send_words(0, S));
+        HEC_TRY(op.launch(Batch{arena(zin, op.host.in.stripe, op.host.in.shard),
+                                arena(zout, op.host.out.stripe, op.host.out.shard), len, S},
+                          p->mask_dev[0], op.wants ? p->want_dev[0].p : nullptr, p->streams[0], /*over_pcie=*/true));
+        if (op.words)
+            HEC_HIP(hipMemcpyAsync(p->mask_host[0], p->mask_dev[0], size_t(S) * 4, hipMemcpyDeviceToHost,
+                                   p->streams[0]));
+        HEC_HIP(hipStreamSynchronize(p->streams[0]));
+        if (op.words) std::memcpy(op.words, p->mask_host[0], size_t(S) * 4);
+        op.done(bad);
+        return HEC_OK;
+    }
+
+    const uint64_t Lp = round_up(len, 256);  // staging shard pitch
+    const uint64_t dstripe = uint64_t(n) * Lp;
+    const uint32_t C = chunk_stripes(Lp, n, S);
+    auto at = [&](uint8_t* slot, uint32_t s, int i) { return slot + s * dstripe + uint64_t(i) * Lp; };
+    auto slot_batch = [&](uint8_t* slot, uint32_t c) {
+        const Strided a = arena(slot, dstripe, Lp);
+        return Batch{a, a.from(uint64_t(op.split)), op.true_len ? len : round_up(len, 16), c};
+    };
+
+    // 2. pageable memory through the two pinned slots
+    if (zero_copy_enabled()) {
+        HEC_TRY(reserve(0, C));
+        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
+        HEC_TRY(op.prepare(p->streams[0]));
+        uint8_t* zs[2];
+        uint32_t *zm[2] = {}, *zw[2] = {};
+        for (int q = 0; q < 2; ++q) zs[q] = pinned_device_ptr(p->hslot[q]);
+        if (op.masks)
+            for (int q = 0; q < 2; ++q) zm[q] = reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[q]));
+        if (op.wants)
+            for (int q = 0; q < 2; ++q) zw[q] = reinterpret_cast<uint32_t*>(pinned_device_ptr(p->want_host[q]));
+        // a slot the device cannot address: the copy pipeline instead
+        if (zs[0] && zs[1] && (!op.masks || (zm[0] && zm[1])) && (!op.wants || (zw[0] && zw[1]))) {
+            auto host_copy = [&](bool in, uint32_t s0, uint32_t c, int q) {
+                const ShardRange& r = in ? op.in : op.out;
+                const size_t w = size_t(r.hi - r.lo);
+                if (!w) return;
+                parallel_for(size_t(c) * w, uint64_t(c) * r.typical * len, [&](size_t t) {
+                    const uint32_t s = uint32_t(t / w);
+                    const int i = r.lo + int(t % w);
+                    if (!moves(in, q, s, i)) return;
+                    uint8_t *h = op.shard(s0 + s, i), *z = at(p->hslot[q], s, i);
+                    std::memcpy(in ? z : h, in ? h : z, len);
+                });
+            };
+            auto unpack = [&](uint32_t s0, uint32_t c, int q) {
+                host_copy(false, s0, c, q);
+                if (op.words) std::memcpy(op.words + s0, p->mask_host[q], size_t(c) * 4);
+            };
+            uint32_t prev_s0 = 0, prev_c = 0;
+            int q = 0;
+            for (uint32_t s0 = 0; s0 < S; s0 += C, q ^= 1) {
+                const uint32_t c = std::min(C, S - s0);
+                load_words(q, s0, c);  // the kernel reads them where they are
+                host_copy(true, s0, c, q);
+                HEC_TRY(op.launch(slot_batch(zs[q], c), op.masks ? zm[q] : p->mask_dev[q].p, zw[q], p->streams[0],
+                                  /*over_pcie=*/true));
+                if (op.words)
+                    HEC_HIP(hipMemcpyAsync(p->mask_host[q], p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
+                                           p->streams[0]));
+                HEC_HIP(hipEventRecord(p->hdone[q], p->streams[0]));
+                if (s0 > 0) {  // the previous chunk (other slot) is done or nearly: hand it back
+                    HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
+                    unpack(prev_s0, prev_c, q ^ 1);
+                }
+                prev_s0 = s0, prev_c = c;
+            }
+            HEC_HIP(hipEventSynchronize(p->hdone[q ^ 1]));
+            unpack(prev_s0, prev_c, q ^ 1);
+            op.done(bad);
+            return HEC_OK;
+        }
+    }
+
+    // 3. the copy pipeline
+    HEC_TRY(reserve(size_t(C) * dstripe, C));
+    HEC_TRY(op.prepare(p->streams[0]));
+    // one copy2d per run of adjacent moving shards of a stripe that lie in one host arena
+    auto dma = [&](bool in, uint32_t s0, uint32_t c, int q) -> int {
+        const ShardRange& r = in ? op.in : op.out;
+        for (uint32_t s = 0; s < c; ++s)
+            HEC_TRY(for_runs(
+                r.lo, r.hi, op.split, [&](int i) { return moves(in, q, s, i); },
+                [&](int i, int count) -> int {
+                    uint8_t *h = op.shard(s0 + s, i), *d = at(p->slot[q], s, i);
+                    const uint64_t hpitch = op.arena_of(i).shard;
+                    HEC_HIP(in ? copy2d(d, Lp, h, hpitch, len, uint64_t(count), hipMemcpyHostToDevice, p->streams[q])
+                               : copy2d(h, hpitch, d, Lp, len, uint64_t(count), hipMemcpyDeviceToHost, p->streams[q]));
+                    return HEC_OK;
+                }));
+        return HEC_OK;
+    };
+    const int fail_at = forced_failure_chunk();
+    for (uint32_t s0 = 0, it = 0; s0 < S; s0 += C, ++it) {
+        const uint32_t c = std::min(C, S - s0);
+        const int q = int(it % kDepth);
+        if (op.masks) {
+            // the staging of this slot was last read by the copy issued kDepth chunks ago
+            HEC_HIP(hipStreamSynchronize(p->streams[q]));
+            load_words(q, s0, c);
+        }
+        HEC_TRY(dma(true, s0, c, q));
+        HEC_TRY(send_words(q, c));
+        HEC_TRY(op.launch(slot_batch(p->slot[q], c), p->mask_dev[q], op.wants ? p->want_dev[q].p : nullptr,
+                          p->streams[q], /*over_pcie=*/false));
+        if (int(it) == fail_at) return fail(HEC_ERR_HIP, "test hook: failure after chunk " + std::to_string(it));
+        HEC_TRY(dma(false, s0, c, q));
+        if (op.words)  // D2H of the words only
+            HEC_HIP(hipMemcpyAsync(op.words + s0, p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
+                                   p->streams[q]));
+    }
+    for (auto st : p->streams) HEC_HIP(hipStreamSynchronize(st));
+    op.done(bad);
+    return HEC_OK;
+}
+
+// Encode: the k data shards of every stripe in, the m parity shards back.
+struct HostEncode : HostOp {
+    HostEncode(const hec_rs_t* r, const Batch& b) {
+        rs = r, host = b, split = r->k;
+        in = {0, r->k, r->k};
+        out = {r->k, r->n, r->m};
+    }
+    int launch(const Batch& b, uint32_t*, const uint32_t*, hipStream_t s, bool over_pcie) override {
+        return run_apply(gd->encode, uint32_t(rs->k), b, nullptr, nullptr, s, nullptr, over_pcie);
+    }
+};
+
+// hec_host_reconstruct_batch (want_masks == nullptr: every erased shard,
+// run_apply's launches) and hec_host_reconstruct_some_batch. A stripe takes
+// part when it has k shards present and wants an erased one: its first k
+// present shards go in (the ones the decode reads), and only the wanted erased
+// shards are computed, stored and brought back.
+struct HostReconstruct : HostOp {
+    HostReconstruct(const hec_rs_t* r, const Batch& b, const uint32_t* present_masks, const uint32_t* want_masks,
+                    uint32_t* n_bad) {
+        rs = r, host = b, masks = present_masks, wants = want_masks, n_bad_stripes = n_bad;
+        in = {0, r->n, r->k};
+        out = {0, r->n, 4};
+    }
+    bool takes_part(uint32_t mask, uint32_t want) const { return __builtin_popcount(mask) >= rs->k && want; }
+    bool goes_in(uint32_t mask, uint32_t want, int i) const override {
+        return takes_part(mask, want) && ((mask >> i) & 1) && __builtin_popcount(mask & ((1u << i) - 1)) < rs->k;
+    }
+    bool comes_back(uint32_t mask, uint32_t want, int i) const override {
+        return takes_part(mask, want) && ((want >> i) & 1);
+    }
+    int prepare(hipStream_t s) override { return ensure_dense_decode(rs, gd, s); }
+    int launch(const Batch& b, uint32_t* words, const uint32_t* want_words, hipStream_t s, bool) override {
+        return run_some(gd->decode_dense, uint32_t(rs->k), b, words, want_words, nullptr, s);
+    }
+    void done(uint32_t bad) override {
+        if (n_bad_stripes) *n_bad_stripes = bad;
+    }
+};
+
+// Verify: all n shards in, nothing but the mismatch words back. The words
+// always live in device memory (the pipeline's mask words): the kernels'
+// atomics stay on the device, and only the words cross PCIe back. Every launch
+// gets the true shard_len, never a length rounded up to the staging pitch: the
+// pad bytes of a reused slot hold garbage, and a verify compares what an encode
+// merely overwrites.
+struct HostVerify : HostOp {
+    HostVerify(const hec_rs_t* r, const Batch& b, uint32_t* mismatch, uint32_t* n_bad) {
+        rs = r, host = b, split = r->k, words = mismatch, n_bad_stripes = n_bad, true_len = true;
+        in = {0, r->n, r->n};
+    }
+    int launch(const Batch& b, uint32_t* dev_words, const uint32_t*, hipStream_t s, bool) override {
+        ScrubOut o;  // one verify launch into the chunk's words: no count
+        o.words = dev_words;
+        return run_scrub(*gd, b, ScrubSpec{}, o, s);
+    }
+    void done(uint32_t) override {
+        if (n_bad_stripes)
+            for (uint32_t s = 0; s < host.n_stripes; ++s) *n_bad_stripes += words[s] ? 1u : 0u;
+    }
+};
 
 }  // namespace
 }  // namespace hec
@@ -302,85 +542,11 @@ int hec_host_encode_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
                           uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes) {
     HEC_TRY(check_batch_args(rs, h_data, h_parity, shard_len));
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_encode_strides(rs, Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
-                                                  arena(h_parity, parity_stripe_stride, parity_shard_stride),
-                                                  shard_len, n_stripes)));
-    GeomDevice* gd;
-    HEC_TRY(geom_device(rs, &gd));
-    Lease<Pipeline> p;
-    HEC_TRY(lease_slot(p));
-    const int k = rs->k, m = rs->m;
-    uint8_t *zd, *zp;
-    if (host_device_view(h_data, batch_span(data_stripe_stride, data_shard_stride, k, shard_len, n_stripes), &zd) &&
-        host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
-                         &zp)) {
-        HEC_TRY(p->reserve(0, 1));
-        HEC_TRY(run_apply(gd->encode, uint32_t(k),
-                          Batch::split(arena(zd, data_stripe_stride, data_shard_stride),
-                                       arena(zp, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes),
-                          nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true));
-        HEC_HIP(hipStreamSynchronize(p->streams[0]));
-        return HEC_OK;
-    }
-    const uint64_t Lp = round_up(shard_len, 256);  // device shard pitch
-    // len rounded to 16: the pad bytes of the pitch are computed but never copied back
-    const uint64_t L16 = round_up(shard_len, 16);
-    const uint32_t C = chunk_stripes(Lp, rs->n, n_stripes);
-    const uint64_t dstripe = uint64_t(rs->n) * Lp;
-    if (zero_copy_enabled()) {
-        // Pageable memory: chunks are copied into two pinned slots on the host
-        // pool and coded in place by the zero-copy kernel.
-        HEC_TRY(p->reserve(0, 1));
-        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
-        uint8_t* zs[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
-        if (zs[0] && zs[1])
-            return two_slot_loop(
-                p.sc, n_stripes, C,
-                [&](uint32_t s0, uint32_t c, int q) {
-                    uint8_t* h = p->hslot[q];
-                    parallel_for(size_t(c) * k, uint64_t(c) * k * shard_len, [&](size_t t) {
-                        const uint32_t s = uint32_t(t / k);
-                        const int i = int(t % k);
-                        std::memcpy(h + s * dstripe + uint64_t(i) * Lp,
-                                    h_data + (s0 + s) * data_stripe_stride + i * data_shard_stride, shard_len);
-                    });
-                },
-                [&](uint32_t c, int q) {
-                    return run_apply(gd->encode, uint32_t(k), Batch::split_at(arena(zs[q], dstripe, Lp), k, L16, c),
-                                     nullptr, nullptr, p->streams[0], nullptr, /*over_pcie=*/true);
-                },
-                [&](uint32_t s0, uint32_t c, int q) {
-                    parallel_for(size_t(c) * m, uint64_t(c) * m * shard_len, [&](size_t t) {
-                        const uint32_t s = uint32_t(t / m);
-                        const int j = int(t % m);
-                        std::memcpy(h_parity + (s0 + s) * parity_stripe_stride + j * parity_shard_stride,
-                                    p->hslot[q] + s * dstripe + uint64_t(k + j) * Lp, shard_len);
-                    });
-                });
-    }
-    HEC_TRY(p->reserve(size_t(C) * rs->n * Lp, 1));
-    const int fail_at = forced_failure_chunk();
-    return copy_loop(
-        p.sc, n_stripes, C,
-        [&](uint32_t s0, uint32_t c, int q) -> int {
-            for (uint32_t s = 0; s < c; ++s)  // data shards of stripe s -> [s][0..k)
-                HEC_HIP(copy2d(p->slot[q] + s * dstripe, Lp, h_data + (s0 + s) * data_stripe_stride,
-                               data_shard_stride, shard_len, uint64_t(k), hipMemcpyHostToDevice, p->streams[q]));
-            return HEC_OK;
-        },
-        [&](uint32_t c, int q, uint32_t it) -> int {
-            HEC_TRY(run_apply(gd->encode, uint32_t(k), Batch::split_at(arena(p->slot[q], dstripe, Lp), k, L16, c),
-                              nullptr, nullptr, p->streams[q]));
-            if (int(it) == fail_at) return fail(HEC_ERR_HIP, "test hook: failure after chunk " + std::to_string(it));
-            return HEC_OK;
-        },
-        [&](uint32_t s0, uint32_t c, int q) -> int {
-            for (uint32_t s = 0; s < c; ++s)
-                HEC_HIP(copy2d(h_parity + (s0 + s) * parity_stripe_stride, parity_shard_stride,
-                               p->slot[q] + s * dstripe + uint64_t(k) * Lp, Lp, shard_len, uint64_t(m),
-                               hipMemcpyDeviceToHost, p->streams[q]));
-            return HEC_OK;
-        });
+    const Batch b = Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
+                                 arena(h_parity, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_encode_strides(rs, b));
+    HostEncode op(rs, b);
+    return run_host_op(op);
 }
 
 int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
@@ -389,163 +555,23 @@ int hec_host_reconstruct_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t s
     HEC_TRY(check_batch_args(rs, h_shards, h_present_masks, shard_len));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_strided("shards", uint32_t(rs->n), arena(h_shards, stripe_stride, shard_stride), shard_len,
-                          n_stripes));
-    return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks, nullptr,
-                            n_bad_stripes);
+    const Batch b = Batch::in_place(arena(h_shards, stripe_stride, shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_strided("shards", uint32_t(rs->n), b.in, shard_len, n_stripes));
+    HostReconstruct op(rs, b, h_present_masks, nullptr, n_bad_stripes);
+    return run_host_op(op);
 }
 
 int hec_host_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride,
                                     uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
                                     const uint32_t* h_present_masks, const uint32_t* h_want_masks,
                                     uint32_t* n_bad_stripes) {
-    HEC_TRY(check_some_args(rs, Batch::in_place(arena(h_shards, stripe_stride, shard_stride), shard_len, n_stripes),
-                            h_present_masks, h_want_masks));
+    const Batch b = Batch::in_place(arena(h_shards, stripe_stride, shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_some_args(rs, b, h_present_masks, h_want_masks));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    return host_reconstruct(rs, h_shards, stripe_stride, shard_stride, shard_len, n_stripes, h_present_masks,
-                            h_want_masks, n_bad_stripes);
+    HostReconstruct op(rs, b, h_present_masks, h_want_masks, n_bad_stripes);
+    return run_host_op(op);
 }
-
-}  // extern "C"
-
-namespace hec {
-namespace {
-
-int host_reconstruct(const hec_rs_t* rs, uint8_t* h_shards, uint64_t stripe_stride, uint64_t shard_stride,
-                     uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_present_masks,
-                     const uint32_t* h_want_masks, uint32_t* n_bad_stripes) {
-    const uint32_t* const wants = h_want_masks;
-    GeomDevice* gd;
-    HEC_TRY(geom_device(rs, &gd));
-    Lease<Pipeline> p;
-    HEC_TRY(lease_slot(p));
-    const int k = rs->k, n = rs->n;
-    const uint32_t full = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1);
-    uint32_t bad = 0;
-    // the erased shards stripe s of slot q's chunk rebuilds (0: it takes no part)
-    auto wanted = [&](int q, uint32_t s) { return wants ? p->want_host[q][s] : ~p->mask_host[q][s] & full; };
-    uint8_t* zs;
-    if (host_device_view(h_shards, batch_span(stripe_stride, shard_stride, n, shard_len, n_stripes), &zs)) {
-        // masks to the device (the caller's array may be pageable), then one
-        // decode over the pinned host shards in place
-        HEC_TRY(p->reserve(0, n_stripes));
-        if (wants) HEC_TRY(p->reserve_wants(n_stripes));
-        HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
-        bad = load_masks(p->mask_host[0], h_present_masks, n_stripes, full, k, p->want_host[0], wants);
-        HEC_HIP(hipMemcpyAsync(p->mask_dev[0], p->mask_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
-                               p->streams[0]));
-        if (wants)
-            HEC_HIP(hipMemcpyAsync(p->want_dev[0], p->want_host[0], size_t(n_stripes) * 4, hipMemcpyHostToDevice,
-                                   p->streams[0]));
-        HEC_TRY(run_some(gd->decode_dense, uint32_t(k),
-                         Batch::in_place(arena(zs, stripe_stride, shard_stride), shard_len, n_stripes), p->mask_dev[0],
-                         wants ? p->want_dev[0].p : nullptr, nullptr, p->streams[0]));
-        HEC_HIP(hipStreamSynchronize(p->streams[0]));
-        if (n_bad_stripes) *n_bad_stripes = bad;
-        return HEC_OK;
-    }
-    const uint64_t Lp = round_up(shard_len, 256), L16 = round_up(shard_len, 16);
-    const uint32_t C = chunk_stripes(Lp, n, n_stripes);
-    const uint64_t dstripe = uint64_t(n) * Lp;
-    auto host_shard = [&](uint32_t s, int i) { return h_shards + s * stripe_stride + uint64_t(i) * shard_stride; };
-    auto finish = [&](int rc) {
-        if (!rc && n_bad_stripes) *n_bad_stripes = bad;
-        return rc;
-    };
-    if (zero_copy_enabled()) {
-        // Pageable memory: the first k present shards of each stripe are copied
-        // into two pinned slots on the host pool, decoded in place there by the
-        // zero-copy kernel, and only the erased shards are copied back.
-        HEC_TRY(p->reserve(0, C));
-        if (wants) HEC_TRY(p->reserve_wants(C));
-        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
-        HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
-        uint8_t* hz[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
-        uint32_t* zm[2] = {reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[0])),
-                           reinterpret_cast<uint32_t*>(pinned_device_ptr(p->mask_host[1]))};
-        uint32_t* zw[2] = {nullptr, nullptr};
-        if (wants)
-            for (int q = 0; q < 2; ++q) zw[q] = reinterpret_cast<uint32_t*>(pinned_device_ptr(p->want_host[q]));
-        if (hz[0] && hz[1] && zm[0] && zm[1] && (!wants || (zw[0] && zw[1])))
-            return finish(two_slot_loop(
-                p.sc, n_stripes, C,
-                [&](uint32_t s0, uint32_t c, int q) {
-                    bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k, p->want_host[q],
-                                      wants ? wants + s0 : nullptr);
-                    parallel_for(size_t(c) * n, uint64_t(c) * k * shard_len, [&](size_t t) {
-                        const uint32_t s = uint32_t(t / n);
-                        const int i = int(t % n);
-                        const uint32_t mask = p->mask_host[q][s];
-                        if (__builtin_popcount(mask) < k || !wanted(q, s) || !((mask >> i) & 1)) return;
-                        if (__builtin_popcount(mask & ((1u << i) - 1)) >= k) return;  // only the first k present
-                        std::memcpy(p->hslot[q] + s * dstripe + uint64_t(i) * Lp, host_shard(s0 + s, i), shard_len);
-                    });
-                },
-                [&](uint32_t c, int q) {
-                    return run_some(gd->decode_dense, uint32_t(k), Batch::in_place(arena(hz[q], dstripe, Lp), L16, c),
-                                    zm[q], zw[q], nullptr, p->streams[0]);
-                },
-                [&](uint32_t s0, uint32_t c, int q) {
-                    parallel_for(size_t(c) * n, uint64_t(c) * 4 * shard_len, [&](size_t t) {
-                        const uint32_t s = uint32_t(t / n);
-                        const int i = int(t % n);
-                        const uint32_t mask = p->mask_host[q][s];
-                        if (__builtin_popcount(mask) < k || !((wanted(q, s) >> i) & 1)) return;
-                        std::memcpy(host_shard(s0 + s, i), p->hslot[q] + s * dstripe + uint64_t(i) * Lp, shard_len);
-                    });
-                }));
-    }
-    HEC_TRY(p->reserve(size_t(C) * n * Lp, C));
-    if (wants) HEC_TRY(p->reserve_wants(C));
-    HEC_TRY(ensure_dense_decode(rs, gd, p->streams[0]));
-    auto dev_shard = [&](int q, uint32_t s, int i) { return p->slot[q] + s * dstripe + uint64_t(i) * Lp; };
-    return finish(copy_loop(
-        p.sc, n_stripes, C,
-        [&](uint32_t s0, uint32_t c, int q) -> int {
-            // the staging of this slot was last read by the copy issued kDepth chunks ago
-            HEC_HIP(hipStreamSynchronize(p->streams[q]));
-            bad += load_masks(p->mask_host[q], h_present_masks + s0, c, full, k, p->want_host[q],
-                              wants ? wants + s0 : nullptr);
-            for (uint32_t s = 0; s < c; ++s) {
-                const uint32_t mask = p->mask_host[q][s];
-                if (__builtin_popcount(mask) < k || !wanted(q, s)) continue;
-                // H2D only the first k present shards (the ones the decode reads),
-                // merged into runs of adjacent shard ids
-                HEC_TRY(for_bit_runs(mask, n, k, [&](int i, int count) -> int {
-                    HEC_HIP(copy2d(dev_shard(q, s, i), Lp, host_shard(s0 + s, i), shard_stride, shard_len,
-                                   uint64_t(count), hipMemcpyHostToDevice, p->streams[q]));
-                    return HEC_OK;
-                }));
-            }
-            HEC_HIP(hipMemcpyAsync(p->mask_dev[q], p->mask_host[q], c * 4, hipMemcpyHostToDevice, p->streams[q]));
-            if (wants)
-                HEC_HIP(hipMemcpyAsync(p->want_dev[q], p->want_host[q], c * 4, hipMemcpyHostToDevice, p->streams[q]));
-            return HEC_OK;
-        },
-        [&](uint32_t c, int q, uint32_t) {
-            return run_some(gd->decode_dense, uint32_t(k), Batch::in_place(arena(p->slot[q], dstripe, Lp), L16, c),
-                            p->mask_dev[q], wants ? p->want_dev[q].p : nullptr, nullptr, p->streams[q]);
-        },
-        [&](uint32_t s0, uint32_t c, int q) -> int {
-            for (uint32_t s = 0; s < c; ++s) {
-                const uint32_t mask = p->mask_host[q][s];
-                if (__builtin_popcount(mask) < k) continue;
-                // D2H the erased shards that were rebuilt, merged into runs
-                HEC_TRY(for_bit_runs(wanted(q, s), n, n, [&](int i, int count) -> int {
-                    HEC_HIP(copy2d(host_shard(s0 + s, i), shard_stride, dev_shard(q, s, i), Lp, shard_len,
-                                   uint64_t(count), hipMemcpyDeviceToHost, p->streams[q]));
-                    return HEC_OK;
-                }));
-            }
-            return HEC_OK;
-        }));
-}
-
-}  // namespace
-}  // namespace hec
-
-extern "C" {
 
 int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t data_stripe_stride,
                           uint64_t data_shard_stride, const uint8_t* h_parity, uint64_t parity_stripe_stride,
@@ -555,98 +581,11 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
     HEC_TRY(check_verify_args(rs, h_mismatch));
     if (n_bad_stripes) *n_bad_stripes = 0;
     if (n_stripes == 0) return HEC_OK;
-    HEC_TRY(check_encode_strides(rs, Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
-                                                  arena(h_parity, parity_stripe_stride, parity_shard_stride),
-                                                  shard_len, n_stripes)));
-    GeomDevice* gd;
-    HEC_TRY(geom_device(rs, &gd));
-    Lease<Pipeline> p;
-    HEC_TRY(lease_slot(p));
-    const int k = rs->k, m = rs->m, n = rs->n;
-    // one verify launch into slot q's words: no count
-    auto verify = [&](const Batch& b, int q, hipStream_t s) {
-        ScrubOut out;
-        out.words = p->mask_dev[q];
-        return run_scrub(*gd, b, ScrubSpec{}, out, s);
-    };
-    auto finish = [&](int rc) {
-        if (!rc && n_bad_stripes)
-            for (uint32_t s = 0; s < n_stripes; ++s) *n_bad_stripes += h_mismatch[s] ? 1u : 0u;
-        return rc;
-    };
-    // The result words always live in device memory (the pipeline's mask
-    // words): the kernels' atomics stay on the device, and only the words
-    // cross PCIe back. Every launch gets the true shard_len, never a length
-    // rounded up to the staging pitch: the pad bytes of a reused slot hold
-    // garbage, and a verify compares what an encode merely overwrites.
-    uint8_t *zd, *zp;
-    if (host_device_view(h_data, batch_span(data_stripe_stride, data_shard_stride, k, shard_len, n_stripes), &zd) &&
-        host_device_view(h_parity, batch_span(parity_stripe_stride, parity_shard_stride, m, shard_len, n_stripes),
-                         &zp)) {
-        HEC_TRY(p->reserve(0, n_stripes));
-        HEC_TRY(verify(Batch::split(arena(zd, data_stripe_stride, data_shard_stride),
-                                    arena(zp, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes),
-                       0, p->streams[0]));
-        HEC_HIP(hipMemcpyAsync(p->mask_host[0], p->mask_dev[0], size_t(n_stripes) * 4, hipMemcpyDeviceToHost,
-                               p->streams[0]));
-        HEC_HIP(hipStreamSynchronize(p->streams[0]));
-        std::memcpy(h_mismatch, p->mask_host[0], size_t(n_stripes) * 4);
-        return finish(HEC_OK);
-    }
-    const uint64_t Lp = round_up(shard_len, 256);  // staging shard pitch
-    const uint32_t C = chunk_stripes(Lp, n, n_stripes);
-    const uint64_t dstripe = uint64_t(n) * Lp;
-    auto host_shard = [&](uint32_t s, int i) {
-        return i < k ? h_data + s * data_stripe_stride + uint64_t(i) * data_shard_stride
-                     : h_parity + s * parity_stripe_stride + uint64_t(i - k) * parity_shard_stride;
-    };
-    if (zero_copy_enabled()) {
-        // Pageable memory: all 14 shards of a chunk are packed into a pinned
-        // slot the kernel reads over PCIe; nothing but the words comes back.
-        HEC_TRY(p->reserve(0, C));
-        HEC_TRY(p->reserve_host(size_t(C) * dstripe));
-        uint8_t* zs[2] = {pinned_device_ptr(p->hslot[0]), pinned_device_ptr(p->hslot[1])};
-        if (zs[0] && zs[1])
-            return finish(two_slot_loop(
-                p.sc, n_stripes, C,
-                [&](uint32_t s0, uint32_t c, int q) {
-                    uint8_t* h = p->hslot[q];
-                    parallel_for(size_t(c) * n, uint64_t(c) * n * shard_len, [&](size_t t) {
-                        const uint32_t s = uint32_t(t / n);
-                        const int i = int(t % n);
-                        std::memcpy(h + s * dstripe + uint64_t(i) * Lp, host_shard(s0 + s, i), shard_len);
-                    });
-                },
-                [&](uint32_t c, int q) -> int {
-                    HEC_TRY(verify(Batch::split_at(arena(zs[q], dstripe, Lp), k, shard_len, c), q, p->streams[0]));
-                    HEC_HIP(hipMemcpyAsync(p->mask_host[q], p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
-                                           p->streams[0]));
-                    return HEC_OK;
-                },
-                [&](uint32_t s0, uint32_t c, int q) {
-                    std::memcpy(h_mismatch + s0, p->mask_host[q], size_t(c) * 4);
-                }));
-    }
-    HEC_TRY(p->reserve(size_t(C) * dstripe, C));
-    return finish(copy_loop(
-        p.sc, n_stripes, C,
-        [&](uint32_t s0, uint32_t c, int q) -> int {
-            for (uint32_t s = 0; s < c; ++s) {  // 14-shard H2D: data then parity of stripe s -> [s][0..n)
-                HEC_HIP(copy2d(p->slot[q] + s * dstripe, Lp, host_shard(s0 + s, 0), data_shard_stride, shard_len,
-                               uint64_t(k), hipMemcpyHostToDevice, p->streams[q]));
-                HEC_HIP(copy2d(p->slot[q] + s * dstripe + uint64_t(k) * Lp, Lp, host_shard(s0 + s, k),
-                               parity_shard_stride, shard_len, uint64_t(m), hipMemcpyHostToDevice, p->streams[q]));
-            }
-            return HEC_OK;
-        },
-        [&](uint32_t c, int q, uint32_t) {
-            return verify(Batch::split_at(arena(p->slot[q], dstripe, Lp), k, shard_len, c), q, p->streams[q]);
-        },
-        [&](uint32_t s0, uint32_t c, int q) -> int {  // D2H of the words only
-            HEC_HIP(hipMemcpyAsync(h_mismatch + s0, p->mask_dev[q], size_t(c) * 4, hipMemcpyDeviceToHost,
-                                   p->streams[q]));
-            return HEC_OK;
-        }));
+    const Batch b = Batch::split(arena(h_data, data_stripe_stride, data_shard_stride),
+                                 arena(h_parity, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_encode_strides(rs, b));
+    HostVerify op(rs, b, h_mismatch, n_bad_stripes);
+    return run_host_op(op);
 }
 
 int hec_host_encode_batch_multi(const hec_rs_t* rs, const int* devices, size_t n_devices, const uint8_t* h_data,

@@ -338,6 +338,45 @@ def test_host_batch_across_chunk_edges(gpu, host_arenas, path):
             M.assert_counted(plan, bad, (path, lay))
 
 
+PINNED_COPY_S, PINNED_COPY_L = 10, 1000  # chunks of 3, 3, 3 and 1 stripes in the small-chunk build
+PINNED_COPY_LOST = (1, 2, 5, 0, 3, 4, 0, 1, 2, 5)  # shards lost per stripe: 5 | 0 at the first chunk edge, 5 alone last
+
+
+def test_host_batch_pinned_memory_on_the_copy_pipeline(gpu, host_arenas):
+    """6c. Pinned memory with zero copy off: the copy pipeline's 2-D copies
+    read and write the caller's pinned arena (the three paths above give it
+    pageable memory only). Ten stripes of 1000 bytes with a mask of its own
+    each, against some_model: two stripes with 5 shards lost (one wants a lost
+    shard, one everything: both counted, both untouched), two with none lost,
+    one that wants nothing, the others all or one of their lost shards. In the
+    small-chunk build the chunks are 3, 3, 3 and 1 stripes: all three streams
+    and device slots reused, a short last chunk, and 1000 is a multiple of
+    neither 16 nor 256."""
+    import helyim_amd as H
+    rs = H.ReedSolomon(K, MP)
+    rng = np.random.default_rng(680)
+    S, L = PINNED_COPY_S, PINNED_COPY_L
+    lay = F.stripe_major(N, L, S, F.r16(L) + 16, 48)
+    stripes = F.stripes_of(lay)
+    masks, wants = [], []
+    for s, e in enumerate(PINNED_COPY_LOST):
+        m = erase(rng, e)
+        gone = [i for i in range(N) if not (m >> i) & 1]
+        kind = "all one one none none all one all none all".split()[s]
+        w = {"all": 0xFFFFFFFF, "one": 1 << gone[s % len(gone)] if gone else 0, "none": 0}[kind]
+        masks.append(m)
+        wants.append(noisy(rng, m, w))
+    with host_path(HOST_PATHS[2]) as hp:  # zero copy off ...
+        live, before = host_arenas.take(HOST_PATHS[0], stripes, rng)  # ... on the pinned buffers
+        plan = M.plan_reconstruct_some(before, stripes, K, MP, present_of(masks, N), wants)
+        assert plan.n_bad == 2 and plan.n_noop_short == 0
+        hp.check_view(live, lay)
+        rc, bad = host_some(rs, live, lay, masks, wants)
+        assert rc == 0
+        F.assert_footprint(plan, live, ("pinned copy2d", lay))
+        M.assert_counted(plan, bad, ("pinned copy2d", lay))
+
+
 def per_call_stripe(rng, k, m, L, base):
     n = k + m
     stride = F.r16(L) + 16

@@ -6,8 +6,8 @@ The product's sizes (96 MiB, 4 MiB, 1 MiB) keep almost every host batch and
 volume of the suite inside chunk 0, slot 0. Every selected test compares the
 library with the C oracle, tests/footprint.py, some_model or the scrub models,
 never with itself, so under the variant their batches of a few hundred KiB
-become chunk-boundary tests: both pinned slots of two_slot_loop and all three
-streams of copy_loop reused, s0 > 0 in every pack, launch and unpack, short
+become chunk-boundary tests: both pinned slots and all three streams and
+device slots of run_host_op reused, s0 > 0 in every pack, launch and unpack, short
 last chunks, the file scrubs' collect(c - 2) while later chunks are in flight,
 and rows read in several pieces with a ragged last one.
 
@@ -83,7 +83,7 @@ def test_variant_is_built_and_the_product_exports_no_query():
 def test_selected_host_shapes_cross_chunk_edges_under_the_variant():
     """From the selected tests' own shape constants: under the variant there
     are batches of several stripes a chunk in four or more chunks -- slot 0 of
-    both loops and stream 0 of copy_loop reused -- with a short last chunk,
+    both loops and stream 0 of the copy pipeline reused -- with a short last chunk,
     batches of one stripe a chunk, and batches that stay in one chunk; the
     product takes the reconstruct-some, footprint and generic-codec batches
     in one chunk each."""
@@ -98,6 +98,10 @@ def test_selected_host_shapes_cross_chunk_edges_under_the_variant():
     assert probe.host_chunks(TS.HOST_LENGTHS[1], 14, TS.HOST_S) == (1, 64, 1)
     assert probe.host_chunks(3000, 14, TS.HOST_S)[0] == 1  # the longer stripes that go through the slots first
     assert probe.host_chunks(TS.EDGE_L, 14, TS.EDGE_S, product)[1] == 1
+    # pinned memory on the copy pipeline, reconstruct some and verify: ten stripes in chunks of 3, 3, 3 and 1
+    for L, S in ((TS.PINNED_COPY_L, TS.PINNED_COPY_S), TV.PINNED_COPIES[::-1]):
+        assert probe.host_chunks(L, 14, S) == (3, 4, 1) and probe.host_chunks(L, 14, S, product)[1] == 1
+    assert (TS.PINNED_COPY_LOST[2], TS.PINNED_COPY_LOST[3], TS.PINNED_COPY_LOST[9]) == (5, 0, 5)
     # footprint: the mixed-mask batch in chunks of 3, 3, 3 and 2 with the edges the test names; the layout
     # families one stripe a chunk from 2048 bytes up, and nine stripes of 17 bytes in one chunk of up to 13
     L, lost = TF.MIXED

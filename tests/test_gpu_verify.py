@@ -556,6 +556,48 @@ def test_host_verify_across_chunks_shard_major(gpu, path):
     assert np.array_equal(data, d0) and np.array_equal(par, p0), path
 
 
+PINNED_COPIES = (10, 1000)  # stripes, shard length: chunks of 3, 3, 3 and 1 stripes in the small-chunk build
+
+
+def test_host_verify_pinned_memory_on_the_copy_pipeline(gpu):
+    """Pinned memory with zero copy off: the copy pipeline's two 2-D copies a
+    stripe read the caller's pinned arena (the tests above give that path
+    pageable memory only). Ten RS(10,4) stripes of 1000 bytes -- a multiple of
+    neither 16 nor 256 -- after ten random stripes of 1024 bytes went through
+    the same device slots, so the pads of the 1024-byte staging pitch hold
+    garbage. Dirty are both sides of the first chunk edge of the small-chunk
+    build (stripes 2 and 3), stripe 5 in its last data byte and the short last
+    chunk's only stripe; words and count against the oracle, clean batch all
+    zero, the caller's bytes as they were."""
+    import helyim_amd as H
+    S, L = PINNED_COPIES
+    k, m, n, pitch = 10, 4, 14, F.r16(L) + 48
+    rs = H.ReedSolomon(k, m)
+    image = np.random.default_rng(L).integers(0, 256, (S, n, pitch), dtype=np.uint8)  # the shard gaps too
+    image[:, k:, :L] = oracle_parity(k, m, image[:, :k, :L]).transpose(1, 0, 2)
+    dirty = image.copy()
+    dirty[2, 11, 0] ^= 0x01
+    dirty[3, 0, 17] ^= 0x80
+    dirty[5, 9, L - 1] ^= 0x10
+    dirty[9, 13, L - 1] ^= 0x04
+    want = batch_words(k, m, dirty[:, :k, :L], dirty[:, k:, :L])
+    assert np.flatnonzero(want).tolist() == [2, 3, 5, 9] and int(want[2]) == 1 << 1 and int(want[9]) == 1 << 3
+    big = random_image(S * n * 1024)
+    pinned = H.HostBuffer(image.nbytes)
+    try:
+        with host_path("copies"):
+            words, n_bad = host_verify(rs, *in_place(big.ctypes.data, k, n, 1024), 1024, S)
+            assert words.all() and n_bad == S
+            for label, img, expect in (("dirty", dirty, want), ("clean", image, np.zeros(S, np.uint32))):
+                pinned.array[:] = img.reshape(-1)
+                got = host_verify(rs, *in_place(pinned.ptr, k, n, pitch), L, S)
+                check_words(got, expect, (label, "pinned copies"))
+                assert np.array_equal(pinned.array, img.reshape(-1)), label
+    finally:
+        H.lib.hec_set_host_zero_copy(1)
+        pinned.close()
+
+
 @pytest.fixture(scope="module")
 def thread_batches():
     """Four batches (dirty, its copy, reference words), each built by a thread
