@@ -119,6 +119,49 @@ def reconstruct_some_kernel_name(L: int) -> str:
     return lib.hec_reconstruct_some_kernel_name(L).decode()
 
 
+def _update(rs, old, new, parity, update_masks, stream):
+    """old / new: (pointer, stripe stride, shard stride) of data arenas indexed
+    by shard id; parity: the checked [S, m, L] tensor."""
+    S, _m, L = parity.shape
+    if update_masks is None:
+        raise ValueError("update_masks is required")
+    masks = _words_arg(S, update_masks, "update_masks")
+    check(lib.hec_gpu_update_batch(rs.handle, *old, *new, parity.data_ptr(), parity.stride(0), parity.stride(1), L, S,
+                                   masks.data_ptr(), _stream_ptr(stream)))
+
+
+def update_batch(rs: ReedSolomon, stripes: torch.Tensor, new_data: torch.Tensor, update_masks: torch.Tensor,
+                 stream=None) -> None:
+    """Fold changed data shards into the stored parity of ``stripes[S, 14, L]``
+    in place (hec_gpu_update_batch, RS(10,4)): update_masks 32-bit ``[S]``, bit
+    c = data shard c changed from ``stripes[s, c]`` (old) to ``new_data[s, c]``
+    (``new_data[S, 10, L]``). Only the four parity shards of stripes with a
+    non-empty mask are written; only the shards a mask names are read. The
+    new data is not copied over the old. Asynchronous on the stream."""
+    _check_stripes(stripes, rs)
+    k = rs.data_shard_count()
+    update_batch_sep(rs, stripes[:, :k], new_data, stripes[:, k:], update_masks, stream)
+
+
+def update_batch_sep(rs: ReedSolomon, old: torch.Tensor, new: torch.Tensor, parity: torch.Tensor,
+                     update_masks: torch.Tensor, stream=None) -> None:
+    """update_batch of old[S, k, L] -> new[S, k, L] into parity[S, m, L]
+    (separate buffers). ``old`` may be None: old is zero, and the parity
+    accumulates the coded new shards (over zeroed parity, any partition of the
+    data shards into calls gives encode_batch's bytes)."""
+    _layout_sep(rs, new, parity)
+    old_arg = (None, 0, 0)
+    if old is not None:
+        _layout_sep(rs, old, parity)
+        old_arg = (old.data_ptr(), old.stride(0), old.stride(1))
+    _update(rs, old_arg, (new.data_ptr(), new.stride(0), new.stride(1)), parity, update_masks, stream)
+
+
+def update_kernel_name(L: int) -> str:
+    """Kernel an aligned update_batch of shard length L runs (hec_update_kernel_name)."""
+    return lib.hec_update_kernel_name(L).decode()
+
+
 def _words_arg(S: int, t: torch.Tensor, name: str) -> torch.Tensor:
     """A per-stripe result tensor (mismatch, suspects, present_masks): allocated when not given."""
     if t is None:
@@ -516,6 +559,27 @@ def host_reconstruct_some_batch(rs: ReedSolomon, stripes: torch.Tensor, present_
     _host_call("hec_host_reconstruct_some_batch", rs, None, *shards, L, S, m.ctypes.data, w.ctypes.data,
                ctypes.byref(bad))
     return int(bad.value)
+
+
+def host_update_batch(rs: ReedSolomon, delta: torch.Tensor, parity: torch.Tensor, update_masks) -> None:
+    """Fold host-memory deltas into host-memory parity on the GPU
+    (hec_host_update_batch, RS(10,4)): ``delta[S, 10, L]`` holds old ^ new of
+    each changed data shard (or the new shard where the parity has not seen it
+    yet), ``parity[S, 4, L]`` is updated in place, update_masks one word per
+    stripe (bit c = data shard c changed). Only the named deltas and the parity
+    of the stripes with a non-empty mask cross PCIe. Synchronous."""
+    k, m = rs.data_shard_count(), rs.parity_shard_count()
+    for t, n, name in ((delta, k, "delta"), (parity, m, "parity")):
+        if t.dtype != torch.uint8 or t.is_cuda or t.dim() != 3 or t.stride(2) != 1:
+            raise TypeError(f"{name}: expected a host uint8 tensor [stripes, shards, L] with contiguous shards")
+        if t.shape[1] != n:
+            raise ValueError(f"{name}: expected {n} shards per stripe, got {t.shape[1]}")
+    S, _k, L = delta.shape
+    if parity.shape[0] != S or parity.shape[2] != L:
+        raise ValueError(f"parity {tuple(parity.shape)} does not match delta {tuple(delta.shape)}")
+    w = _host_masks(S, update_masks, "update")
+    _host_call("hec_host_update_batch", rs, None, delta.data_ptr(), delta.stride(0), delta.stride(1),
+               parity.data_ptr(), parity.stride(0), parity.stride(1), L, S, w.ctypes.data)
 
 
 def host_verify_batch(rs: ReedSolomon, stripes: torch.Tensor):

@@ -114,6 +114,23 @@ const char* hec_reconstruct_some_batch_kernel_name(const uint8_t* d_shards, uint
     return some_batch_kernel_name(shard_len, n_stripes, b.aligned());
 }
 
+int hec_gpu_update_batch(const hec_rs_t* rs, const uint8_t* d_old, uint64_t old_stripe_stride,
+                         uint64_t old_shard_stride, const uint8_t* d_new, uint64_t new_stripe_stride,
+                         uint64_t new_shard_stride, uint8_t* d_parity, uint64_t parity_stripe_stride,
+                         uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                         const uint32_t* d_update_masks, void* stream) {
+    const Strided old = arena(d_old, old_stripe_stride, old_shard_stride);
+    const Batch b = Batch::split(arena(d_new, new_stripe_stride, new_shard_stride),
+                                 arena(d_parity, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_update_args(rs, old, b, d_update_masks));
+    if (n_stripes == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    return run_update(gd->encode, old, b, d_update_masks, static_cast<hipStream_t>(stream));
+}
+
+const char* hec_update_kernel_name(uint64_t shard_len) { return update_kernel_name(shard_len); }
+
 // The scrubs of separate data and parity arenas (hec_gpu_verify_batch, the
 // locates and the corrects): one body. spec: the pass 2 and its pairs form.
 static int scrub_batch(const hec_rs_t* rs, const uint8_t* d_data, uint64_t data_stripe_stride,

@@ -2,7 +2,7 @@
 // record (errors.cpp), the strided batch view (Strided, Batch), staging
 // buffers, the per-device registry and slot leases, the host worker pool
 // (host_pool.cpp), plans, per-geometry device state and the launches of a
-// plan set or a scrub over a batch (plans.cpp: run_apply, run_some, run_scrub)
+// plan set or a scrub over a batch (plans.cpp: run_apply, run_some, run_update, run_scrub)
 // and the per-call host paths' scratch (host_calls.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -494,6 +494,23 @@ inline int check_some_args(const hec_rs* rs, const Batch& b, const void* masks, 
     if (rs->k != 10 || rs->m != 4)
         return fail(HEC_ERR_INVALID_ARGUMENT, "batched reconstruct some is RS(10,4) only");
     return check_strided("shards", uint32_t(rs->n), b.in, b.len, b.n_stripes);
+}
+
+// Update over a strided RS(10,4) batch (hec.h hec_gpu_update_batch is the
+// contract), asynchronously on s: parity ^= P[:,U] * (old[U] ^ new[U]) with U
+// from masks (device words). enc: the RS(10,4) encode set. old.base == nullptr:
+// old is zero. b.in = the new data arena, b.out = the parity arena.
+int run_update(const DevicePlanSet& enc, const Strided& old, const Batch& b, const uint32_t* masks, hipStream_t s,
+               Completion* done = nullptr);
+// Prologue of the update batch entry points: nulls, the empty shard, the
+// codec, the layouts (the old arena only when given). All before device work.
+inline int check_update_args(const hec_rs* rs, const Strided& old, const Batch& b, const void* masks) {
+    if (!rs || !b.in.base || !b.out.base || !masks) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (b.len == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+    if (rs->k != 10 || rs->m != 4) return fail(HEC_ERR_INVALID_ARGUMENT, "batched update is RS(10,4) only");
+    if (old.base) HEC_TRY(check_strided("old data", uint32_t(rs->k), old, b.len, b.n_stripes));
+    HEC_TRY(check_strided("new data", uint32_t(rs->k), b.in, b.len, b.n_stripes));
+    return check_strided("parity", uint32_t(rs->m), b.out, b.len, b.n_stripes);
 }
 
 // The scrub of a strided batch, asynchronously on s with no host

@@ -198,6 +198,90 @@ static int reconstruct_host(const hec_rs* rs, uint8_t* const* shards, const size
     return HEC_OK;
 }
 
+// hec_rs_update after its checks: the deltas old ^ new of the changed shards
+// (XORed while packing) and the m parity shards in pinned staging, shard i at
+// i * Lp, coded in place there over PCIe or through device staging, and the
+// parity copied back. RS(10,4): the update kernel with no old arena, its mask
+// word behind the shards. Any other codec: the generic plan interpreter over an
+// ad-hoc plan whose inputs are the deltas and the parity shards and whose
+// outputs are the parity shards in place, coefficients [P[:,U] | I]. A lane
+// loads its vector of every input before it stores its rows (apply_group), and
+// a later row group re-reads the rows an earlier one stored with coefficient 0
+// only, so in place is safe.
+static int update_host(const hec_rs* rs, uint8_t* const* shards, const uint8_t* const* new_data, size_t L) {
+    const int k = rs->k, m = rs->m, n = rs->n;
+    const bool is104 = k == 10 && m == 4;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<Scratch> lease;
+    HEC_TRY(lease_slot(lease));
+    Scratch* sc = lease.sc;
+    const uint64_t Lp = round_up(L, 256);
+    const size_t words_off = size_t(n) * Lp, bytes = words_off + 256;
+    HEC_TRY(sc->hbuf.reserve(bytes, kStagingFloor));
+    std::vector<uint32_t> in_ids, out_ids;
+    uint32_t mask = 0;
+    for (int c = 0; c < k; ++c)
+        if (new_data[c]) {
+            in_ids.push_back(uint32_t(c));
+            if (is104) mask |= 1u << c;
+        }
+    const size_t n_changed = in_ids.size();
+    if (!is104) {
+        for (int j = 0; j < m; ++j) {
+            in_ids.push_back(uint32_t(k + j));
+            out_ids.push_back(uint32_t(k + j));
+        }
+        Mat coefs(m, int(in_ids.size()));
+        for (int j = 0; j < m; ++j) {
+            for (size_t t = 0; t < n_changed; ++t) coefs.at(j, int(t)) = rs->matrix.at(k + j, int(in_ids[t]));
+            coefs.at(j, int(n_changed) + j) = 1;
+        }
+        HostPlans hp;
+        hp.add(coefs, in_ids, out_ids);
+        HEC_TRY(sc->adhoc.upload(hp, nullptr, sc->stream));
+    }
+    const uint64_t moved = uint64_t(n_changed + size_t(m)) * L;
+    parallel_for(size_t(n), moved, [&](size_t i) {
+        uint8_t* dst = sc->hbuf + i * Lp;
+        if (i >= size_t(k)) {
+            std::memcpy(dst, shards[i], L);
+        } else if (new_data[i]) {
+            const uint8_t *o = shards[i], *w = new_data[i];
+            for (size_t b = 0; b < L; ++b) dst[b] = o[b] ^ w[b];
+        }
+    });
+    std::memcpy(sc->hbuf + words_off, &mask, sizeof mask);
+    uint8_t* zh = zero_copy_enabled() ? pinned_device_ptr(sc->hbuf) : nullptr;
+    uint8_t* dev = zh;
+    const size_t par_off = size_t(k) * Lp;
+    if (!zh) {
+        HEC_TRY(sc->dbuf.reserve(bytes, kStagingFloor));
+        dev = sc->dbuf;
+        for (size_t t = 0; t < n_changed; ++t)
+            HEC_HIP(hipMemcpyAsync(dev + in_ids[t] * Lp, sc->hbuf + in_ids[t] * Lp, L, hipMemcpyHostToDevice,
+                                   sc->stream));
+        // the parity shards and the mask word behind them
+        HEC_HIP(hipMemcpyAsync(dev + par_off, sc->hbuf + par_off, bytes - par_off, hipMemcpyHostToDevice, sc->stream));
+    }
+    const Strided st = arena(dev, 0, Lp);
+    Completion* done = zh && moved <= completion_flag_max() ? &sc->done : nullptr;
+    if (is104)
+        HEC_TRY(run_update(gd->encode, Strided{}, Batch::split_at(st, k, round_up(L, 16), 1),
+                           reinterpret_cast<const uint32_t*>(dev + words_off), sc->stream, done));
+    else
+        HEC_TRY(run_apply(sc->adhoc, uint32_t(in_ids.size()), Batch::in_place(st, round_up(L, 16), 1), nullptr, nullptr,
+                          sc->stream, done));
+    if (!zh)
+        HEC_HIP(hipMemcpyAsync(sc->hbuf + par_off, dev + par_off, size_t(m - 1) * Lp + L, hipMemcpyDeviceToHost,
+                               sc->stream));
+    if (done) HEC_TRY(done->wait(sc->stream));
+    else HEC_HIP(hipStreamSynchronize(sc->stream));
+    parallel_for(size_t(m), uint64_t(m) * L,
+                 [&](size_t j) { std::memcpy(shards[size_t(k) + j], sc->hbuf + par_off + j * Lp, L); });
+    return HEC_OK;
+}
+
 }  // namespace hec
 
 using namespace hec;
@@ -271,6 +355,31 @@ int hec_rs_reconstruct_some(const hec_rs_t* rs, uint8_t* const* shards, const si
     if (!rs) return fail(HEC_ERR_INVALID_ARGUMENT, "null codec");
     if (!required) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
     return reconstruct_host(rs, shards, shard_lens, present, n_shards, required);
+}
+
+int hec_rs_update(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
+                  const uint8_t* const* new_data, size_t n_shards) {
+    if (!rs || !shards || !shard_lens || !new_data) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_shards < size_t(rs->n)) return fail(HEC_ERR_TOO_FEW_SHARDS, "");
+    if (n_shards > size_t(rs->n)) return fail(HEC_ERR_TOO_MANY_SHARDS, "");
+    bool any = false;
+    for (int i = 0; i < rs->n; ++i) {
+        const bool used = i >= rs->k || new_data[i];
+        if (i < rs->k) any = any || used;
+        if (used && !shards[i])
+            return fail(HEC_ERR_INVALID_ARGUMENT,
+                        i < rs->k ? "changed shard without its old buffer" : "null parity shard");
+    }
+    // the lengths in use: the old slots of the changed shards and the parity
+    size_t L = 0;
+    for (int i = 0; i < rs->n; ++i) {
+        if (i < rs->k && !new_data[i]) continue;
+        if (shard_lens[i] == 0) return fail(HEC_ERR_EMPTY_SHARD, "");
+        if (L && shard_lens[i] != L) return fail(HEC_ERR_INCORRECT_SHARD_SIZE, "");
+        L = shard_lens[i];
+    }
+    if (!any) return HEC_OK;
+    return update_host(rs, shards, new_data, L);
 }
 
 }  // extern "C"

@@ -530,6 +530,29 @@ struct HostVerify : HostOp {
     }
 };
 
+// Update (hec.h hec_host_update_batch): host.in holds the deltas (old ^ new,
+// or the new shard where the parity has not seen it yet), host.out the parity.
+// Of a stripe whose mask names a shard, the named deltas and the four parity
+// shards go in, the update runs with no old arena, and the parity comes back;
+// a stripe with an empty mask moves nothing. The masks are update masks, not
+// present masks: what load_masks counts over them means nothing here, and the
+// bits it leaves above the data shards are the kernel's to ignore.
+struct HostUpdate : HostOp {
+    HostUpdate(const hec_rs_t* r, const Batch& b, const uint32_t* update_masks) {
+        rs = r, host = b, split = r->k, masks = update_masks;
+        in = {0, r->n, r->m + 1};
+        out = {r->k, r->n, r->m};
+    }
+    bool changed(uint32_t mask) const { return (mask & ((1u << rs->k) - 1)) != 0; }
+    bool goes_in(uint32_t mask, uint32_t, int i) const override {
+        return i < rs->k ? ((mask >> i) & 1) != 0 : changed(mask);
+    }
+    bool comes_back(uint32_t mask, uint32_t, int i) const override { return i >= rs->k && changed(mask); }
+    int launch(const Batch& b, uint32_t* words, const uint32_t*, hipStream_t s, bool) override {
+        return run_update(gd->encode, Strided{}, b, words, s);
+    }
+};
+
 }  // namespace
 }  // namespace hec
 
@@ -585,6 +608,18 @@ int hec_host_verify_batch(const hec_rs_t* rs, const uint8_t* h_data, uint64_t da
                                  arena(h_parity, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes);
     HEC_TRY(check_encode_strides(rs, b));
     HostVerify op(rs, b, h_mismatch, n_bad_stripes);
+    return run_host_op(op);
+}
+
+int hec_host_update_batch(const hec_rs_t* rs, const uint8_t* h_delta, uint64_t delta_stripe_stride,
+                          uint64_t delta_shard_stride, uint8_t* h_parity, uint64_t parity_stripe_stride,
+                          uint64_t parity_shard_stride, uint64_t shard_len, uint32_t n_stripes,
+                          const uint32_t* h_update_masks) {
+    const Batch b = Batch::split(arena(h_delta, delta_stripe_stride, delta_shard_stride),
+                                 arena(h_parity, parity_stripe_stride, parity_shard_stride), shard_len, n_stripes);
+    HEC_TRY(check_update_args(rs, Strided{}, b, h_update_masks));
+    if (n_stripes == 0) return HEC_OK;
+    HostUpdate op(rs, b, h_update_masks);
     return run_host_op(op);
 }
 

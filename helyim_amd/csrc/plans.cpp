@@ -369,6 +369,20 @@ int run_some(const DevicePlanSet& ps, uint32_t nin, const Batch& b, const uint32
     return HEC_OK;
 }
 
+int run_update(const DevicePlanSet& enc, const Strided& old, const Batch& b, const uint32_t* masks, hipStream_t s,
+               Completion* done) {
+    if (!enc.fast104) return fail(HEC_ERR_INVALID_ARGUMENT, "update needs the RS(10,4) encode plan");
+    UpdateArgs v{};
+    if (done) HEC_TRY(done->arm(s, &v.a.done_count, &v.a.done_flag, &v.a.done_seq));
+    fill_args(v.a, enc, b, nullptr);
+    v.a.masks = masks;
+    v.old_base = old.base;
+    v.old_stripe = old.stripe;
+    v.old_shard = old.shard;
+    HEC_HIP(launch_update(v, b.aligned() && (!old.base || old.low_bits() % 16 == 0), s));
+    return HEC_OK;
+}
+
 // Pass 2 of a scrub, the part every kernel argument type shares: pass 1's
 // arguments with its counters nulled (the counts are pass 1's), the words to
 // name the shards in, cleared, and the locate's constants.

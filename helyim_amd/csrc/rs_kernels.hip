@@ -41,6 +41,9 @@
 //    want word per stripe: a compile-time SOME form of the decode bodies picks
 //    the wanted rows of the mask's plan with scalar work, so only those rows
 //    are computed and stored.
+//  * The update (rs104_update_kernel) folds changed data shards into the
+//    stored parity: the encode plan's column tables over old ^ new of the
+//    shards a per-stripe mask names, XORed into the four parity shards.
 //
 // Every kernel here is a product path: rs104_pick / ragged_pick choose among
 // them by shard length, alignment and where the bytes live. Variants measured
@@ -950,6 +953,7 @@ static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
 static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
 static ApplyArgs& apply_args(SomeArgs& v) { return v.a; }
+static ApplyArgs& apply_args(UpdateArgs& v) { return v.a; }
 static ApplyArgs& apply_args(CorrectArgs& c) { return c.a; }
 static ApplyArgs& apply_args(CorrectPresentArgs& c) { return c.a; }
 
@@ -1078,6 +1082,169 @@ hipError_t launch_some(const SomeArgs& v, bool aligned, hipStream_t stream) {
             set_fast_map(w.a, kThreads * kVecBytes, true);
             return launch_items(rs104_some_kernel<uint32_t>, rs104_some_kernel<uint64_t>, w, stream);
     }
+}
+
+// ---------------------------------------------------------------------------
+// Update (hec.h hec_gpu_update_batch): the code is linear, so when the data
+// shards in U change from old to new, parity[j] ^= XOR over c in U of
+// P[j][c] * (old[c] ^ new[c]). Column c of the encode plan's tables
+// ([10 inputs][4 rows][5 words]) is the four-row table of shard c: one gf_mac<4>
+// of the delta per changed shard, no table set of its own. A stripe moves
+// 2|U| + 8 shard lengths (|U| + 8 without old) where the encode moves 14.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kUpdateBits = 0x3FFu;  // data shards 0..9; the other mask bits mean nothing
+
+// old[c] ^ new[c] of this lane's vector (new[c] itself without an old arena).
+template <bool HAS_OLD, typename OffT>
+__device__ __forceinline__ u32x4 update_delta(const uint8_t* new_b, uint64_t new_shard, const uint8_t* old_b,
+                                              uint64_t old_shard, uint32_t c, OffT o) {
+    u32x4 d = load_at(new_b + uint64_t(c) * new_shard, o);
+    if constexpr (HAS_OLD) d ^= load_at(old_b + uint64_t(c) * old_shard, o);
+    return d;
+}
+
+// One lane's vector of one (stripe, column range) item, one changed shard at a
+// time, the pointers already at the lane's offset: FULL, 16 bytes with
+// alignment-free access (the generic kernel); else the `avail` (< 16) bytes
+// left of the shard, byte-wise (both kernels' lane that crosses len).
+template <bool HAS_OLD, bool FULL>
+__device__ __forceinline__ void update_lane(const UpdateArgs& v, uint32_t u, const uint8_t* new_b, const uint8_t* old_b,
+                                            uint8_t* par_b, cu32p tab, uint64_t avail) {
+    constexpr int R = 4;
+    const ApplyArgs& a = v.a;
+    u32x4 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = u32x4{0, 0, 0, 0};
+    for (; u; u &= u - 1) {
+        const uint32_t c = __builtin_ctz(u);
+        const uint8_t* pn = new_b + uint64_t(c) * a.in_shard;
+        u32x4 d = FULL ? load_full(pn, false) : load_tail(pn, avail);
+        if constexpr (HAS_OLD) {
+            const uint8_t* po = old_b + uint64_t(c) * v.old_shard;
+            d ^= FULL ? load_full(po, false) : load_tail(po, avail);
+        }
+        gf_mac<R>(acc, d, tab + c * (R * 5));
+    }
+    for (int r = 0; r < R; ++r) {
+        uint8_t* row = par_b + uint64_t(r) * a.out_shard;
+        if constexpr (FULL)
+            store_full(row, acc[r] ^ load_full(row, false), false);
+        else
+            store_tail(row, acc[r] ^ load_tail(row, avail), avail);
+    }
+}
+
+// One workgroup per (stripe, 4 KiB column range), 16 bytes per lane. The mask
+// is one scalar load; an empty U leaves before any vector load. Otherwise the
+// four parity loads go first, then the changed shards two at a time (scalar
+// bit scan): their loads, a fence, the table multiply. With one or two
+// changed shards that is every load in flight before any math, as the decode.
+template <bool HAS_OLD, typename OffT>
+__global__ __launch_bounds__(kThreads) void rs104_update_kernel(UpdateArgs v) {
+    constexpr int R = 4;
+    const ApplyArgs& a = v.a;
+    uint32_t stripe, chunk;
+    fast_item(a, a.chunks_per_stripe, stripe, chunk);
+    uint32_t u = as_const(a.masks)[stripe] & kUpdateBits;
+    const OffT o = OffT(chunk) * OffT(kThreads * kVecBytes) + OffT(threadIdx.x * kVecBytes);
+    if (u != 0 && o < a.len) {
+        const uint64_t avail = a.len - o;
+        const uint8_t* new_b = a.in_base + uint64_t(stripe) * a.in_stripe;
+        const uint8_t* old_b = HAS_OLD ? v.old_base + uint64_t(stripe) * v.old_stripe : nullptr;
+        uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe;
+        cu32p tab = as_const(a.tabs);
+        u32x4 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = u32x4{0, 0, 0, 0};
+        if (avail >= kVecBytes) {
+            u32x4 p[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) p[r] = load_at(par_b + uint64_t(r) * a.out_shard, o);
+            while (u) {
+                const uint32_t c0 = __builtin_ctz(u);
+                u &= u - 1;
+                const u32x4 d0 = update_delta<HAS_OLD>(new_b, a.in_shard, old_b, v.old_shard, c0, o);
+                if (u) {
+                    const uint32_t c1 = __builtin_ctz(u);
+                    u &= u - 1;
+                    const u32x4 d1 = update_delta<HAS_OLD>(new_b, a.in_shard, old_b, v.old_shard, c1, o);
+                    __builtin_amdgcn_sched_barrier(0);
+                    gf_mac2<R>(acc, d0, d1, tab + c0 * (R * 5), tab + c1 * (R * 5));
+                } else {
+                    __builtin_amdgcn_sched_barrier(0);
+                    gf_mac<R>(acc, d0, tab + c0 * (R * 5));
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) store_at(par_b + uint64_t(r) * a.out_shard, o, acc[r] ^ p[r]);
+        } else {  // the lane that crosses len, in the stripe's last column range
+            update_lane<HAS_OLD, false>(v, u, new_b + o, HAS_OLD ? old_b + o : nullptr, par_b + o, tab, avail);
+        }
+    }
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+// The update on every other layout (unaligned bases or strides, a stripe whose
+// column ranges pass one launch): grid-stride over (stripe, 4 KiB column
+// range) items with alignment-free access, one changed shard at a time.
+template <bool HAS_OLD>
+__global__ __launch_bounds__(kThreads) void rs104_update_stride_kernel(UpdateArgs v) {
+    const ApplyArgs& a = v.a;
+    cu32p tab = as_const(a.tabs);
+    for (uint64_t item = stride_first_item(); item < a.n_items; item += gridDim.x) {
+        const uint32_t stripe = uint32_t(item / a.chunks_per_stripe);
+        const uint32_t chunk = uint32_t(item - uint64_t(stripe) * a.chunks_per_stripe);
+        const uint32_t u = as_const(a.masks)[stripe] & kUpdateBits;
+        if (u == 0) continue;
+        const uint64_t o = uint64_t(chunk) * (kThreads * kVecBytes) + threadIdx.x * kVecBytes;
+        if (o >= a.len) continue;
+        const uint64_t avail = a.len - o;
+        const uint8_t* new_b = a.in_base + uint64_t(stripe) * a.in_stripe + o;
+        const uint8_t* old_b = HAS_OLD ? v.old_base + uint64_t(stripe) * v.old_stripe + o : nullptr;
+        uint8_t* par_b = a.out_base + uint64_t(stripe) * a.out_stripe + o;
+        if (avail >= kVecBytes)
+            update_lane<HAS_OLD, true>(v, u, new_b, old_b, par_b, tab, avail);
+        else
+            update_lane<HAS_OLD, false>(v, u, new_b, old_b, par_b, tab, avail);
+    }
+    if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
+}
+
+static UpdateArgs stripe_range(UpdateArgs v, Range r) {
+    v.a = stripe_range(v.a, r);  // the new arena, the parity arena and the mask words
+    if (v.old_base) v.old_base += uint64_t(r.first) * v.old_stripe;
+    return v;
+}
+
+// An aligned update runs one workgroup per 4 KiB column range when one
+// stripe's ranges fit a launch.
+static bool update_per_item(uint64_t len) { return (len + 4095) / 4096 <= kMaxLaunchBlocks; }
+
+const char* update_kernel_name(uint64_t len) {
+    if (len == 0) return kNoLaunch;
+    return update_per_item(len) ? "rs104_update_kernel (table lookup)" : "rs104_update_stride_kernel (table lookup)";
+}
+
+hipError_t launch_update(const UpdateArgs& v, bool aligned, hipStream_t stream) {
+    const ApplyArgs& a = v.a;
+    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
+    const bool has_old = v.old_base != nullptr;
+    if (aligned && update_per_item(a.len)) {
+        // one column range per workgroup and no grid-stride loop: batches past
+        // one launch's workgroup limit go in stripe ranges, as launch_apply's
+        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, (a.len + 4095) / 4096);
+        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
+            UpdateArgs w = stripe_range(v, range_at(a.n_stripes, step, i));
+            set_fast_map(w.a, kThreads * kVecBytes, true);
+            hipError_t e = has_old ? launch_items(rs104_update_kernel<true, uint32_t>,
+                                                  rs104_update_kernel<true, uint64_t>, w, stream)
+                                   : launch_items(rs104_update_kernel<false, uint32_t>,
+                                                  rs104_update_kernel<false, uint64_t>, w, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    return launch_stride(has_old ? rs104_update_stride_kernel<true> : rs104_update_stride_kernel<false>, v, stream);
 }
 
 // ---------------------------------------------------------------------------

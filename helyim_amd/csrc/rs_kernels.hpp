@@ -153,6 +153,26 @@ hipError_t launch_some(const SomeArgs& v, bool aligned, hipStream_t stream);
 const char* some_kernel_name(uint64_t len);
 const char* some_batch_kernel_name(uint64_t len, uint64_t n_stripes, bool aligned);
 
+// Update (hec.h hec_gpu_update_batch) of a strided RS(10,4) batch: for every
+// stripe, parity ^= P[:,U] * (old[U] ^ new[U]), U = the data shards its mask
+// word names (bits 0..9; the others mean nothing). a: in_* = the NEW data
+// arena and out_* = the parity arena (read and written), both indexed from
+// their own base (data shard c at in_base + s*in_stripe + c*in_shard, parity
+// shard j at out_base + s*out_stripe + j*out_shard), masks = the update masks
+// (device words), tabs = the RS(10,4) ENCODE plan's tables: column c's
+// four-row table is tabs + c * 20 words. The old arena is indexed as the new
+// one; old_base == nullptr: old is zero. A stripe with U empty is neither read
+// nor written; no byte outside [0, len) of a parity shard is written.
+struct UpdateArgs {
+    ApplyArgs a;
+    const uint8_t* old_base = nullptr;
+    uint64_t old_stripe = 0, old_shard = 0;
+};
+// aligned: every base and stride of the three arenas 16-byte aligned.
+hipError_t launch_update(const UpdateArgs& v, bool aligned, hipStream_t stream);
+// Name of the kernel an aligned update of one stripe of this shard length runs.
+const char* update_kernel_name(uint64_t len);
+
 // Parity verify (scrub) of a strided batch: the encode plan's parity is
 // recomputed in registers and compared with the stored parity; nothing but
 // the result words is written. a: the encode's arguments with out_* naming

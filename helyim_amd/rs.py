@@ -89,6 +89,23 @@ class ReedSolomon:
         check(lib.hec_rs_verify(self._h, _ptr_array(arrs), _len_array(arrs), len(arrs), ctypes.byref(ok)))
         return bool(ok.value)
 
+    def update(self, shards: Sequence[Optional[object]], new_data: Sequence[Optional[object]]) -> None:
+        """Fold changed data shards into the parity in place, without
+        re-encoding (hec_rs_update, klauspost's Update). ``shards``: total
+        entries; the data entries are the OLD shards, needed only where
+        ``new_data`` has an entry (the others may be None); the parity entries
+        are updated. ``new_data``: data_shard_count entries, the new bytes of
+        each changed shard, None = unchanged. Neither old nor new data is
+        written, and new is not copied over old."""
+        olds = [None if s is None else _as_u8(s) for s in shards]
+        news = [None if s is None else _as_u8(s) for s in new_data]
+        if len(news) != self._k:
+            raise ValueError(f"{len(news)} new_data entries for {self._k} data shards")
+        for i, w in enumerate(news):
+            if w is not None and i < len(olds) and olds[i] is not None and olds[i].size != w.size:
+                raise ValueError(f"new_data[{i}] has {w.size} bytes, the old shard {olds[i].size}")
+        check(lib.hec_rs_update(self._h, _ptr_array(olds), _len_array(olds), _ptr_array(news), len(olds)))
+
     def reconstruct(self, shards: MutableSequence[Optional[object]]) -> None:
         self._reconstruct(shards, data_only=False)
 

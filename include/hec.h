@@ -199,6 +199,22 @@ int hec_rs_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* const* shards, co
                                   const uint8_t* present, const uint8_t* required, size_t n_stripes,
                                   size_t* bad_index);
 
+/* Update (klauspost's Update): fold changed data shards into the parity
+ * without re-encoding. shards: total pointers; shards[i] for i < data is the
+ * OLD data shard i, needed only where new_data[i] is non-NULL (the other data
+ * slots and their lengths are ignored and may be NULL); shards[data..total)
+ * are the parity shards, all required, updated in place: parity[j] ^= sum over
+ * the changed c of P[j][c] * (old[c] ^ new[c]). new_data: data pointers, the
+ * new bytes of each changed shard (shard_lens[c] bytes), NULL = unchanged; no
+ * non-NULL entry: HEC_OK, nothing touched. Neither old nor new shards are
+ * written, and the call does not copy new over old. Errors, in this order:
+ * null rs / arrays (HEC_ERR_INVALID_ARGUMENT), TOO_FEW_SHARDS /
+ * TOO_MANY_SHARDS (n_shards != total), a changed shard without an old buffer
+ * or a NULL parity pointer (HEC_ERR_INVALID_ARGUMENT), then EMPTY_SHARD and
+ * INCORRECT_SHARD_SIZE over the lengths in use. Any codec. */
+int hec_rs_update(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
+                  const uint8_t* const* new_data, size_t n_shards);
+
 /* ---- device-resident batches (no reference counterpart: the GPU form of the
  * encode_data_one_batch loop, encoder.rs:158-198, over many stripes) -------
  * Shard (stripe s, shard i) lives at base + s*stripe_stride + i*shard_stride.
@@ -265,6 +281,57 @@ int hec_gpu_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* d_shards, uint64
                                    uint64_t shard_stride, uint64_t shard_len, uint32_t n_stripes,
                                    const uint32_t* d_present_masks, const uint32_t* d_want_masks,
                                    uint32_t* d_bad_stripes, void* stream);
+
+/* Update: fold changed data shards into the stored parity without re-encoding
+ * the stripe (klauspost's Update, ISA-L's ec_encode_data_update). RS(10,4).
+ * d_update_masks (device, n_stripes words): bit c set = data shard c of that
+ * stripe changed, c in 0..9; bits 10..31 mean nothing. Per stripe, with U the
+ * set bits:
+ *     parity[j] ^= XOR over c in U of P[j][c] * (old[c] ^ new[c]),  j = 0..3
+ * (P = the parity rows of hec_rs_matrix). Data shard c of stripe s is at
+ * d_old + s*old_stripe_stride + c*old_shard_stride, and likewise for d_new:
+ * both are indexed by shard id 0..9, so an in-place [S][14][pitch] batch
+ * passes its own base as d_old and base + 10*shard_stride as d_parity.
+ *  - only the shards in U are read, of d_old and d_new alike;
+ *  - d_old == NULL means old is zero: the parity accumulates P[:,U] * new[U]
+ *    (klauspost's EncodeIdx). Over zeroed parity, any partition of 0..9 into
+ *    calls gives hec_gpu_encode_batch's bytes, so a caller that receives a
+ *    stripe's shards one after another never needs to hold all ten;
+ *  - U empty: the stripe is not read and not written;
+ *  - the call writes bytes [0, shard_len) of the four parity shards of the
+ *    stripes with U non-empty and no other byte; d_old and d_new are never
+ *    written. It does NOT copy new over old ("commit"): the caller swaps
+ *    buffers or copies;
+ *  - d_parity must overlap neither d_old nor d_new (not checked).
+ * Layouts, strides and lengths as hec_gpu_encode_batch (any shard_len >= 1;
+ * bases or strides that are not 16-byte aligned take a generic kernel).
+ * Asynchronous on `stream`, no host synchronisation beyond the first plan
+ * upload on a device, nothing allocated. Errors, all before device work and in
+ * this order: a null rs, d_new, d_parity or d_update_masks, also with
+ * n_stripes == 0 (HEC_ERR_INVALID_ARGUMENT); shard_len == 0
+ * (HEC_ERR_EMPTY_SHARD); any codec but RS(10,4) (HEC_ERR_INVALID_ARGUMENT,
+ * detail "RS(10,4) only"); overlapping shards or stripes, or an extent that
+ * wraps 64 bits, in any of the three arenas, the old one only when given
+ * (HEC_ERR_INVALID_ARGUMENT). With valid pointers n_stripes == 0 returns
+ * HEC_OK and writes nothing.
+ * Cost: a stripe moves 2|U| + 8 shard lengths (old and new of U read, four
+ * parity shards read and four written), |U| + 8 without d_old, where
+ * hec_gpu_encode_batch moves 14: one changed shard is 10 against 14. With
+ * d_old, from |U| = 3 on a re-encode moves no more bytes.
+ * Measured on one MI355X, 4096 x 1 MiB stripes with the 64 KiB shard pad,
+ * medians (min..max) of 9 alternating rounds (tools/bench_update.py,
+ * profiles/update/bench_update.json): hec_gpu_encode_batch 9.61 ms
+ * (9.60..9.75); with d_old, |U| = 1: 6.82 ms (6.82..6.89), 0.710 of the
+ * encode where the bytes say 10/14 = 0.714; |U| = 2: 8.26 ms (8.26..8.28);
+ * |U| = 3: 9.74 ms (9.71..9.76), 1.013 of the encode at the same 14 shard
+ * lengths. Without d_old, |U| = 1: 6.11 ms (6.10..6.13); |U| = 5: 8.91 ms
+ * (8.89..8.91); |U| = 10: 12.33 ms (12.30..12.34) for 18 shard lengths. Every
+ * leg moves 6.18 to 6.33 TB/s: the time follows the bytes. */
+int hec_gpu_update_batch(const hec_rs_t* rs,
+                         const uint8_t* d_old, uint64_t old_stripe_stride, uint64_t old_shard_stride,
+                         const uint8_t* d_new, uint64_t new_stripe_stride, uint64_t new_shard_stride,
+                         uint8_t* d_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                         uint64_t shard_len, uint32_t n_stripes, const uint32_t* d_update_masks, void* stream);
 
 /* Verify (scrub) n_stripes stripes: the batched, on-device form of
  * ReedSolomon::verify. Reads the data shards from d_data and the STORED parity
@@ -745,6 +812,27 @@ int hec_host_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* h_shards, uint6
                                     const uint32_t* h_present_masks, const uint32_t* h_want_masks,
                                     uint32_t* n_bad_stripes);
 
+/* hec_gpu_update_batch on host memory, in delta form: h_delta shard c (indexed
+ * by shard id 0..9 as d_new) holds old ^ new of data shard c, or the new shard
+ * itself when the parity has not seen that shard yet; h_update_masks: host,
+ * n_stripes words. parity[j] ^= XOR over c in U of P[j][c] * delta[c]. The
+ * host call takes a delta and not old plus new because this path is bound by
+ * PCIe: one shard crossing the link per changed shard instead of two is worth
+ * a CPU XOR, and |U| + 8 shard lengths cross where a host encode moves 14 (9
+ * against 14 for one changed shard; the untouched shards need not be in
+ * memory). Over the three paths of hec_host_encode_batch: pinned memory in
+ * place, pageable memory through the pinned slots, H2D / D2H copies with zero
+ * copy off; they give identical parity. Of a stripe only the deltas of U and
+ * the parity are read, only bytes [0, shard_len) of its parity shards are
+ * written, and a stripe with U empty moves nothing either way. h_delta is
+ * never written. RS(10,4) only. Argument errors as the device call's, in its
+ * order. Synchronous: nothing queued is in flight on return, error returns
+ * included. */
+int hec_host_update_batch(const hec_rs_t* rs,
+                          const uint8_t* h_delta, uint64_t delta_stripe_stride, uint64_t delta_shard_stride,
+                          uint8_t* h_parity, uint64_t parity_stripe_stride, uint64_t parity_shard_stride,
+                          uint64_t shard_len, uint32_t n_stripes, const uint32_t* h_update_masks);
+
 /* Ragged device batches (RS(10,4)): every stripe has its own length, shard
  * stride and erasure pattern -- BASELINE config 5's mixed 64 KiB-4 MiB
  * stripes in ONE launch. Stripe j's shard i is at d_base + offset + i *
@@ -1185,6 +1273,8 @@ const char* hec_reconstruct_some_kernel_name(uint64_t shard_len);
 const char* hec_reconstruct_some_batch_kernel_name(const uint8_t* d_shards, uint64_t stripe_stride,
                                                    uint64_t shard_stride, uint64_t shard_len,
                                                    uint32_t n_stripes);
+/* Same for a 16-byte-aligned hec_gpu_update_batch of one stripe. */
+const char* hec_update_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned RS(10,4) device batch verify. */
 const char* hec_verify_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned hec_gpu_verify_present_batch (masked verify). */

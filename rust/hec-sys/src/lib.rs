@@ -139,8 +139,19 @@ extern "C" {
     pub fn hec_rs_reconstruct_some_batch(rs: *const hec_rs_t, shards: *const *mut u8, lens: *const usize,
                                          present: *const u8, required: *const u8, n_stripes: usize,
                                          bad_index: *mut usize) -> c_int;
+    pub fn hec_rs_update(rs: *const hec_rs_t, shards: *const *mut u8, shard_lens: *const usize,
+                         new_data: *const *const u8, n_shards: usize) -> c_int;
 
     // device-resident and host-memory stripe batches
+    pub fn hec_gpu_update_batch(rs: *const hec_rs_t, d_old: *const u8, old_stripe_stride: u64,
+                                old_shard_stride: u64, d_new: *const u8, new_stripe_stride: u64,
+                                new_shard_stride: u64, d_parity: *mut u8, parity_stripe_stride: u64,
+                                parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                d_update_masks: *const u32, stream: *mut c_void) -> c_int;
+    pub fn hec_host_update_batch(rs: *const hec_rs_t, h_delta: *const u8, delta_stripe_stride: u64,
+                                 delta_shard_stride: u64, h_parity: *mut u8, parity_stripe_stride: u64,
+                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
+                                 h_update_masks: *const u32) -> c_int;
     pub fn hec_gpu_encode_batch(rs: *const hec_rs_t, d_data: *const u8, data_stripe_stride: u64,
                                 data_shard_stride: u64, d_parity: *mut u8, parity_stripe_stride: u64,
                                 parity_shard_stride: u64, shard_len: u64, n_stripes: u32,
@@ -333,6 +344,7 @@ extern "C" {
     pub fn hec_encode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_decode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_reconstruct_some_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_update_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_reconstruct_some_batch_kernel_name(d_shards: *const u8, stripe_stride: u64, shard_stride: u64,
                                                   shard_len: u64, n_stripes: u32) -> *const c_char;
     pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;
