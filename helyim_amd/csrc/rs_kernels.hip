@@ -895,20 +895,56 @@ hipError_t launch_rs104_ragged_some(const RaggedArgs& a, hipStream_t stream) {
     return launch_ragged(a.compact ? rs104_ragged_some_kernel<true> : rs104_ragged_some_kernel<false>, a, stream);
 }
 
+// ---------------------------------------------------------------------------
+// The launch layer of the strided batches. Two shapes of kernel:
+//  * one workgroup per chunk behind fast_item (a FastKind): no loop in the
+//    kernel, so a batch of more chunks than one launch takes goes in ranges
+//    of whole stripes (launch_stripe_ranges);
+//  * a grid-stride loop over (stripe, 4 KiB chunk) items (launch_stride): one
+//    launch whatever the batch.
+// The name functions ask the predicates and picks the launchers ask, so a
+// reported name is the kernel that runs.
+// ---------------------------------------------------------------------------
+// How the workgroups of one kind of kernel cut a shard into column ranges.
+struct ChunkGeom {
+    uint32_t bytes;  // column range of one workgroup
+    bool round_up;   // a partial last range is a workgroup too; else the kind takes whole multiples only
+    constexpr uint64_t chunks(uint64_t len) const { return round_up ? (len + bytes - 1) / bytes : len / bytes; }
+    constexpr bool takes(uint64_t len) const { return round_up || len % bytes == 0; }
+};
+constexpr ChunkGeom kBsGeom{kBsChunk, false};                // bit-sliced: 8 KiB
+constexpr ChunkGeom kNarrowGeom{kNarrowChunk, false};        // 8 bytes per lane: 2 KiB
+constexpr ChunkGeom kTableGeom{kThreads * kVecBytes, true};  // 16 bytes per lane: 4 KiB, any length
+
+// Every byte offset inside a shard fits 32 bits.
+static bool off32(uint64_t len) { return len <= 0xFFFFFFFFull; }
+
+// One kind of kernel behind fast_item: its geometry and its two offset widths.
+template <typename Args>
+struct FastKind {
+    ChunkGeom geom;
+    void (*k32)(Args);  // shards below 4 GiB
+    void (*k64)(Args);  // shards of 4 GiB and more; k32 again where the kind has no such form
+    // The kind runs batches of this shard length: a length it takes, one
+    // stripe's chunks within a launch (its stripe ranges hold whole stripes),
+    // and a kernel for the offsets.
+    bool serves(uint64_t len) const {
+        return geom.takes(len) && geom.chunks(len) <= kMaxLaunchBlocks && (off32(len) || k64 != k32);
+    }
+};
+
 // The kernel an aligned RS(10,4) batch with the fast plan layout runs, shared
-// by launch_apply and the name functions so a reported name is the kernel
-// that runs.
+// by launch_apply and the name functions.
 enum class Rs104Kind { Apply, Bitslice, Narrow, Table };
 static Rs104Kind rs104_pick(uint64_t len, uint64_t n_stripes, bool dec, bool over_pcie) {
     // launch_apply sizes its stripe ranges for 4 KiB chunks; a batch whose
     // chunks would pass one launch's workgroup limit takes the generic kernel
-    const uint64_t items = (len + 4095) / 4096 * n_stripes;
-    if (items > kMaxLaunchBlocks) return Rs104Kind::Apply;
-    const bool off32 = len <= 0xFFFFFFFFull;
-    if (!dec && !over_pcie && len % kBsChunk == 0) return Rs104Kind::Bitslice;
+    if (kTableGeom.chunks(len) * n_stripes > kMaxLaunchBlocks) return Rs104Kind::Apply;
+    if (!dec && !over_pcie && kBsGeom.takes(len)) return Rs104Kind::Bitslice;
     // the decode, and the encode over PCIe: 8 bytes per lane where the shard
     // length is a multiple of 2 KiB
-    if ((dec || over_pcie) && off32 && len % kNarrowChunk == 0 && (len / kNarrowChunk) * n_stripes <= kMaxLaunchBlocks)
+    if ((dec || over_pcie) && off32(len) && kNarrowGeom.takes(len) &&
+        kNarrowGeom.chunks(len) * n_stripes <= kMaxLaunchBlocks)
         return Rs104Kind::Narrow;
     return Rs104Kind::Table;
 }
@@ -936,70 +972,57 @@ const char* encode_kernel_name(uint64_t len, bool over_pcie) {
     return rs104_name(rs104_pick(len, 1, false, over_pcie), false);
 }
 
-// Launch constants of fast_item: the XCD eighths of the grid and the chunks
-// per stripe as a multiply-shift divisor.
-static void set_fast_map(ApplyArgs& a, uint32_t chunk_bytes, bool round_up) {
-    a.chunks_per_stripe = uint32_t(round_up ? (a.len + chunk_bytes - 1) / chunk_bytes : a.len / chunk_bytes);
+// The coding arguments of either kernel argument struct (CorrectArgs and
+// CorrectPresentArgs through their bases).
+static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
+static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
+static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
+static ApplyArgs& apply_args(SomeArgs& v) { return v.a; }
+static ApplyArgs& apply_args(UpdateArgs& v) { return v.a; }
+
+// One workgroup per chunk of the batch through a kind's kernel, with
+// fast_item's launch constants: the XCD eighths of the grid and the chunks per
+// stripe as a multiply-shift divisor.
+template <typename Args>
+static hipError_t launch_fast(const FastKind<Args>& k, Args v, hipStream_t stream) {
+    ApplyArgs& a = apply_args(v);
+    a.chunks_per_stripe = uint32_t(k.geom.chunks(a.len));
     a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
     a.map_q8 = uint32_t(a.n_items / 8);
     a.map_r8 = uint32_t(a.n_items % 8);
     const FastDiv f = make_fastdiv(a.chunks_per_stripe ? a.chunks_per_stripe : 1);
     a.cps_mul = f.mul;
     a.cps_shift = f.shift;
-}
-
-// The coding arguments of either kernel argument struct.
-static ApplyArgs& apply_args(ApplyArgs& a) { return a; }
-static ApplyArgs& apply_args(VerifyArgs& v) { return v.a; }
-static ApplyArgs& apply_args(CheckArgs& v) { return v.a; }
-static ApplyArgs& apply_args(SomeArgs& v) { return v.a; }
-static ApplyArgs& apply_args(UpdateArgs& v) { return v.a; }
-static ApplyArgs& apply_args(CorrectArgs& c) { return c.a; }
-static ApplyArgs& apply_args(CorrectPresentArgs& c) { return c.a; }
-
-// A fast-mapped batch (set_fast_map), one workgroup per item: k32 where every
-// byte offset inside a shard fits 32 bits, k64 for shards of 4 GiB and more.
-template <typename Args>
-static hipError_t launch_items(void (*k32)(Args), void (*k64)(Args), Args v, hipStream_t stream) {
-    const ApplyArgs& a = apply_args(v);
     if (a.n_items == 0) return hipSuccess;
-    hipLaunchKernelGGL(a.len <= 0xFFFFFFFFull ? k32 : k64, dim3(uint32_t(a.n_items)), dim3(kThreads), 0, stream, v);
+    hipLaunchKernelGGL(off32(a.len) ? k.k32 : k.k64, dim3(uint32_t(a.n_items)), dim3(kThreads), 0, stream, v);
     return hipGetLastError();
 }
 
-template <bool DEC>
-static hipError_t launch_rs104(ApplyArgs a, Rs104Kind kind, hipStream_t stream) {
-    switch (kind) {
-        case Rs104Kind::Bitslice:
-            set_fast_map(a, kBsChunk, false);
-            return launch_items(rs104_bs_encode_kernel<uint32_t>, rs104_bs_encode_kernel<uint64_t>, a, stream);
-        case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
-            set_fast_map(a, kNarrowChunk, false);
-            return launch_items(rs104_narrow_kernel<DEC>, rs104_narrow_kernel<DEC>, a, stream);
-        default:
-            set_fast_map(a, kThreads * kVecBytes, true);
-            return launch_items(rs104_kernel<DEC, uint32_t>, rs104_kernel<DEC, uint64_t>, a, stream);
-    }
-}
-
-// A grid-stride kernel (rs_apply_kernel / rs_verify_kernel / rs104_locate_kernel)
-// over the batch's (stripe, 4 KiB chunk) items, on at most max_grid workgroups.
+// A grid-stride kernel over n_items items on at most max_grid workgroups; an
+// empty batch launches nothing.
 template <typename Args>
-static hipError_t launch_stride(void (*kern)(Args), Args v, hipStream_t stream,
-                                uint64_t max_grid = kMaxLaunchBlocks) {
-    ApplyArgs& a = apply_args(v);
-    const uint64_t chunk = uint64_t(kThreads) * kVecBytes;
-    a.chunks_per_stripe = uint32_t((a.len + chunk - 1) / chunk);
-    a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
-    if (a.n_items == 0) return hipSuccess;
-    const uint64_t grid = std::min<uint64_t>(a.n_items, max_grid);  // grid-stride covers the rest
+static hipError_t launch_grid_stride(void (*kern)(Args), const Args& v, uint64_t n_items, uint64_t max_grid,
+                                     hipStream_t stream) {
+    if (n_items == 0) return hipSuccess;
+    const uint64_t grid = std::min<uint64_t>(n_items, max_grid);  // grid-stride covers the rest
     hipLaunchKernelGGL(kern, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, v);
     return hipGetLastError();
 }
 
-// The arguments of one stripe range of a batch (launch_split.hpp): bases and
-// masks advanced to its first stripe. The launches share a stream, so only the
-// last range signals completion.
+// A strided grid-stride kernel (rs_apply_kernel / rs_verify_kernel /
+// rs104_locate_kernel, ...) over the batch's (stripe, 4 KiB chunk) items.
+template <typename Args>
+static hipError_t launch_stride(void (*kern)(Args), Args v, hipStream_t stream,
+                                uint64_t max_grid = kMaxLaunchBlocks) {
+    ApplyArgs& a = apply_args(v);
+    a.chunks_per_stripe = uint32_t(kTableGeom.chunks(a.len));
+    a.n_items = uint64_t(a.chunks_per_stripe) * a.n_stripes;
+    return launch_grid_stride(kern, v, a.n_items, max_grid, stream);
+}
+
+// The arguments of one stripe range of a batch (launch_split.hpp): bases,
+// masks and each struct's own per-stripe words advanced to its first stripe.
+// The launches share a stream, so only the last range signals completion.
 static ApplyArgs stripe_range(ApplyArgs a, Range r) {
     a.in_base += uint64_t(r.first) * a.in_stripe;
     a.out_base += uint64_t(r.first) * a.out_stripe;
@@ -1013,27 +1036,86 @@ static SomeArgs stripe_range(SomeArgs v, Range r) {
     v.wants += r.first;
     return v;
 }
+static UpdateArgs stripe_range(UpdateArgs v, Range r) {
+    v.a = stripe_range(v.a, r);  // the new arena, the parity arena and the mask words
+    if (v.old_base) v.old_base += uint64_t(r.first) * v.old_stripe;
+    return v;
+}
+static VerifyArgs stripe_range(VerifyArgs v, Range r) {
+    v.a = stripe_range(v.a, r);
+    v.mismatch += r.first;
+    return v;
+}
+static CheckArgs stripe_range(CheckArgs v, Range r) {
+    v.a = stripe_range(v.a, r);
+    v.check += r.first;
+    return v;
+}
+
+// Stripes per range of a batch whose kernel runs per_stripe workgroups per
+// stripe and has no grid-stride loop. The whole batch where it fits one
+// launch, and where no range of whole stripes would: one stripe, or a stripe
+// of more chunks than a launch takes (the callers' picks and predicates send
+// those to a grid-stride kernel).
+static uint64_t stripes_per_range(uint64_t n_stripes, uint64_t per_stripe) {
+    if (per_stripe * n_stripes <= kMaxLaunchBlocks || n_stripes == 1 || per_stripe > kMaxLaunchBlocks) return n_stripes;
+    return stripes_per_launch(kMaxLaunchBlocks, per_stripe);
+}
+
+// The batch in stripe ranges sized by per_stripe, each through launch_range
+// (which takes the range's arguments).
+template <typename Args, typename LaunchRange>
+static hipError_t launch_stripe_ranges(Args v, uint64_t per_stripe, LaunchRange launch_range) {
+    const uint64_t n_stripes = apply_args(v).n_stripes, step = stripes_per_range(n_stripes, per_stripe);
+    for (uint64_t i = 0, n = n_ranges(n_stripes, step); i < n; ++i) {
+        hipError_t e = launch_range(stripe_range(v, range_at(n_stripes, step, i)));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The batch through one kind's kernel, in stripe ranges of the kind's own chunks.
+template <typename Args>
+static hipError_t launch_fast_ranges(const FastKind<Args>& k, Args v, hipStream_t stream) {
+    return launch_stripe_ranges(v, k.geom.chunks(apply_args(v).len),
+                                [&](const Args& r) { return launch_fast(k, r, stream); });
+}
+
+template <bool DEC>
+static FastKind<ApplyArgs> rs104_fast(Rs104Kind kind) {
+    switch (kind) {
+        case Rs104Kind::Bitslice:
+            return {kBsGeom, rs104_bs_encode_kernel<uint32_t>, rs104_bs_encode_kernel<uint64_t>};
+        case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
+            return {kNarrowGeom, rs104_narrow_kernel<DEC>, rs104_narrow_kernel<DEC>};
+        default: return {kTableGeom, rs104_kernel<DEC, uint32_t>, rs104_kernel<DEC, uint64_t>};
+    }
+}
 
 hipError_t launch_apply(const ApplyArgs& a, int nin, bool aligned, bool over_pcie, hipStream_t stream) {
+    const auto launch_range = [&](const ApplyArgs& r) {
+        const bool dec = r.masks != nullptr;
+        const Rs104Kind kind = rs104_pick(r.len, r.n_stripes, dec, over_pcie && !dec);
+        if (r.fast104 && aligned && kind != Rs104Kind::Apply)
+            return launch_fast(dec ? rs104_fast<true>(kind) : rs104_fast<false>(kind), r, stream);
+        return launch_stride(nin == 10 ? (aligned ? rs_apply_kernel<10, true> : rs_apply_kernel<10, false>)
+                                       : (aligned ? rs_apply_kernel<0, true> : rs_apply_kernel<0, false>),
+                             r, stream);
+    };
+    if (!a.fast104) return launch_range(a);  // any codec: the grid-stride kernel
     // RS(10,4) fast path: fixed 4-row table stride, one chunk of >= 2 KiB per
     // workgroup and no grid-stride loop, so one launch takes at most
     // kMaxLaunchBlocks chunks: larger batches (tens of millions of short
-    // stripes) go in stripe ranges.
-    const uint64_t per_stripe = (a.len + 4095) / 4096;
-    const uint64_t items = per_stripe * a.n_stripes;
-    if (a.fast104 && items > kMaxLaunchBlocks && a.n_stripes > 1 && per_stripe <= kMaxLaunchBlocks) {
-        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
-        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
-            hipError_t e = launch_apply(stripe_range(a, range_at(a.n_stripes, step, i)), nin, aligned, over_pcie, stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    const Rs104Kind kind = rs104_pick(a.len, a.n_stripes, a.masks != nullptr, over_pcie && !a.masks);
-    if (a.fast104 && aligned && kind != Rs104Kind::Apply)
-        return a.masks ? launch_rs104<true>(a, kind, stream) : launch_rs104<false>(a, kind, stream);
-    if (nin == 10) return launch_stride(aligned ? rs_apply_kernel<10, true> : rs_apply_kernel<10, false>, a, stream);
-    return launch_stride(aligned ? rs_apply_kernel<0, true> : rs_apply_kernel<0, false>, a, stream);
+    // stripes) go in stripe ranges. Two rules of these ranges, pinned by
+    // tests/test_launch_record.py:
+    //  * they are sized in 4 KiB chunks whatever the chunk of the kernel that
+    //    runs, so the 8 KiB bit-sliced encode fills half a launch per range
+    //    and the 2 KiB kernels are picked only where twice the chunks fit;
+    //  * the kernel is picked per range, so a short last range can run
+    //    another kernel than the ranges before it (4 KiB shards: rs104_kernel
+    //    on the full ranges, rs104_narrow_kernel on a last one of half a
+    //    launch's stripes or fewer).
+    return launch_stripe_ranges(a, kTableGeom.chunks(a.len), launch_range);
 }
 
 // Reconstruct some over a strided in-place batch: launch_apply's decode, its
@@ -1046,42 +1128,32 @@ static const char* some_name(Rs104Kind k) {
     }
 }
 
+// The kernel of one stripe range of launch_some.
+static Rs104Kind some_pick(uint64_t len, uint64_t n_stripes, bool aligned) {
+    return aligned ? rs104_pick(len, n_stripes, true, false) : Rs104Kind::Apply;
+}
+
 const char* some_kernel_name(uint64_t len) {
     if (len == 0) return kNoLaunch;
-    return some_name(rs104_pick(len, 1, true, false));
+    return some_name(some_pick(len, 1, true));
 }
 const char* some_batch_kernel_name(uint64_t len, uint64_t n_stripes, bool aligned) {
     if (len == 0 || n_stripes == 0) return kNoLaunch;
-    if (!aligned) return some_name(Rs104Kind::Apply);
-    const uint64_t per_stripe = (len + 4095) / 4096;  // launch_some's stripe ranges
-    if (per_stripe * n_stripes > kMaxLaunchBlocks && n_stripes > 1 && per_stripe <= kMaxLaunchBlocks)
-        n_stripes = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
-    return some_name(rs104_pick(len, n_stripes, true, false));
+    return some_name(some_pick(len, stripes_per_range(n_stripes, kTableGeom.chunks(len)), aligned));
 }
 
 hipError_t launch_some(const SomeArgs& v, bool aligned, hipStream_t stream) {
-    const ApplyArgs& a = v.a;
-    const uint64_t per_stripe = (a.len + 4095) / 4096;
-    const uint64_t items = per_stripe * a.n_stripes;
-    if (items > kMaxLaunchBlocks && a.n_stripes > 1 && per_stripe <= kMaxLaunchBlocks) {
-        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, per_stripe);
-        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
-            hipError_t e = launch_some(stripe_range(v, range_at(a.n_stripes, step, i)), aligned, stream);
-            if (e != hipSuccess) return e;
+    // launch_apply's two rules: ranges sized in 4 KiB chunks, the kernel picked per range
+    return launch_stripe_ranges(v, kTableGeom.chunks(v.a.len), [&](const SomeArgs& r) {
+        switch (some_pick(r.a.len, r.a.n_stripes, aligned)) {
+            case Rs104Kind::Apply:
+                return launch_stride(aligned ? rs_some_kernel<true> : rs_some_kernel<false>, r, stream);
+            case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
+                return launch_fast({kNarrowGeom, rs104_narrow_some_kernel, rs104_narrow_some_kernel}, r, stream);
+            default:
+                return launch_fast({kTableGeom, rs104_some_kernel<uint32_t>, rs104_some_kernel<uint64_t>}, r, stream);
         }
-        return hipSuccess;
-    }
-    SomeArgs w = v;
-    switch (aligned ? rs104_pick(a.len, a.n_stripes, true, false) : Rs104Kind::Apply) {
-        case Rs104Kind::Apply:
-            return launch_stride(aligned ? rs_some_kernel<true> : rs_some_kernel<false>, w, stream);
-        case Rs104Kind::Narrow:  // rs104_pick: only shards below 4 GiB
-            set_fast_map(w.a, kNarrowChunk, false);
-            return launch_items(rs104_narrow_some_kernel, rs104_narrow_some_kernel, w, stream);
-        default:
-            set_fast_map(w.a, kThreads * kVecBytes, true);
-            return launch_items(rs104_some_kernel<uint32_t>, rs104_some_kernel<uint64_t>, w, stream);
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1210,40 +1282,23 @@ __global__ __launch_bounds__(kThreads) void rs104_update_stride_kernel(UpdateArg
     if (a.done_flag) signal_done(a.done_count, a.done_flag, a.done_seq);
 }
 
-static UpdateArgs stripe_range(UpdateArgs v, Range r) {
-    v.a = stripe_range(v.a, r);  // the new arena, the parity arena and the mask words
-    if (v.old_base) v.old_base += uint64_t(r.first) * v.old_stripe;
-    return v;
-}
-
 // An aligned update runs one workgroup per 4 KiB column range when one
 // stripe's ranges fit a launch.
-static bool update_per_item(uint64_t len) { return (len + 4095) / 4096 <= kMaxLaunchBlocks; }
+static FastKind<UpdateArgs> update_fast(bool has_old) {
+    if (has_old) return {kTableGeom, rs104_update_kernel<true, uint32_t>, rs104_update_kernel<true, uint64_t>};
+    return {kTableGeom, rs104_update_kernel<false, uint32_t>, rs104_update_kernel<false, uint64_t>};
+}
 
 const char* update_kernel_name(uint64_t len) {
     if (len == 0) return kNoLaunch;
-    return update_per_item(len) ? "rs104_update_kernel (table lookup)" : "rs104_update_stride_kernel (table lookup)";
+    return update_fast(true).serves(len) ? "rs104_update_kernel (table lookup)"
+                                         : "rs104_update_stride_kernel (table lookup)";
 }
 
 hipError_t launch_update(const UpdateArgs& v, bool aligned, hipStream_t stream) {
-    const ApplyArgs& a = v.a;
-    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
     const bool has_old = v.old_base != nullptr;
-    if (aligned && update_per_item(a.len)) {
-        // one column range per workgroup and no grid-stride loop: batches past
-        // one launch's workgroup limit go in stripe ranges, as launch_apply's
-        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, (a.len + 4095) / 4096);
-        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
-            UpdateArgs w = stripe_range(v, range_at(a.n_stripes, step, i));
-            set_fast_map(w.a, kThreads * kVecBytes, true);
-            hipError_t e = has_old ? launch_items(rs104_update_kernel<true, uint32_t>,
-                                                  rs104_update_kernel<true, uint64_t>, w, stream)
-                                   : launch_items(rs104_update_kernel<false, uint32_t>,
-                                                  rs104_update_kernel<false, uint64_t>, w, stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+    const FastKind<UpdateArgs> fast = update_fast(has_old);
+    if (aligned && fast.serves(v.a.len)) return launch_fast_ranges(fast, v, stream);
     return launch_stride(has_old ? rs104_update_stride_kernel<true> : rs104_update_stride_kernel<false>, v, stream);
 }
 
@@ -1313,29 +1368,16 @@ constexpr const char* kGenericVerifyName = "rs_verify_kernel<10> (table lookup)"
 
 // An aligned RS(10,4) verify runs bit-sliced when the shard length is a
 // multiple of 8 KiB and one stripe's chunks fit a launch.
-static bool verify_bitsliced(uint64_t len) { return len % kBsChunk == 0 && len / kBsChunk <= kMaxLaunchBlocks; }
+static const FastKind<VerifyArgs> kBsVerify{kBsGeom, rs104_bs_verify_kernel<uint32_t>,
+                                            rs104_bs_verify_kernel<uint64_t>};
 
 const char* verify_kernel_name(uint64_t len) {
     if (len == 0) return kNoLaunch;
-    return verify_bitsliced(len) ? kBsVerifyName : kGenericVerifyName;
+    return kBsVerify.serves(len) ? kBsVerifyName : kGenericVerifyName;
 }
 
 hipError_t launch_verify(const VerifyArgs& v, int nin, bool aligned, hipStream_t stream) {
-    const ApplyArgs& a = v.a;
-    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
-    if (a.fast104 && aligned && verify_bitsliced(a.len)) {
-        // one chunk per workgroup and no grid-stride loop: batches past one
-        // launch's workgroup limit go in stripe ranges, as launch_apply's
-        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, a.len / kBsChunk);
-        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
-            const Range r = range_at(a.n_stripes, step, i);
-            VerifyArgs b{stripe_range(a, r), v.mismatch + r.first};
-            set_fast_map(b.a, kBsChunk, false);
-            hipError_t e = launch_items(rs104_bs_verify_kernel<uint32_t>, rs104_bs_verify_kernel<uint64_t>, b, stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+    if (v.a.fast104 && aligned && kBsVerify.serves(v.a.len)) return launch_fast_ranges(kBsVerify, v, stream);
     if (nin == 10) return launch_stride(aligned ? rs_verify_kernel<10, true> : rs_verify_kernel<10, false>, v, stream);
     return launch_stride(aligned ? rs_verify_kernel<0, true> : rs_verify_kernel<0, false>, v, stream);
 }
@@ -1725,58 +1767,68 @@ __global__ __launch_bounds__(kThreads, CORRECT ? 4 : PAIRS ? 5 : 1) void rs104_l
     }
 }
 
-// rs104_correct_kernel<ALIGNED, PAIRS>: the locate kernel's CORRECT form, taking CorrectArgs.
-template <bool ALIGNED, bool PAIRS>
-constexpr auto rs104_correct_kernel = rs104_locate_kernel<ALIGNED, PAIRS, true>;
+// The locate kernel (CORRECT: its correct form, taking CorrectArgs) on the locate grid.
+template <bool CORRECT, typename Args>
+static hipError_t launch_locate_form(const Args& v, bool aligned, bool pairs, hipStream_t stream) {
+    return launch_stride(
+        pairs ? (aligned ? rs104_locate_kernel<true, true, CORRECT> : rs104_locate_kernel<false, true, CORRECT>)
+              : (aligned ? rs104_locate_kernel<true, false, CORRECT> : rs104_locate_kernel<false, false, CORRECT>),
+        v, stream, kLocateMaxBlocks);
+}
 
 hipError_t launch_correct(const CorrectArgs& c, bool aligned, bool pairs, hipStream_t stream) {
-    if (c.a.n_stripes == 0 || c.a.len == 0) return hipSuccess;
-    if (pairs)
-        return launch_stride(aligned ? rs104_correct_kernel<true, true> : rs104_correct_kernel<false, true>, c, stream,
-                             kLocateMaxBlocks);
-    return launch_stride(aligned ? rs104_correct_kernel<true, false> : rs104_correct_kernel<false, false>, c, stream,
-                         kLocateMaxBlocks);
+    return launch_locate_form<true>(c, aligned, pairs, stream);
 }
 
 hipError_t launch_locate(const VerifyArgs& v, bool aligned, bool pairs, hipStream_t stream) {
-    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
-    if (pairs)
-        return launch_stride(aligned ? rs104_locate_kernel<true, true> : rs104_locate_kernel<false, true>, v, stream,
-                             kLocateMaxBlocks);
-    return launch_stride(aligned ? rs104_locate_kernel<true> : rs104_locate_kernel<false>, v, stream,
-                         kLocateMaxBlocks);
+    return launch_locate_form<false>(v, aligned, pairs, stream);
 }
 
-// Present masks of a repair, one lane per stripe; a wave counts the stripes it
-// leaves alone with one atomic.
-__global__ __launch_bounds__(kThreads) void repair_masks_kernel(const uint32_t* suspects, uint32_t* masks,
-                                                                uint32_t* unrepaired, uint32_t n_stripes) {
-    constexpr uint32_t kAll = (1u << 14) - 1;
-    // whole waves run every round, so the ballot below sees all 64 lanes
+// ---------------------------------------------------------------------------
+// The mask kernels: one lane per stripe writes the stripe's present mask for
+// the reconstruct that follows, by a rule of its own. rule(s) writes what
+// stripe s gets and says whether the stripe is left alone; a wave counts the
+// stripes it leaves alone with one atomic. Whole waves run every round, so the
+// ballot sees all 64 lanes.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAllShards = (1u << 14) - 1;
+
+template <typename Rule>
+__device__ __forceinline__ void mask_rounds(uint32_t n_stripes, uint32_t* unrepaired, Rule rule) {
     const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
     const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
     for (uint32_t r = 0; r < rounds; ++r) {
         const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
-        bool left = false;
-        if (s < n_stripes) {
-            const uint32_t w = suspects[s];
-            const uint32_t named = uint32_t(__builtin_popcount(w & kAll));
-            const bool repair = (w & kSuspectUnexplained) == 0 && named >= 1 && named <= 4;
-            masks[s] = repair ? (kAll & ~w) : kAll;
-            left = w != 0 && !repair;
-        }
+        const bool left = s < n_stripes && rule(s);
         const unsigned long long b = __ballot(left);
         if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
     }
 }
 
-hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32_t* unrepaired, uint32_t n_stripes,
-                               hipStream_t stream) {
+// One lane per stripe on at most kLocateMaxBlocks workgroups; args end with n_stripes.
+template <typename... Params, typename... Vals>
+static hipError_t launch_mask_rounds(void (*kern)(Params...), uint32_t n_stripes, hipStream_t stream, Vals... args) {
     if (n_stripes == 0) return hipSuccess;
     const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
-    hipLaunchKernelGGL(repair_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, suspects, masks, unrepaired,
-                       n_stripes);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), 0, stream, args...);
     return hipGetLastError();
+}
+
+// Present masks of a repair.
+__global__ __launch_bounds__(kThreads) void repair_masks_kernel(const uint32_t* suspects, uint32_t* masks,
+                                                                uint32_t* unrepaired, uint32_t n_stripes) {
+    mask_rounds(n_stripes, unrepaired, [&](uint64_t s) {
+        const uint32_t w = suspects[s];
+        const uint32_t named = uint32_t(__builtin_popcount(w & kAllShards));
+        const bool repair = (w & kSuspectUnexplained) == 0 && named >= 1 && named <= 4;
+        masks[s] = repair ? (kAllShards & ~w) : kAllShards;
+        return w != 0 && !repair;
+    });
+}
+
+hipError_t launch_repair_masks(const uint32_t* suspects, uint32_t* masks, uint32_t* unrepaired, uint32_t n_stripes,
+                               hipStream_t stream) {
+    return launch_mask_rounds(repair_masks_kernel, n_stripes, stream, suspects, masks, unrepaired, n_stripes);
 }
 
 // ---------------------------------------------------------------------------
@@ -1885,34 +1937,15 @@ constexpr const char* kStrideCheckName = "rs104_check_stride_kernel (table looku
 
 // The fast check takes shard lengths that are a multiple of 2 KiB below 4 GiB
 // whose chunks fit one launch (launch_check's stripe ranges hold whole stripes).
-static bool check_fast(uint64_t len) {
-    return len % kNarrowChunk == 0 && len <= 0xFFFFFFFFull && len / kNarrowChunk <= kMaxLaunchBlocks;
-}
+static const FastKind<CheckArgs> kFastCheck{kNarrowGeom, rs104_check_kernel, rs104_check_kernel};
 
 const char* check_kernel_name(uint64_t len) {
     if (len == 0) return kNoLaunch;
-    return check_fast(len) ? kFastCheckName : kStrideCheckName;
+    return kFastCheck.serves(len) ? kFastCheckName : kStrideCheckName;
 }
 
 hipError_t launch_check(const CheckArgs& v, bool aligned, hipStream_t stream) {
-    const ApplyArgs& a = v.a;
-    if (a.n_stripes == 0 || a.len == 0) return hipSuccess;
-    if (aligned && check_fast(a.len)) {
-        // one chunk per workgroup and no grid-stride loop: batches past one
-        // launch's workgroup limit go in stripe ranges, as launch_verify's
-        // (the masks advance in stripe_range, the words here)
-        const uint64_t step = stripes_per_launch(kMaxLaunchBlocks, a.len / kNarrowChunk);
-        for (uint64_t i = 0, n = n_ranges(a.n_stripes, step); i < n; ++i) {
-            const Range r = range_at(a.n_stripes, step, i);
-            CheckArgs b = v;
-            b.a = stripe_range(a, r);
-            b.check = v.check + r.first;
-            set_fast_map(b.a, kNarrowChunk, false);
-            hipError_t e = launch_items(rs104_check_kernel, rs104_check_kernel, b, stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+    if (aligned && kFastCheck.serves(v.a.len)) return launch_fast_ranges(kFastCheck, v, stream);
     return launch_stride(aligned ? rs104_check_stride_kernel<true> : rs104_check_stride_kernel<false>, v, stream);
 }
 
@@ -2144,20 +2177,22 @@ __global__ __launch_bounds__(kThreads) void rs104_locate_present_kernel(
     }
 }
 
-// rs104_correct_present_kernel<ALIGNED>: the masked locate's CORRECT form, taking CorrectPresentArgs.
-template <bool ALIGNED>
-constexpr auto rs104_correct_present_kernel = rs104_locate_present_kernel<ALIGNED, true>;
+// The masked locate (CORRECT: rs104_correct_present_kernel, taking
+// CorrectPresentArgs) on the locate grid; launch_ragged_walk launches the
+// RAGGED forms.
+template <bool CORRECT, typename Args>
+static hipError_t launch_locate_present_form(const Args& v, bool aligned, hipStream_t stream) {
+    return launch_stride(
+        aligned ? rs104_locate_present_kernel<true, CORRECT> : rs104_locate_present_kernel<false, CORRECT>, v, stream,
+        kLocateMaxBlocks);
+}
 
 hipError_t launch_locate_present(const CheckArgs& v, bool aligned, hipStream_t stream) {
-    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
-    return launch_stride(aligned ? rs104_locate_present_kernel<true> : rs104_locate_present_kernel<false>, v, stream,
-                         kLocateMaxBlocks);
+    return launch_locate_present_form<false>(v, aligned, stream);
 }
 
 hipError_t launch_correct_present(const CorrectPresentArgs& v, bool aligned, hipStream_t stream) {
-    if (v.a.n_stripes == 0 || v.a.len == 0) return hipSuccess;
-    return launch_stride(aligned ? rs104_correct_present_kernel<true> : rs104_correct_present_kernel<false>, v, stream,
-                         kLocateMaxBlocks);
+    return launch_locate_present_form<true>(v, aligned, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2265,30 +2300,22 @@ hipError_t launch_ragged_check(const RaggedScrubArgs& v, bool bitslice, hipStrea
     return launch_ragged(bitslice ? rs104_bs_ragged_verify_kernel : rs104_ragged_check_kernel, v, stream);
 }
 
-// rs104_ragged_locate_kernel: the masked locate's RAGGED form, taking RaggedScrubArgs.
-constexpr auto rs104_ragged_locate_kernel = rs104_locate_present_kernel<true, false, true>;
-
-hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream) {
-    RaggedScrubArgs w = v;
-    w.half_shift = bitslice ? 1u : 0u;  // an 8 KiB entry is two of the walk's 4 KiB ranges
-    const uint64_t items = uint64_t(w.a.n_blocks) << w.half_shift;
-    if (items == 0) return hipSuccess;
-    const uint64_t grid = std::min<uint64_t>(items, kLocateMaxBlocks);  // grid-stride covers the rest
-    hipLaunchKernelGGL(rs104_ragged_locate_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, w);
-    return hipGetLastError();
+// The masked locate's RAGGED form (rs104_ragged_locate_kernel, taking
+// RaggedScrubArgs; CORRECT: rs104_ragged_correct_kernel, taking
+// RaggedCorrectArgs) over the 4 KiB ranges of pass 1's map, on the locate grid.
+template <bool CORRECT, typename Args>
+static hipError_t launch_ragged_walk(Args v, bool bitslice, hipStream_t stream) {
+    v.half_shift = bitslice ? 1u : 0u;  // an 8 KiB entry is two of the walk's 4 KiB ranges
+    return launch_grid_stride(rs104_locate_present_kernel<true, CORRECT, true>, v,
+                              uint64_t(v.a.n_blocks) << v.half_shift, kLocateMaxBlocks, stream);
 }
 
-// rs104_ragged_correct_kernel: the masked locate's RAGGED and CORRECT form, taking RaggedCorrectArgs.
-constexpr auto rs104_ragged_correct_kernel = rs104_locate_present_kernel<true, true, true>;
+hipError_t launch_ragged_locate(const RaggedScrubArgs& v, bool bitslice, hipStream_t stream) {
+    return launch_ragged_walk<false>(v, bitslice, stream);
+}
 
 hipError_t launch_ragged_correct(const RaggedCorrectArgs& v, bool bitslice, hipStream_t stream) {
-    RaggedCorrectArgs w = v;
-    w.half_shift = bitslice ? 1u : 0u;  // as launch_ragged_locate
-    const uint64_t items = uint64_t(w.a.n_blocks) << w.half_shift;
-    if (items == 0) return hipSuccess;
-    const uint64_t grid = std::min<uint64_t>(items, kLocateMaxBlocks);  // grid-stride covers the rest
-    hipLaunchKernelGGL(rs104_ragged_correct_kernel, dim3(uint32_t(grid)), dim3(kThreads), 0, stream, w);
-    return hipGetLastError();
+    return launch_ragged_walk<true>(v, bitslice, stream);
 }
 
 __global__ void add_word_kernel(uint32_t* word, uint32_t n) { atomicAdd(word, n); }
@@ -2298,78 +2325,54 @@ hipError_t launch_add_word(uint32_t* word, uint32_t n, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// repair_masks_kernel with the present mask and the check word taken into
-// account; a wave counts the stripes it leaves alone with one atomic.
+// repair_masks_kernel's rounds (mask_rounds) with the present mask and the
+// check word taken into account.
 __global__ __launch_bounds__(kThreads) void use_masks_kernel(const uint32_t* present, const uint32_t* check,
                                                              const uint32_t* suspects, uint32_t* use,
                                                              uint32_t* unrepaired, uint32_t n_stripes) {
-    constexpr uint32_t kAll = (1u << 14) - 1;
-    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
-    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
-    for (uint32_t r = 0; r < rounds; ++r) {
-        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
-        bool left = false;
-        if (s < n_stripes) {
-            const uint32_t m = present[s] & kAll;
-            if (check[s] == 0) {
-                use[s] = m;  // clean, or nothing to check: the plain reconstruct
-            } else {
-                const uint32_t w = suspects[s], kept = m & ~w;
-                const bool repair =
-                    (w & kSuspectUnexplained) == 0 && (w & kAll) != 0 && __builtin_popcount(kept) >= 10;
-                use[s] = repair ? kept : kAll;
-                left = !repair;
-            }
+    mask_rounds(n_stripes, unrepaired, [&](uint64_t s) {
+        const uint32_t m = present[s] & kAllShards;
+        if (check[s] == 0) {
+            use[s] = m;  // clean, or nothing to check: the plain reconstruct
+            return false;
         }
-        const unsigned long long b = __ballot(left);
-        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
-    }
+        const uint32_t w = suspects[s], kept = m & ~w;
+        const bool repair =
+            (w & kSuspectUnexplained) == 0 && (w & kAllShards) != 0 && __builtin_popcount(kept) >= 10;
+        use[s] = repair ? kept : kAllShards;
+        return !repair;
+    });
 }
 
 hipError_t launch_use_masks(const uint32_t* present, const uint32_t* check, const uint32_t* suspects, uint32_t* use,
                             uint32_t* unrepaired, uint32_t n_stripes, hipStream_t stream) {
-    if (n_stripes == 0) return hipSuccess;
-    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
-    hipLaunchKernelGGL(use_masks_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects, use,
-                       unrepaired, n_stripes);
-    return hipGetLastError();
+    return launch_mask_rounds(use_masks_kernel, n_stripes, stream, present, check, suspects, use, unrepaired,
+                              n_stripes);
 }
 
 // The use masks after rs104_correct_present_kernel (min_spares: the call's):
 // nothing is dropped; a stripe is rebuilt from its own survivors when they are
 // consistent (clean, unchecked, or corrected with bit 31 clear) and left
-// alone, holes included, otherwise. Same rounds and count as use_masks_kernel.
+// alone, holes included, otherwise.
 __global__ __launch_bounds__(kThreads) void use_masks_corrected_kernel(const uint32_t* present, const uint32_t* check,
                                                                        const uint32_t* suspects, uint32_t* use,
                                                                        uint32_t* unrepaired, uint32_t min_spares,
                                                                        uint32_t n_stripes) {
-    constexpr uint32_t kAll = (1u << 14) - 1;
-    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
-    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
-    for (uint32_t r = 0; r < rounds; ++r) {
-        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
-        bool left = false;
-        if (s < n_stripes) {
-            const uint32_t m = present[s] & kAll;
-            const bool consistent =
-                check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
-                                  (suspects[s] & kSuspectUnexplained) == 0);
-            use[s] = consistent ? m : kAll;
-            left = !consistent;
-        }
-        const unsigned long long b = __ballot(left);
-        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
-    }
+    mask_rounds(n_stripes, unrepaired, [&](uint64_t s) {
+        const uint32_t m = present[s] & kAllShards;
+        const bool consistent =
+            check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
+                              (suspects[s] & kSuspectUnexplained) == 0);
+        use[s] = consistent ? m : kAllShards;
+        return !consistent;
+    });
 }
 
 hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* check, const uint32_t* suspects,
                                       uint32_t* use, uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
                                       hipStream_t stream) {
-    if (n_stripes == 0) return hipSuccess;
-    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
-    hipLaunchKernelGGL(use_masks_corrected_kernel, dim3(grid), dim3(kThreads), 0, stream, present, check, suspects,
-                       use, unrepaired, min_spares, n_stripes);
-    return hipGetLastError();
+    return launch_mask_rounds(use_masks_corrected_kernel, n_stripes, stream, present, check, suspects, use,
+                              unrepaired, min_spares, n_stripes);
 }
 
 // use_masks_corrected_kernel after rs104_ragged_correct_kernel: the present
@@ -2380,35 +2383,23 @@ hipError_t launch_use_masks_corrected(const uint32_t* present, const uint32_t* c
 __global__ __launch_bounds__(kThreads) void ragged_use_masks_corrected_kernel(
     const RaggedItem* scrub_items, RaggedItem* decode_items, const uint32_t* check, const uint32_t* suspects,
     uint32_t* use, uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes) {
-    constexpr uint32_t kAll = (1u << 14) - 1;
-    const uint64_t per_round = uint64_t(gridDim.x) * kThreads;
-    const uint32_t rounds = uint32_t((n_stripes + per_round - 1) / per_round);
-    for (uint32_t r = 0; r < rounds; ++r) {
-        const uint64_t s = (uint64_t(r) * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
-        bool left = false;
-        if (s < n_stripes) {
-            const uint32_t m = scrub_items[s].mask & kAll;
-            const bool consistent =
-                check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
-                                  (suspects[s] & kSuspectUnexplained) == 0);
-            use[s] = consistent ? m : kAll;
-            if (!consistent) decode_items[s].mask = kAll;
-            left = !consistent;
-        }
-        const unsigned long long b = __ballot(left);
-        if (b != 0 && unrepaired && (threadIdx.x & 63u) == 0) atomicAdd(unrepaired, uint32_t(__builtin_popcountll(b)));
-    }
+    mask_rounds(n_stripes, unrepaired, [&](uint64_t s) {
+        const uint32_t m = scrub_items[s].mask & kAllShards;
+        const bool consistent =
+            check[s] == 0 || (uint32_t(__builtin_popcount(m)) >= 10 + min_spares &&
+                              (suspects[s] & kSuspectUnexplained) == 0);
+        use[s] = consistent ? m : kAllShards;
+        if (!consistent) decode_items[s].mask = kAllShards;
+        return !consistent;
+    });
 }
 
 hipError_t launch_ragged_use_masks_corrected(const RaggedItem* scrub_items, RaggedItem* decode_items,
                                              const uint32_t* check, const uint32_t* suspects, uint32_t* use,
                                              uint32_t* unrepaired, uint32_t min_spares, uint32_t n_stripes,
                                              hipStream_t stream) {
-    if (n_stripes == 0) return hipSuccess;
-    const uint32_t grid = std::min<uint32_t>((n_stripes + kThreads - 1) / kThreads, kLocateMaxBlocks);
-    hipLaunchKernelGGL(ragged_use_masks_corrected_kernel, dim3(grid), dim3(kThreads), 0, stream, scrub_items,
-                       decode_items, check, suspects, use, unrepaired, min_spares, n_stripes);
-    return hipGetLastError();
+    return launch_mask_rounds(ragged_use_masks_corrected_kernel, n_stripes, stream, scrub_items, decode_items, check,
+                              suspects, use, unrepaired, min_spares, n_stripes);
 }
 
 // ---------------------------------------------------------------------------
