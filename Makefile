@@ -60,7 +60,7 @@ VARIANTS := null smallgrid smallchunk
 VFLAGS_null := -DHEC_NULL_VARIANT=1
 VSRC_null := rs_kernels.hip
 VFLAGS_smallgrid := -DHEC_MAX_LAUNCH_BLOCKS=100 -DHEC_LOCATE_MAX_BLOCKS=4
-VSRC_smallgrid := rs_kernels.hip
+VSRC_smallgrid := rs_kernels.hip rs_update_ragged.hip
 VFLAGS_smallchunk := -DHEC_HOST_CHUNK_BYTES=49152 -DHEC_SCRUB_CHUNK_COLS=12288 -DHEC_SCRUB_READ_PIECE=5000
 VSRC_smallchunk := host_pipeline.cpp verify_files.cpp
 variants: $(foreach v,$(VARIANTS),build/variants/libhec_$(v).so)

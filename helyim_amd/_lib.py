@@ -59,6 +59,9 @@ SIGNATURES = {
     "hec_gpu_update_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P, _P]),
     "hec_host_update_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P]),
     "hec_update_kernel_name": (ctypes.c_char_p, [ctypes.c_uint64]),
+    "hec_rs_update_batch": (_I, [_P, _P, _P, _P, _S, ctypes.POINTER(_S)]),
+    "hec_gpu_update_ragged": (_I, [_P, _P, _P, _P, _P, _U32, _P]),
+    "hec_update_ragged_kernel_name": (ctypes.c_char_p, [_I]),
     "hec_gpu_encode_batch": (_I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _U32, _P]),
     "hec_gpu_reconstruct_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P]),
     "hec_gpu_reconstruct_some_batch": (_I, [_P, _P, _U64, _U64, _U64, _U32, _P, _P, _P, _P]),

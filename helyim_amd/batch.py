@@ -667,6 +667,111 @@ def reconstruct_some_ragged(rs: ReedSolomon, base: torch.Tensor, descs, want_mas
                                               _counter_arg(bad_stripes, "bad_stripes"), _stream_ptr(stream)))
 
 
+UPDATE_DESC_DTYPE = None
+
+
+def update_desc_dtype():
+    """numpy dtype of include/hec.h ``hec_update_desc`` (56 bytes)."""
+    import numpy as np
+    global UPDATE_DESC_DTYPE
+    if UPDATE_DESC_DTYPE is None:
+        UPDATE_DESC_DTYPE = np.dtype([("parity_offset", "<u8"), ("parity_stride", "<u8"), ("new_offset", "<u8"),
+                                      ("new_stride", "<u8"), ("old_offset", "<u8"), ("old_stride", "<u8"),
+                                      ("shard_len", "<u4"), ("update_mask", "<u4")])
+    return UPDATE_DESC_DTYPE
+
+
+def _update_arena(t, name: str):
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous uint8 CUDA tensor")
+    _check_device(t)
+
+
+def _update_desc_array(descs, old, new: torch.Tensor, parity: torch.Tensor):
+    """descs: an ``update_desc_dtype()`` array, or rows of its eight fields in
+    order. As _desc_array, every stripe's bytes must lie inside its arenas: the
+    four parity shards in ``parity``, the ten data shards in ``new`` and, when
+    given, ``old`` (checked here: the C ABI only sees pointers)."""
+    import numpy as np
+    dt = update_desc_dtype()
+    if isinstance(descs, np.ndarray) and descs.dtype == dt:
+        d = np.ascontiguousarray(descs)
+    else:
+        rows = [tuple(int(x) for x in r) for r in descs]
+        if any(len(r) != len(dt.names) for r in rows):
+            raise ValueError(f"an update descriptor has {len(dt.names)} fields: {', '.join(dt.names)}")
+        d = np.array(rows, dtype=dt)
+    arenas = [("parity", parity, 4), ("new", new, 10)] + ([("old", old, 10)] if old is not None else [])
+    for name, t, shards in arenas:
+        _update_arena(t, name)
+        if not len(d):
+            continue
+        off, stride, ln = d[name + "_offset"], d[name + "_stride"], d["shard_len"].astype(np.uint64)
+        limit = np.uint64(t.numel())
+        # no wrap-around: every term is checked against the buffer before summing
+        bad = (off > limit) | (stride > limit) | (ln > limit)
+        end = off + np.uint64(shards - 1) * np.minimum(stride, limit) + ln
+        bad |= end > limit
+        bad |= (ln > 0) & (stride < ln)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"stripe {i} ({name} offset {int(off[i])}, stride {int(stride[i])}, len {int(ln[i])}) "
+                             f"overlaps itself or runs past the {name} arena ({t.numel()} bytes)")
+    return d
+
+
+def update_ragged(rs: ReedSolomon, old, new: torch.Tensor, parity: torch.Tensor, descs, stream=None) -> None:
+    """update_batch_sep over stripes of mixed lengths in one launch
+    (hec_gpu_update_ragged, RS(10,4)): ``old`` (or None: old is zero), ``new``
+    and ``parity`` are flat uint8 arenas, descs rows are (parity offset, parity
+    stride, new offset, new stride, old offset, old stride, shard length, update
+    mask). ``parity`` may be the tensor ``old`` is (the in-place ragged arena,
+    update_descs_in_place). Only bytes [0, shard length) of the four parity
+    shards of stripes with a non-empty mask are written. Asynchronous."""
+    d = _update_desc_array(descs, old, new, parity)
+    check(lib.hec_gpu_update_ragged(rs.handle, old.data_ptr() if old is not None else None, new.data_ptr(),
+                                    parity.data_ptr(), d.ctypes.data, len(d), _stream_ptr(stream)))
+
+
+def update_descs_in_place(descs, new_descs, masks):
+    """Update descriptors of an in-place ragged arena: ``descs`` (desc_dtype
+    rows) place every stripe's 14 shards in the arena passed as both ``old``
+    and ``parity``; ``new_descs`` (desc_dtype rows; the mask field is not read)
+    place its ten new data shards in the ``new`` arena; masks: one update mask
+    per stripe."""
+    import numpy as np
+    dt = desc_dtype()
+
+    def as_descs(x):
+        if isinstance(x, np.ndarray) and x.dtype == dt:
+            return x
+        return np.array([tuple(int(v) for v in r) for r in x], dtype=dt)
+
+    d, nd = as_descs(descs), as_descs(new_descs)
+    m = np.asarray(masks, dtype=np.uint32).reshape(-1)
+    if not (len(d) == len(nd) == m.size):
+        raise ValueError(f"{len(d)} stripes, {len(nd)} new-data descriptors, {m.size} masks")
+    if (d["shard_len"] != nd["shard_len"]).any():
+        i = int(np.argmax(d["shard_len"] != nd["shard_len"]))
+        raise ValueError(f"stripe {i}: shard length {int(d['shard_len'][i])} against {int(nd['shard_len'][i])} "
+                         "of its new data")
+    out = np.zeros(len(d), dtype=update_desc_dtype())
+    out["parity_offset"] = d["offset"] + np.uint64(10) * d["shard_stride"]
+    out["parity_stride"] = d["shard_stride"]
+    out["new_offset"] = nd["offset"]
+    out["new_stride"] = nd["shard_stride"]
+    out["old_offset"] = d["offset"]
+    out["old_stride"] = d["shard_stride"]
+    out["shard_len"] = d["shard_len"]
+    out["update_mask"] = m
+    return out
+
+
+def update_ragged_kernel_name(with_old: bool) -> str:
+    """Kernel update_ragged runs with an old arena or without (hec_update_ragged_kernel_name)."""
+    return lib.hec_update_ragged_kernel_name(1 if with_old else 0).decode()
+
+
 def _ragged_args(rs, base, descs, **words):
     """The ragged scrub calls' shared preparation -> (the descriptor array,
     the per-stripe result tensors named in words, allocated when None)."""

@@ -285,7 +285,7 @@ int current_device(int* dev);
 
 // Completion of one small host call without hipStreamSynchronize: the
 // launch's last workgroup stores a sequence number into a pinned host flag
-// (signal_done in rs_kernels.hip) and the caller spins on it. Measured on
+// (signal_done in rs_device.hpp) and the caller spins on it. Measured on
 // MI355X (profiles/r02/latency_completion_signal.jsonl): a one-workgroup zero-copy stripe
 // completes in 9.2 us this way against 13.3 us through hipStreamSynchronize.
 // Owned by a scratch object, so calls on it are serialised by its mutex.
@@ -442,6 +442,22 @@ using CompactFill = std::function<int(size_t job, int slot, int shard, uint8_t* 
 using CompactTake = std::function<void(size_t job, int shard, const uint8_t* src)>;
 int compact_reconstruct_104(const hec_rs* rs, const std::vector<CompactJob>& jobs, const CompactFill& fill,
                             const CompactTake& take, bool io_bound_fill = false);
+
+// Batched RS(10,4) update of independent stripes through the same compact
+// staging and one rs104_ragged_update_kernel<false, true> launch
+// (intervals.cpp; hec.h hec_rs_update_batch is the contract). Job j has shard
+// length len (1 .. 2^32 - 1) and a non-empty update mask; shards / new_data are
+// hec_rs_update's arrays of that stripe, already checked. The deltas old ^ new
+// of the changed shards are packed at their rank in the mask, the four parity
+// shards behind them; the updated parity is copied back into shards[10..13].
+// Synchronous, error returns included.
+struct UpdateJob {
+    uint64_t len;
+    uint32_t mask;
+    uint8_t* const* shards;
+    const uint8_t* const* new_data;
+};
+int compact_update_104(const hec_rs* rs, const std::vector<UpdateJob>& jobs);
 
 // Run fn(i) for i in [0, n) on a persistent host worker pool of the calling
 // thread's current device (host memcpy of staging): up to 16 threads, at

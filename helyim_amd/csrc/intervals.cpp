@@ -297,7 +297,7 @@ uint64_t ragged_chunks(const hec_stripe_desc& d, RaggedOp op, uint32_t chunk_byt
 // The kernel of one ragged launch, shared by gpu_ragged and
 // hec_ragged_kernel_name so a reported name is the kernel that runs. Both
 // ragged kernels deal each XCD a contiguous eighth of the launch's column
-// ranges (ragged_block, rs_kernels.hip).
+// ranges (ragged_block, rs_device.hpp).
 struct RaggedPick {
     bool bitslice;  // encode with every length a multiple of 8 KiB: rs104_bs_ragged_kernel
 };
@@ -525,10 +525,247 @@ int gpu_ragged_scrub(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc*
     return c.end(stream);
 }
 
+// One arena of a ragged update descriptor: 16-byte aligned, shards apart, the
+// extent offset + shards * stride inside 64 bits.
+bool update_arena_ok(const void* base, uint64_t off, uint64_t stride, uint32_t len, uint64_t shards) {
+    uint64_t ext;
+    if ((off | stride | uint64_t(reinterpret_cast<uintptr_t>(base))) % 16 != 0 || stride < len) return false;
+    return !__builtin_mul_overflow(stride, shards, &ext) && !__builtin_add_overflow(ext, off, &ext);
+}
+
+// The argument and descriptor checks of hec_gpu_update_ragged in
+// ragged_check_args' order, all before device work; *n_blocks = the workgroup
+// map's entries (4 KiB column ranges of the stripes with U non-empty).
+int update_ragged_check_args(const hec_rs_t* rs, const uint8_t* d_old, const uint8_t* d_new, const uint8_t* d_parity,
+                             const hec_update_desc* descs, uint32_t n, uint64_t* n_blocks) {
+    if (!rs || !d_new || !d_parity || (n && !descs)) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(rs->k == 10 && rs->m == 4)) return fail(HEC_ERR_INVALID_ARGUMENT, "ragged update is RS(10,4) only");
+    *n_blocks = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        const hec_update_desc& d = descs[j];
+        if (d.shard_len == 0) return fail(HEC_ERR_EMPTY_SHARD, "stripe " + std::to_string(j));
+        if (!update_arena_ok(d_parity, d.parity_offset, d.parity_stride, d.shard_len, 4) ||
+            !update_arena_ok(d_new, d.new_offset, d.new_stride, d.shard_len, 10) ||
+            (d_old && !update_arena_ok(d_old, d.old_offset, d.old_stride, d.shard_len, 10)))
+            return fail(HEC_ERR_INVALID_ARGUMENT, "stripe " + std::to_string(j) +
+                                                      ": offsets/strides must be 16-byte aligned, stride >= len");
+        if (d.update_mask & 0x3FFu) *n_blocks += (uint64_t(d.shard_len) + 4095) / 4096;
+        if (*n_blocks > UINT32_MAX) return fail(HEC_ERR_INVALID_ARGUMENT, "ragged batch above 2^32 workgroups");
+    }
+    return HEC_OK;
+}
+
+// hec_gpu_update_ragged: a sibling of RaggedCall (its descriptor, its item and
+// its three arenas are the update's own), over the same metadata slots.
+int gpu_update_ragged(const hec_rs_t* rs, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
+                      const hec_update_desc* descs, uint32_t n, hipStream_t stream) {
+    uint64_t n_blocks = 0;
+    HEC_TRY(update_ragged_check_args(rs, d_old, d_new, d_parity, descs, n, &n_blocks));
+    if (n == 0) return HEC_OK;
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<RaggedScratch> lease;
+    HEC_TRY(lease_slot(lease));
+    const size_t map_off = round_up(size_t(n) * sizeof(UpdateItem), 256);
+    const size_t bytes = map_off + n_blocks * 4;
+    MetaSlot* slot = &lease.sc->slots[lease.sc->next_slot++ % kMetaSlots];
+    HEC_TRY(slot->reserve(bytes));  // waits for this slot's previous kernels only
+    if (n_blocks) {
+        UpdateItem* items = reinterpret_cast<UpdateItem*>(slot->h.p);
+        uint32_t* block_item = reinterpret_cast<uint32_t*>(slot->h + map_off);
+        uint32_t first = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const hec_update_desc& d = descs[j];
+            const uint32_t chunks = (d.update_mask & 0x3FFu) ? uint32_t((uint64_t(d.shard_len) + 4095) / 4096) : 0;
+            items[j] = UpdateItem{d.parity_offset, d.parity_stride, d.new_offset,  d.new_stride, d.old_offset,
+                                  d.old_stride,    d.shard_len,     d.update_mask, first,        0};
+            std::fill(block_item + first, block_item + first + chunks, j);
+            first += chunks;
+        }
+        HEC_HIP(hipMemcpyAsync(slot->d, slot->h, bytes, hipMemcpyHostToDevice, stream));
+        RaggedUpdateArgs v{};
+        v.a.base = d_parity;
+        v.a.block_item = reinterpret_cast<const uint32_t*>(slot->d + map_off);
+        v.a.n_blocks = uint32_t(n_blocks);
+        v.a.tabs = gd->encode.tabs;
+        v.new_base = d_new;
+        v.old_base = d_old;
+        v.items = reinterpret_cast<const UpdateItem*>(slot->d.p);
+        HEC_HIP(launch_ragged_update(v, stream));
+    }
+    // every mask empty: nothing launched, the slot free again in stream order
+    HEC_HIP(hipEventRecord(slot->free, stream));
+    return HEC_OK;
+}
+
 }  // namespace
+
+// hec_rs_update_batch's RS(10,4) path, compact_reconstruct_104's shape: per job
+// the deltas old ^ new of its changed shards packed compactly (XORed while
+// packing) and its four parity shards behind them in the pinned staging, one
+// rs104_ragged_update_kernel<false, true> launch over them in place (zero copy)
+// or through the device copy, and the parity handed back.
+int compact_update_104(const hec_rs* rs, const std::vector<UpdateJob>& jobs) {
+    const int k = rs->k, m = rs->m;
+    struct Lay {
+        uint64_t Lp, off, par_off;
+    };
+    std::vector<Lay> lay(jobs.size());
+    uint64_t total = 0, n_blocks = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {  // the deltas of every job first: one upload
+        if (jobs[j].len == 0 || jobs[j].len > 0xFFFFFFFFull || (jobs[j].mask & 0x3FFu) == 0)
+            return fail(HEC_ERR_INVALID_ARGUMENT, "compact update job without a length or a changed shard");
+        lay[j].Lp = round_up(jobs[j].len, 16);
+        lay[j].off = total;
+        total += round_up(uint64_t(__builtin_popcount(jobs[j].mask & 0x3FFu)) * lay[j].Lp, 256);
+        n_blocks += (jobs[j].len + 4095) / 4096;
+    }
+    if (jobs.empty()) return HEC_OK;
+    if (n_blocks > UINT32_MAX) return fail(HEC_ERR_INVALID_ARGUMENT, "update batch above 2^32 workgroups");
+    const uint64_t delta_total = total;
+    for (size_t j = 0; j < jobs.size(); ++j) {  // then the parity, read and written
+        lay[j].par_off = total;
+        total += round_up(uint64_t(m) * lay[j].Lp, 256);
+    }
+    GeomDevice* gd;
+    HEC_TRY(geom_device(rs, &gd));
+    Lease<RaggedScratch> lease;
+    HEC_TRY(lease_slot(lease));
+    RaggedScratch* sc = lease.sc;
+    std::vector<UpdateItem> items(jobs.size());
+    std::vector<uint32_t> block_item;
+    block_item.reserve(n_blocks);
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        items[j] = UpdateItem{lay[j].par_off, lay[j].Lp, lay[j].off, lay[j].Lp, 0, 0, uint32_t(jobs[j].len),
+                              jobs[j].mask & 0x3FFu, uint32_t(block_item.size()), 0};
+        block_item.insert(block_item.end(), size_t((jobs[j].len + 4095) / 4096), uint32_t(j));
+    }
+    const size_t items_bytes = items.size() * sizeof(UpdateItem);
+    const size_t map_off = round_up(items_bytes, 256);
+    const size_t meta = map_off + block_item.size() * 4;
+    HEC_TRY(sc->reserve(total, meta));
+    // one task per (job, slot): slots 0..k-1 the data shards (a changed one packs
+    // its delta at its rank in U), slots k..k+m-1 the parity shards
+    parallel_for(jobs.size() * size_t(k + m), total, [&](size_t t) {
+        const size_t j = t / size_t(k + m);
+        const int i = int(t % size_t(k + m));
+        const UpdateJob& job = jobs[j];
+        const size_t L = job.len;
+        if (i >= k) {
+            std::memcpy(sc->host + lay[j].par_off + uint64_t(i - k) * lay[j].Lp, job.shards[i], L);
+        } else if ((job.mask >> i) & 1) {
+            const uint32_t q = uint32_t(__builtin_popcount(job.mask & ((1u << i) - 1)));
+            uint8_t* dst = sc->host + lay[j].off + uint64_t(q) * lay[j].Lp;
+            const uint8_t *o = job.shards[i], *w = job.new_data[i];
+            for (size_t b = 0; b < L; ++b) dst[b] = o[b] ^ w[b];
+        }
+    });
+    // zero-copy: the kernel reads the deltas and updates the parity in the pinned staging itself
+    uint8_t* zh = zero_copy_enabled() ? pinned_device_ptr(sc->host) : nullptr;
+    StreamDrain drain{sc->stream};
+    if (!zh) HEC_HIP(hipMemcpyAsync(sc->dev, sc->host, total, hipMemcpyHostToDevice, sc->stream));
+    RaggedUpdateArgs v{};
+    v.a.base = zh ? zh : sc->dev.p;
+    v.new_base = v.a.base;
+    v.a.n_blocks = uint32_t(block_item.size());
+    v.a.tabs = gd->encode.tabs;
+    v.a.compact = 1;
+    if (items.size() == 1) {  // one stripe: descriptor as a kernel argument
+        v.a.inline_one = 1;
+        v.one = items[0];
+    } else {
+        std::memcpy(sc->hmeta, items.data(), items_bytes);
+        std::memcpy(sc->hmeta + map_off, block_item.data(), block_item.size() * 4);
+        HEC_HIP(hipMemcpyAsync(sc->dmeta, sc->hmeta, meta, hipMemcpyHostToDevice, sc->stream));
+        v.items = reinterpret_cast<const UpdateItem*>(sc->dmeta.p);
+        v.a.block_item = reinterpret_cast<const uint32_t*>(sc->dmeta + map_off);
+    }
+    const bool signal = zh && total <= completion_flag_max();
+    if (signal) HEC_TRY(sc->done.arm(sc->stream, &v.a.done_count, &v.a.done_flag, &v.a.done_seq));
+    HEC_HIP(launch_ragged_update(v, sc->stream));
+    if (!zh)
+        HEC_HIP(hipMemcpyAsync(sc->host + delta_total, sc->dev + delta_total, total - delta_total,
+                               hipMemcpyDeviceToHost, sc->stream));
+    if (signal) HEC_TRY(sc->done.wait(sc->stream));
+    else HEC_HIP(hipStreamSynchronize(sc->stream));
+    parallel_for(jobs.size() * size_t(m), total - delta_total, [&](size_t t) {
+        const size_t j = t / size_t(m), r = t % size_t(m);
+        std::memcpy(jobs[j].shards[size_t(k) + r], sc->host + lay[j].par_off + r * lay[j].Lp, jobs[j].len);
+    });
+    return HEC_OK;
+}
+
 }  // namespace hec
 
 extern "C" {
+
+int hec_gpu_update_ragged(const hec_rs_t* rs, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
+                          const hec_update_desc* descs, uint32_t n_stripes, void* stream) {
+    return hec::gpu_update_ragged(rs, d_old, d_new, d_parity, descs, n_stripes, static_cast<hipStream_t>(stream));
+}
+
+const char* hec_update_ragged_kernel_name(int with_old) { return hec::ragged_update_kernel_name(with_old != 0); }
+
+// Every stripe through hec_rs_update's checks, in its order, before any work.
+int hec_rs_update_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens,
+                        const uint8_t* const* new_data, size_t n_stripes, size_t* bad_index) {
+    if (!rs || (n_stripes && (!shards || !lens || !new_data))) return fail(HEC_ERR_INVALID_ARGUMENT, "null argument");
+    const int k = rs->k, n = rs->n;
+    if (bad_index) *bad_index = n_stripes;
+    std::vector<hec::UpdateJob> jobs;
+    std::vector<size_t> act;
+    for (size_t s = 0; s < n_stripes; ++s) {
+        uint8_t* const* sh = shards + s * n;
+        const size_t* ln = lens + s * n;
+        const uint8_t* const* nd = new_data + s * k;
+        int err = HEC_OK;
+        const char* what = nullptr;
+        uint32_t mask = 0;
+        bool any = false;
+        for (int i = 0; i < n && !err; ++i) {
+            const bool used = i >= k || nd[i];
+            if (i < k && used) {
+                any = true;
+                if (i < 32) mask |= 1u << i;  // the RS(10,4) path's; k may be up to 255
+            }
+            if (used && !sh[i]) {
+                err = HEC_ERR_INVALID_ARGUMENT;
+                what = i < k ? "changed shard without its old buffer" : "null parity shard";
+            }
+        }
+        size_t L = 0;
+        for (int i = 0; i < n && !err; ++i) {
+            if (i < k && !nd[i]) continue;
+            if (ln[i] == 0) err = HEC_ERR_EMPTY_SHARD;
+            else if (L && ln[i] != L) err = HEC_ERR_INCORRECT_SHARD_SIZE;
+            L = ln[i];
+        }
+        if (!err && L > 0xFFFFFFFFull) {
+            err = HEC_ERR_INVALID_ARGUMENT;
+            what = "shard length above 2^32 - 1";
+        }
+        if (err) {
+            if (bad_index) *bad_index = s;
+            return fail(err, "stripe " + std::to_string(s) + (what ? std::string(": ") + what : std::string()));
+        }
+        if (!any) continue;  // nothing changed: the stripe is skipped untouched
+        act.push_back(s);
+        jobs.push_back(hec::UpdateJob{L, mask, sh, nd});
+    }
+    if (act.empty()) return HEC_OK;
+    // Other geometries: one host-API update per active stripe (generic path).
+    if (!(k == 10 && rs->m == 4)) {
+        for (size_t s : act) {
+            const int rc = hec_rs_update(rs, shards + s * n, lens + s * n, new_data + s * k, size_t(n));
+            if (rc) {
+                if (bad_index) *bad_index = s;
+                return rc;
+            }
+        }
+        return HEC_OK;
+    }
+    return hec::compact_update_104(rs, jobs);
+}
 
 int hec_gpu_correct_ragged(const hec_rs_t* rs, uint8_t* d_base, const hec_stripe_desc* descs, uint32_t n_stripes,
                            uint32_t min_spares, uint32_t* d_check, uint32_t* d_suspects, uint32_t* d_bad_stripes,

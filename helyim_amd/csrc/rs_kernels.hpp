@@ -28,8 +28,8 @@ constexpr int kThreads = 256;               // 4 waves of 64 lanes
 // HEC_MAX_LAUNCH_BLOCKS / HEC_LOCATE_MAX_BLOCKS: test builds only (the
 // Makefile's smallgrid variant), so that batches of a few hundred stripes go
 // in several launches, grid-stride iterations and mask rounds. The shipped
-// library defines neither. Only rs_kernels.hip reads the two limits, the one
-// file that variant recompiles.
+// library defines neither. Only rs_kernels.hip and rs_update_ragged.hip read
+// the limits, the files that variant recompiles.
 #ifdef HEC_MAX_LAUNCH_BLOCKS
 constexpr uint64_t kMaxLaunchBlocks = HEC_MAX_LAUNCH_BLOCKS;
 #else
@@ -119,6 +119,39 @@ constexpr uint32_t kBsChunk = 2 * kThreads * kVecBytes;  // 8 KiB
 constexpr uint32_t kNarrowChunk = kThreads * 8;  // 2 KiB
 hipError_t launch_rs104_bs_ragged(const RaggedArgs& a, hipStream_t stream);
 
+// Ragged update (hec.h hec_gpu_update_ragged): the update of UpdateArgs below
+// with every stripe's own length, mask and place in three arenas. An item is
+// hec_update_desc's fields plus first_block, a struct of its own: RaggedItem's
+// 40 bytes are the indexing of the other ragged kernels. Parity shard j of the
+// stripe is at a.base + par_off + j * par_stride; data shard c at new_base +
+// new_off + c * new_stride and old_base + old_off + c * old_stride (read only
+// with an old arena). a.compact (the host batch, no old arena): the new arena
+// holds the shards of U alone, the q-th set bit of U at new_off + q * new_stride.
+struct UpdateItem {
+    uint64_t par_off, par_stride;
+    uint64_t new_off, new_stride;
+    uint64_t old_off, old_stride;
+    uint32_t len;
+    uint32_t mask;         // update mask; bits 10..31 mean nothing
+    uint32_t first_block;
+    uint32_t pad;
+};
+static_assert(sizeof(UpdateItem) == 64, "UpdateItem is indexed by the kernel and filled by the host");
+// a: base = the parity arena, the workgroup map (one entry per 4 KiB column
+// range of every stripe with U non-empty, none for the others), tabs = the
+// RS(10,4) ENCODE plan's tables, the launcher's fields and the completion
+// signal; a.items and a.one are not read (a.inline_one: `one` below).
+struct RaggedUpdateArgs {
+    RaggedArgs a;
+    const uint8_t* new_base;
+    const uint8_t* old_base;  // nullptr: old is zero
+    const UpdateItem* items;
+    UpdateItem one;
+};
+hipError_t launch_ragged_update(const RaggedUpdateArgs& v, hipStream_t stream);
+// Name of the kernel launch_ragged_update runs without a.compact.
+const char* ragged_update_kernel_name(bool has_old);
+
 
 // Launch one coding pass. nin: number of inputs the caller guarantees (10
 // selects the unrolled helyim RS(10,4) path; anything else the generic loop).
@@ -168,6 +201,7 @@ struct UpdateArgs {
     const uint8_t* old_base = nullptr;
     uint64_t old_stripe = 0, old_shard = 0;
 };
+constexpr uint32_t kUpdateBits = 0x3FFu;  // data shards 0..9; the other mask bits mean nothing
 // aligned: every base and stride of the three arenas 16-byte aligned.
 hipError_t launch_update(const UpdateArgs& v, bool aligned, hipStream_t stream);
 // Name of the kernel an aligned update of one stripe of this shard length runs.

@@ -106,6 +106,41 @@ class ReedSolomon:
                 raise ValueError(f"new_data[{i}] has {w.size} bytes, the old shard {olds[i].size}")
         check(lib.hec_rs_update(self._h, _ptr_array(olds), _len_array(olds), _ptr_array(news), len(olds)))
 
+    def update_batch(self, stripes: Sequence) -> None:
+        """update() over many independent stripes (any lengths) in one GPU
+        round trip -- the batched form of the small write
+        (hec_rs_update_batch). ``stripes``: (shards, new_data) pairs, each as
+        update() takes them. Raises the first failing stripe's error
+        (attribute .stripe) with nothing written; a stripe with no changed
+        shard is skipped untouched."""
+        n = self.total_shard_count()
+        flat_old: List[Optional[np.ndarray]] = []
+        flat_new: List[Optional[np.ndarray]] = []
+        for si, (shards, new_data) in enumerate(stripes):
+            olds = [None if s is None else _as_u8(s) for s in shards]
+            news = [None if s is None else _as_u8(s) for s in new_data]
+            if len(olds) != n:
+                from .errors import TooFewShards, TooManyShards
+                err = TooFewShards() if len(olds) < n else TooManyShards()
+                err.stripe = si
+                raise err
+            if len(news) != self._k:
+                raise ValueError(f"stripe {si}: {len(news)} new_data entries for {self._k} data shards")
+            for i, w in enumerate(news):
+                if w is not None and olds[i] is not None and olds[i].size != w.size:
+                    raise ValueError(f"stripe {si}: new_data[{i}] has {w.size} bytes, the old shard {olds[i].size}")
+            flat_old.extend(olds)
+            flat_new.extend(news)
+        bad = ctypes.c_size_t(0)
+        rc = lib.hec_rs_update_batch(self._h, _ptr_array(flat_old), _len_array(flat_old), _ptr_array(flat_new),
+                                     len(stripes), ctypes.byref(bad))
+        if rc:
+            try:
+                check(rc)
+            except Exception as e:
+                e.stripe = int(bad.value)
+                raise
+
     def reconstruct(self, shards: MutableSequence[Optional[object]]) -> None:
         self._reconstruct(shards, data_only=False)
 

@@ -215,6 +215,32 @@ int hec_rs_reconstruct_some_batch(const hec_rs_t* rs, uint8_t* const* shards, co
 int hec_rs_update(const hec_rs_t* rs, uint8_t* const* shards, const size_t* shard_lens,
                   const uint8_t* const* new_data, size_t n_shards);
 
+/* Batched hec_rs_update over n_stripes independent stripes of any lengths in
+ * ONE GPU round trip, as hec_rs_reconstruct_batch is for degraded reads: the
+ * small-write path, byte ranges of a few hundred bytes to a few MiB that each
+ * touch one or two data shards. shards / lens are n_stripes * total entries,
+ * stripe-major; new_data is n_stripes * data entries. Per stripe the semantics
+ * and errors are hec_rs_update's, in its order. Every stripe is validated
+ * before any work; on error nothing is written and *bad_index (optional) names
+ * the first failing stripe; it is n_stripes on success. A stripe with no
+ * non-NULL new_data entry is skipped untouched (and a batch of such stripes
+ * needs no device). Null rs, or n_stripes > 0 with a null array:
+ * HEC_ERR_INVALID_ARGUMENT; a shard length in use above 2^32 - 1 likewise.
+ * RS(10,4): the deltas old ^ new of the changed shards are packed compactly
+ * into pinned staging with the four parity shards behind them, one
+ * rs104_ragged_update_kernel launch runs over them (in place over PCIe with
+ * zero copy, else through one upload and one download), and the parity is
+ * copied back. Any other codec: hec_rs_update per active stripe after the
+ * validation pass. Synchronous: nothing queued is in flight on return, error
+ * returns included.
+ * Measured on one MI355X, 1024 updates of 4 KiB shards with one changed shard,
+ * wall clock, medians (min..max) of 9 alternating rounds
+ * (tools/bench_update_ragged.py,
+ * profiles/update_ragged/bench_update_ragged.json): 1024 hec_rs_update calls
+ * 14.35 ms (14.12..14.47); one hec_rs_update_batch 1.78 ms (1.69..1.86). */
+int hec_rs_update_batch(const hec_rs_t* rs, uint8_t* const* shards, const size_t* lens,
+                        const uint8_t* const* new_data, size_t n_stripes, size_t* bad_index);
+
 /* ---- device-resident batches (no reference counterpart: the GPU form of the
  * encode_data_one_batch loop, encoder.rs:158-198, over many stripes) -------
  * Shard (stripe s, shard i) lives at base + s*stripe_stride + i*shard_stride.
@@ -975,6 +1001,60 @@ int hec_gpu_reconstruct_corrected_ragged(const hec_rs_t* rs, uint8_t* d_base, co
                                          uint32_t* d_suspects, uint32_t* d_use_masks, uint32_t* d_bad_stripes,
                                          uint32_t* d_unrepaired, unsigned long long* d_corrected_bytes, void* stream);
 
+/* Ragged update (RS(10,4)): hec_gpu_update_batch over stripes of mixed
+ * lengths in one launch -- small writes arrive as byte ranges of their own
+ * lengths, not as n_stripes equal stripes. Per stripe the contract is exactly
+ * hec_gpu_update_batch's (what is read, what is written, d_old == NULL as the
+ * accumulate form, no commit, no overlap of d_parity with a data arena),
+ * evaluated with that stripe's own shard_len, its place in the three arenas
+ * and U = update_mask & 0x3FF; over zeroed parity, any partition of 0..9 into
+ * calls without d_old gives hec_gpu_encode_ragged's bytes. A stripe with U
+ * empty is not read, not written and owns no workgroup. No byte outside
+ * [0, shard_len) of the four parity shards of the stripes with U non-empty is
+ * written: not the slack up to the stride, not a gap, not d_old or d_new.
+ * Three arenas, so the in-place ragged layout and separate buffers both fit:
+ * a stripe of an arena hec_gpu_encode_ragged made with descriptor d passes
+ * d_old = d_parity = d_base, old_offset = d.offset, parity_offset = d.offset +
+ * 10 * d.shard_stride and both strides d.shard_stride.
+ * Alignment as the ragged family: the three bases and every offset and stride
+ * 16-byte aligned, each stride >= shard_len >= 1. descs are HOST memory; the
+ * call is asynchronous on `stream`; the host waits only as the other ragged
+ * calls do (the metadata slot used four ragged calls ago, the first plan
+ * upload on a device) and nothing else is allocated.
+ * Errors, all before any device work, in the ragged calls' order: a null rs,
+ * d_new or d_parity, also with n_stripes == 0, or null descs with n_stripes >
+ * 0 (HEC_ERR_INVALID_ARGUMENT); any codec but RS(10,4)
+ * (HEC_ERR_INVALID_ARGUMENT, detail "RS(10,4) only"); then per descriptor in
+ * index order, whatever its mask: shard_len == 0 (HEC_ERR_EMPTY_SHARD, detail
+ * names the stripe); a misaligned base, offset or stride, a stride below
+ * shard_len, or an extent (offset + 10 * stride; + 4 * for the parity) that
+ * wraps 64 bits, in the parity and new arenas and, only when d_old is given,
+ * the old one (HEC_ERR_INVALID_ARGUMENT, detail names the stripe); more than
+ * 2^32 column ranges of 4 KiB in total (HEC_ERR_INVALID_ARGUMENT). With valid
+ * pointers n_stripes == 0 returns HEC_OK and writes nothing.
+ * The kernel is rs104_ragged_update_kernel (hec_update_ragged_kernel_name):
+ * one workgroup per 4 KiB column range of a stripe with U non-empty, dealt to
+ * the XCDs in eighths, launches of at most 2^23 workgroups.
+ * Measured on one MI355X, medians (min..max) of 9 alternating rounds, HIP
+ * events, the map's upload included (tools/bench_update_ragged.py,
+ * profiles/update_ragged/bench_update_ragged.json). 4096 x 1 MiB stripes with
+ * the 64 KiB pad, d_old given, |U| = 1: hec_gpu_update_batch 6.95 ms
+ * (6.94..6.98), this call on the same bytes 7.14 (7.12..7.55), 1.027x, outside
+ * the strided call's spread: a batch of one length is cheaper there. 2048
+ * stripes of 64 KiB..4 MiB: hec_gpu_encode_ragged 4.83 ms (4.81..4.89); with
+ * d_old, |U| = 1: 3.37 (3.36..3.38), 0.697 of the encode where the bytes say
+ * 10/14; |U| = 2: 4.04; |U| = 3: 4.73; without d_old, |U| = 1: 3.02. Every
+ * update leg moves 6.10 to 6.15 TB/s. */
+typedef struct hec_update_desc {
+    uint64_t parity_offset, parity_stride; /* parity shard j (0..3) at d_parity + parity_offset + j*parity_stride */
+    uint64_t new_offset,    new_stride;    /* new data shard c (shard id 0..9) at d_new + new_offset + c*new_stride */
+    uint64_t old_offset,    old_stride;    /* old data shard c likewise in d_old; ignored when d_old == NULL */
+    uint32_t shard_len;
+    uint32_t update_mask;                  /* bit c = data shard c changed; bits 10..31 mean nothing */
+} hec_update_desc;                         /* 56 bytes */
+int hec_gpu_update_ragged(const hec_rs_t* rs, const uint8_t* d_old, const uint8_t* d_new, uint8_t* d_parity,
+                          const hec_update_desc* descs, uint32_t n_stripes, void* stream);
+
 /* Deterministic splitmix64 stripe data (bench / test inputs): stripe s gets
  * bytes_per_stripe bytes at d_base + s*stripe_stride, 64-bit word n (n >= 1)
  * = splitmix64_mix(seed_base + s + n * 0x9E3779B97F4A7C15), little endian. */
@@ -1275,6 +1355,8 @@ const char* hec_reconstruct_some_batch_kernel_name(const uint8_t* d_shards, uint
                                                    uint32_t n_stripes);
 /* Same for a 16-byte-aligned hec_gpu_update_batch of one stripe. */
 const char* hec_update_kernel_name(uint64_t shard_len);
+/* Kernel hec_gpu_update_ragged runs with d_old given (with_old != 0) or NULL. */
+const char* hec_update_ragged_kernel_name(int with_old);
 /* Same for a 16-byte-aligned RS(10,4) device batch verify. */
 const char* hec_verify_kernel_name(uint64_t shard_len);
 /* Same for a 16-byte-aligned hec_gpu_verify_present_batch (masked verify). */

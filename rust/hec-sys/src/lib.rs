@@ -42,6 +42,21 @@ pub struct hec_interval {
     pub reserved: u32,
 }
 
+/// One stripe of a ragged update (hec_gpu_update_ragged): its place in the
+/// parity, new-data and old-data arenas, its length and its update mask.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct hec_update_desc {
+    pub parity_offset: u64,
+    pub parity_stride: u64,
+    pub new_offset: u64,
+    pub new_stride: u64,
+    pub old_offset: u64,
+    pub old_stride: u64,
+    pub shard_len: u32,
+    pub update_mask: u32,
+}
+
 /// One stripe of a ragged device batch.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -141,6 +156,8 @@ extern "C" {
                                          bad_index: *mut usize) -> c_int;
     pub fn hec_rs_update(rs: *const hec_rs_t, shards: *const *mut u8, shard_lens: *const usize,
                          new_data: *const *const u8, n_shards: usize) -> c_int;
+    pub fn hec_rs_update_batch(rs: *const hec_rs_t, shards: *const *mut u8, lens: *const usize,
+                               new_data: *const *const u8, n_stripes: usize, bad_index: *mut usize) -> c_int;
 
     // device-resident and host-memory stripe batches
     pub fn hec_gpu_update_batch(rs: *const hec_rs_t, d_old: *const u8, old_stripe_stride: u64,
@@ -244,6 +261,8 @@ extern "C" {
                                             h_shards: *mut u8, stripe_stride: u64, shard_stride: u64,
                                             shard_len: u64, n_stripes: u32, h_present_masks: *const u32,
                                             n_bad_stripes: *mut u32) -> c_int;
+    pub fn hec_gpu_update_ragged(rs: *const hec_rs_t, d_old: *const u8, d_new: *const u8, d_parity: *mut u8,
+                                 descs: *const hec_update_desc, n_stripes: u32, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_encode_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
                                  n_stripes: u32, stream: *mut c_void) -> c_int;
     pub fn hec_gpu_reconstruct_ragged(rs: *const hec_rs_t, d_base: *mut u8, descs: *const hec_stripe_desc,
@@ -345,6 +364,7 @@ extern "C" {
     pub fn hec_decode_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_reconstruct_some_kernel_name(shard_len: u64) -> *const c_char;
     pub fn hec_update_kernel_name(shard_len: u64) -> *const c_char;
+    pub fn hec_update_ragged_kernel_name(with_old: c_int) -> *const c_char;
     pub fn hec_reconstruct_some_batch_kernel_name(d_shards: *const u8, stripe_stride: u64, shard_stride: u64,
                                                   shard_len: u64, n_stripes: u32) -> *const c_char;
     pub fn hec_verify_kernel_name(shard_len: u64) -> *const c_char;

@@ -267,6 +267,58 @@ impl ReedSolomon {
         }
         Ok(())
     }
+
+    /// Many independent small writes in ONE GPU round trip
+    /// (hec_rs_update_batch): stripe j is `stripes[j] = (shards, new_data)`.
+    /// `shards` has total entries: a data entry is the OLD shard, needed only
+    /// where `new_data` has an entry (`None` elsewhere is fine); the parity
+    /// entries are all required and are updated in place, parity ^= P[:,U] *
+    /// (old ^ new). `new_data` has data_shard_count entries, `None` =
+    /// unchanged; a stripe with none changed is skipped untouched. Neither old
+    /// nor new data is written. On error nothing is written and the error names
+    /// the first failing stripe.
+    #[allow(clippy::type_complexity)]
+    pub fn update_batch(&self, stripes: &mut [(Vec<Option<Vec<u8>>>, Vec<Option<Vec<u8>>>)])
+                        -> Result<(), (Error, usize)> {
+        let (n, k) = (self.total_shard_count(), self.data_shard_count());
+        // hec_rs_update_batch reads exactly n and k entries per stripe
+        for (j, (shards, new_data)) in stripes.iter().enumerate() {
+            if shards.len() < n || new_data.len() < k {
+                return Err((Error::TooFewShards, j));
+            }
+            if shards.len() > n || new_data.len() > k {
+                return Err((Error::TooManyShards, j));
+            }
+            // the C call reads lens[c] bytes of new_data[c]
+            for c in 0..k {
+                if let (Some(o), Some(w)) = (&shards[c], &new_data[c]) {
+                    if o.len() != w.len() {
+                        return Err((Error::IncorrectShardSize, j));
+                    }
+                }
+            }
+        }
+        let mut ptrs: Vec<*mut u8> = Vec::with_capacity(stripes.len() * n);
+        let mut lens: Vec<usize> = Vec::with_capacity(stripes.len() * n);
+        let mut news: Vec<*const u8> = Vec::with_capacity(stripes.len() * k);
+        for (shards, new_data) in stripes.iter_mut() {
+            for b in shards.iter_mut() {
+                lens.push(b.as_ref().map_or(0, |v| v.len()));
+                ptrs.push(b.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr()));
+            }
+            for w in new_data.iter() {
+                news.push(w.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()));
+            }
+        }
+        let mut bad = 0usize;
+        let rc = unsafe {
+            sys::hec_rs_update_batch(self.0, ptrs.as_ptr(), lens.as_ptr(), news.as_ptr(), stripes.len(), &mut bad)
+        };
+        if rc != 0 {
+            return Err((to_err(rc), bad));
+        }
+        Ok(())
+    }
 }
 
 /// The shard slots `reconstruct` accepts (upstream `ReconstructShard<F>` for
